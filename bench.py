@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: embeddings/sec @ bs=256 on InceptionResnetV1 (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,14 @@ rank embeds its own 256 crops (weak scaling, no data-path collective) and the ra
 resulting (256,512) fp32 embeddings with one RCCL all-gather per step, overlapped with the next
 step.  Rank 0 prints ONE JSON line.
 
-The default run (no --workload) carries, inside that one line:
+A plain run (no --full) is lean: set-up, W warm-up steps, the K timed steps of the headline leg and its line (value,
+ms_per_step, roofline from the same timed steps).  --dump-outputs DIR then writes what the last timed step computed:
+DIR/embeddings.npy, rank 0's (256, 512) fp32 embeddings, and with N > 1 DIR/embeddings_gathered.npy, the all-gathered
+(N*256, 512) block (embed workload only).
+
+--full adds everything else the benchmark measures or checks: the CPU baselines, the parity record and the pinned
+embedding checksum, the pipeline legs' per-kernel stage times, and in the default workload the legs listed below.
+The --full run (no --workload) carries, inside that one line:
   * the headline leg (value / ms_per_step / roofline / cpu_baseline): bf16, BASELINE configs[1]; "in_gate": the rate of
     the f16x2 (split-f16) path that meets the 1e-4 gate, promoted from the legs;
   * "parity": measured L2 error of the timed dtype against the reference's own embeddings (tests/golden/
@@ -288,7 +295,7 @@ def pipeline_leg(args, rank, world, local, steps, warmup, lanes, want_cpu, dtype
         dt = time.perf_counter() - t1
         h2d = {"frames_per_s": round(8 * NF / dt, 1), "GBps": round(8 * host[0].numel() / dt / 1e9, 2)}
     stage_ms = None
-    if rank == 0 and hasattr(det[0], "stage_times") and not from_host:
+    if rank == 0 and args.full and hasattr(det[0], "stage_times") and not from_host:
         stage_ms = det[0].stage_times(batches[0])
     out = None
     if rank == 0:
@@ -359,10 +366,10 @@ def agree(failed, world, dev):
     return bool(t.item() > 0)
 
 
-def embed_leg(args, dtype, rank, world, dev, n_lanes, steps, warmup, want_cpu, with_parity=True, model_name=None):
+def embed_leg(args, dtype, rank, world, dev, n_lanes, steps, warmup, want_cpu, with_parity=True, model_name=None, dump=None):
     """Time the embed path in one compute dtype: `warmup` untimed + exactly `steps` timed steps bracketed by barrier +
-    synchronize; consecutive (independent) batches rotate over `n_lanes` streams / activation contexts.  Returns the
-    result dict (rank 0) or None."""
+    synchronize; consecutive (independent) batches rotate over `n_lanes` streams / activation contexts.  `dump`: a
+    directory that receives the last timed step's embeddings (.npy, fp32).  Returns the result dict (rank 0) or None."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -443,12 +450,19 @@ def embed_leg(args, dtype, rank, world, dev, n_lanes, steps, warmup, want_cpu, w
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
     emb_timed = emb.clone()
-    checksum = float(emb_timed.double().abs().sum().item())
-    want = CHECKSUMS.get((model_name, dtype))
-    bad = not (checksum == checksum) or (want is not None and rank == 0 and abs(checksum - want) > 1e-9 * want)
-    if agree(bad, world, dev):      # every rank leaves together: nobody waits in the next barrier for a rank that exited
-        raise LegError("embedding checksum %.12f of the timed configuration (rank %d) differs from the pinned %r, or is not finite "
-                       "on some rank" % (checksum, rank, want))
+    if dump and rank == 0:
+        os.makedirs(dump, exist_ok=True)
+        np.save(os.path.join(dump, "embeddings.npy"), emb_timed.float().cpu().numpy())
+        if world > 1:
+            np.save(os.path.join(dump, "embeddings_gathered.npy"), gathered[(steps - 1) & 1].float().cpu().numpy())
+    checksum = None
+    if args.full:
+        checksum = float(emb_timed.double().abs().sum().item())
+        want = CHECKSUMS.get((model_name, dtype))
+        bad = not (checksum == checksum) or (want is not None and rank == 0 and abs(checksum - want) > 1e-9 * want)
+        if agree(bad, world, dev):      # every rank leaves together: nobody waits in the next barrier for a rank that exited
+            raise LegError("embedding checksum %.12f of the timed configuration (rank %d) differs from the pinned %r, or is not "
+                           "finite on some rank" % (checksum, rank, want))
 
     out = None
     if rank == 0:
@@ -514,8 +528,13 @@ def embed_leg(args, dtype, rank, world, dev, n_lanes, steps, warmup, want_cpu, w
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="all", choices=["all", "embed", "pipeline", "stream", "detect"],
-                    help="all (default): the embed headline leg + the other legs + the pipeline legs in ONE JSON line; "
-                         "embed / pipeline / stream (pipeline from pinned host memory) / detect: that leg alone")
+                    help="all (default): the embed headline leg; with --full also the other legs + the pipeline legs in ONE "
+                         "JSON line; embed / pipeline / stream (pipeline from pinned host memory) / detect: that leg alone")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, parity and checksum checks, "
+                         "per-kernel stage times and, in the default workload, the other dtype / model / pipeline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--embed-batch", type=int, default=256,
                     help="pipeline workload: faces of consecutive frame batches are embedded together once this many wait "
                          "(0: every frame batch on its own)")
@@ -537,6 +556,10 @@ def main():
                     help="irv1 = BASELINE configs[1] (default); ir100 = configs[4], the ArcFace IR-100 swap-in")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload not in ("all", "embed"):
+        raise SystemExit("--dump-outputs writes the embed leg's outputs: use it with --workload all or embed")
     if args.workload == "detect":
         return run_detect(args)
 
@@ -549,9 +572,11 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with torch.distributed.run" % (args.gpus, world))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    want_cpu = not args.no_cpu_baseline
+    want_cpu = args.full and not args.no_cpu_baseline
     emb_lanes = args.lanes if args.lanes > 0 else 3
     pipe_lanes = args.lanes if args.lanes > 0 else 1
+    # the default workload's side legs (other dtypes / models, pipeline, stream) run with --full only
+    side = args.workload == "all" and args.full
 
     out = None
     p = None
@@ -573,15 +598,16 @@ def main():
 
     # legs of one process share the package's process-wide side streams (streams.py): with fresh streams per leg the
     # second leg's streams could share a hardware queue and lose 15-20 %
-    if args.workload in ("all", "pipeline") and pipe_first:
+    if (side or args.workload == "pipeline") and pipe_first:
         p = run_pipeline()
     if args.workload in ("all", "embed"):
-        out = embed_leg(args, args.dtype, rank, world, dev, emb_lanes, args.steps, args.warmup, want_cpu)
+        out = embed_leg(args, args.dtype, rank, world, dev, emb_lanes, args.steps, args.warmup, want_cpu,
+                        with_parity=args.full, dump=args.dump_outputs)
     # the pipeline leg runs right behind the headline leg: after the minute of side legs below the chip holds a lower
     # clock (MI355X_MICROARCH.md, DVFS) and the same leg reads 8-9 % lower (87 k against 95 k faces/s)
-    if args.workload == "all" and not pipe_first:
+    if side and not pipe_first:
         p = run_pipeline()
-    if args.workload == "all" and args.model == "irv1":
+    if side and args.model == "irv1":
         # the other compute dtypes: shorter legs (the f32 leg runs ~7 ms steps), no CPU baseline; then the headline dtype
         # on ONE lane (no overlap of independent batches) and BASELINE configs[4] (IR-100 swap-in encoder)
         legs = {}
@@ -608,12 +634,12 @@ def main():
         p = run_pipeline()
     if args.workload == "stream":
         p = run_pipeline(dtype=args.dtype, from_host=True)
-    if rank == 0 and args.workload in ("all", "pipeline", "stream"):
+    if rank == 0 and (side or args.workload in ("pipeline", "stream")):
         if args.workload in ("pipeline", "stream"):
             out = p
         else:
             out["pipeline"] = p
-    if args.workload == "all":
+    if side:
         # the same pipeline with the in-gate encoder (what the CLIs run by default), then from pinned host memory
         q = run_pipeline(dtype="f16x2", cpu=False)
         r = run_pipeline(dtype="f16x2", from_host=True, cpu=False)

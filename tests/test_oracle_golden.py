@@ -42,7 +42,9 @@ def test_mlp_oracle_matches_reference():
     g = np.load(os.path.join(GOLDEN, "mlp_seed0.npz"))
     e = torch.nn.functional.normalize(seeded_normal((32, 512), g["input_seed"]), dim=1)
     lp = mlp.mlp_forward(generate_state_dict("mlp", 0, as_torch=True), e).numpy()
-    assert np.abs(lp - g["logp"]).max() <= 1e-5
+    # fp32 GEMM: MKL picks its kernels by host CPU, and another summation order moves |logp| up to 40 by a few ulp
+    # (1.1e-5 at -25 on MKL's generic x86 path); 1e-5 + 1e-6 |logp| admits that and nothing a formula error could hide
+    np.testing.assert_allclose(lp, g["logp"], rtol=1e-6, atol=1e-5)
 
 
 def test_identify_person_threshold_and_unknown():
@@ -136,7 +138,10 @@ def _retina_inputs():
 
 def test_retina_oracle_matches_reference():
     """oracle/retina.py against the reference's RetinaFace run in the build container (tools/make_golden.py
-    golden_retina): raw heads bit-exact, detections bit-exact under both tie rules (the fixtures hold no tied scores)."""
+    golden_retina): raw heads bit-exact, detections bit-exact under both tie rules (the fixtures hold no tied scores)
+    except the last bit of coordinates: decode's torch.exp runs on MKL's vector math and MKL picks its kernels by host
+    CPU (1 ulp of the frame's larger side on MKL's generic x86 path), so boxes, and the 720p picture's landmarks, are
+    held to 2 ulp of that side."""
     import hashlib
     from oracle import retina
     g = np.load(os.path.join(GOLDEN, "retina_ref.npz"))
@@ -154,13 +159,15 @@ def test_retina_oracle_matches_reference():
         dets, scores, lms = retina.inference(sd, list(frames), ties=ties)
         for i in range(2):
             assert len(scores[i]) == meta["synth"]["n"][i] > 20
-            assert np.array_equal(dets[i], g["synth/%d/boxes" % i])
+            assert dets[i].shape == g["synth/%d/boxes" % i].shape
+            assert np.abs(dets[i] - g["synth/%d/boxes" % i]).max() <= 2 * np.spacing(np.float32(max(frames[i].shape[:2])))
             assert np.array_equal(scores[i], g["synth/%d/scores" % i])
             assert np.array_equal(lms[i], g["synth/%d/points" % i])
     img = load_image("hoai_linh_4_recog.jpg")
     dets, scores, lms = retina.inference(sd, [img], ties="table")
-    assert np.array_equal(dets[0], g["hoai_linh_4_recog.jpg/0/boxes"])
-    assert np.array_equal(lms[0], g["hoai_linh_4_recog.jpg/0/points"])
+    assert dets[0].shape == g["hoai_linh_4_recog.jpg/0/boxes"].shape
+    assert np.abs(dets[0] - g["hoai_linh_4_recog.jpg/0/boxes"]).max() <= 2 * np.spacing(np.float32(max(img.shape[:2])))
+    assert np.abs(lms[0] - g["hoai_linh_4_recog.jpg/0/points"]).max() <= 2 * np.spacing(np.float32(max(img.shape[:2])))
     d2, s2 = retina.inference(sd, [img], landmark=False)
     assert np.array_equal(d2[0], dets[0]) and np.array_equal(s2[0], scores[0])
 

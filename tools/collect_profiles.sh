@@ -34,20 +34,20 @@ python tools/layer_trace.py $OUT/plan_f16x2.txt $OUT/kt_layers_x/l_kernel_trace.
 python tools/pmc_table.py $OUT/pmc_s/s_counter_collection.csv 0.02 > $OUT/${R}_sq_wait_states_bf16.txt || exit 1
 cp $OUT/${R}_traffic.json $ROOT/profiles/${R}_traffic.json   # bench.py quotes it in roofline.traffic
 # 3. the bench lines
-python bench.py > $OUT/${R}_bench.json 2> $OUT/bench.err || exit 1
-python bench.py --workload detect --detectors 2 > $OUT/${R}_bench_detect.json 2>/dev/null || exit 1
-python bench.py --workload embed --model ir100 --no-cpu-baseline > $OUT/${R}_bench_ir100.json 2>/dev/null || exit 1
+python bench.py --full > $OUT/${R}_bench.json 2> $OUT/bench.err || exit 1
+python bench.py --full --workload detect --detectors 2 > $OUT/${R}_bench_detect.json 2>/dev/null || exit 1
+python bench.py --full --workload embed --model ir100 --no-cpu-baseline > $OUT/${R}_bench_ir100.json 2>/dev/null || exit 1
 python tools/run_layers.py bf16 2>/dev/null | grep -av amdgpu.ids > $OUT/${R}_irv1_bs256_bf16_layer_times.txt || exit 1   # one lane, no internal half-batch forks
 python tools/run_layers.py f16x2 2>/dev/null | grep -av amdgpu.ids > $OUT/${R}_irv1_bs256_f16x2_layer_times.txt || exit 1
-python bench.py --workload stream --dtype f16x2 --no-cpu-baseline > $OUT/${R}_bench_stream_f16x2.json 2>/dev/null || exit 1
-python bench.py --workload stream --no-cpu-baseline > $OUT/${R}_bench_stream_bf16.json 2>/dev/null || exit 1   # bf16: compute no longer hides the PCIe ceiling
-python bench.py --workload pipeline --detectors 1 --no-cpu-baseline > $OUT/${R}_bench_pipeline_1handle.json 2>/dev/null || exit 1   # the default line uses two handles
+python bench.py --full --workload stream --dtype f16x2 --no-cpu-baseline > $OUT/${R}_bench_stream_f16x2.json 2>/dev/null || exit 1
+python bench.py --full --workload stream --no-cpu-baseline > $OUT/${R}_bench_stream_bf16.json 2>/dev/null || exit 1   # bf16: compute no longer hides the PCIe ceiling
+python bench.py --full --workload pipeline --detectors 1 --no-cpu-baseline > $OUT/${R}_bench_pipeline_1handle.json 2>/dev/null || exit 1   # the default line uses two handles
 # 3b. detector stage / layer tables (MTCNN cascade on 16 x 1080p; RetinaFace swap-in detector)
 python tools/mtcnn_layers.py > $OUT/${R}_mtcnn_stage_times.txt 2>&1 || exit 1
 VNF_RETINA_LAYERS=1 python tools/retina_time.py 1080 1920 16 3 > $OUT/${R}_retina_1080p.txt 2>&1 || exit 1
 # 4. kernel-trace summary of the same default bench command (embed legs + pipeline leg)
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o b --output-format csv -- python3 $ROOT/bench.py --no-cpu-baseline --legs "" > $OUT/kt_bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o b --output-format csv -- python3 $ROOT/bench.py --full --no-cpu-baseline --legs "" > $OUT/kt_bench.log 2>&1 || exit 1
 cp $OUT/kt_bench/b_kernel_stats.csv $OUT/${R}_bench_kernel_stats.csv
 rm -rf $OUT/pmc_f $OUT/pmc_w $OUT/pmc_m/*trace* $OUT/pmc_s $OUT/kt_layers $OUT/kt_layers_x $OUT/kt_bench/*trace*
 ls $OUT

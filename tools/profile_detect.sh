@@ -6,7 +6,7 @@ TAG=${1:-det}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $OUT -o k --output-format csv -- python3 $ROOT/bench.py --workload detect --steps 50 --warmup 5 --no-cpu-baseline > $OUT/run.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT -o k --output-format csv -- python3 $ROOT/bench.py --full --workload detect --steps 50 --warmup 5 --no-cpu-baseline > $OUT/run.log 2>&1 || exit 1
 python3 - <<PY
 import csv, glob
 rows = list(csv.DictReader(open(glob.glob("$OUT/**/k_kernel_stats.csv", recursive=True)[0])))
