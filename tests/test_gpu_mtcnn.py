@@ -16,9 +16,16 @@ with open(os.path.join(GOLDEN, "mtcnn_ref.json")) as _f:
     _MT = json.load(_f)
 
 
-@pytest.mark.parametrize("case", _MT, ids=["%s@%d" % (c["file"], c["min_face_size"]) for c in _MT])
-def test_mtcnn_matches_reference_golden(case):
+# the default cascade keeps the ids "<file>@<min face>", the exact-f32 one (VNF_MTCNN_DTYPE=f32) adds "-f32"
+@pytest.mark.parametrize("case,mtcnn_dtype", [
+    pytest.param(c, dt, id="%s@%d%s" % (c["file"], c["min_face_size"], "" if dt == "default" else "-" + dt))
+    for dt in ("default", "f32") for c in _MT])
+def test_mtcnn_matches_reference_golden(case, mtcnn_dtype, monkeypatch):
+    """Default: the split-f16 R-Net / O-Net.  f32 (VNF_MTCNN_DTYPE=f32, read when the handle is created): the exact-f32
+    cascade."""
     from vn_celeb_face_recognition_amd.models import MTCNN
+    if mtcnn_dtype == "f32":
+        monkeypatch.setenv("VNF_MTCNN_DTYPE", "f32")
     g = np.load(os.path.join(GOLDEN, "mtcnn_ref.npz"))
     key = "%s@%d" % (case["file"], case["min_face_size"])
     img = load_image(case["file"])

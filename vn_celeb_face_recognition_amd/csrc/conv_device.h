@@ -1,5 +1,5 @@
 // Device-side building blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip: LDS-DMA ring
-// kernel + register-staged fallback; conv_patch.hip: LDS-resident input patch kernel).
+// kernel; conv_patch.hip: LDS-resident input patch kernel).
 #pragma once
 #include "kernels.h"
 #include "split_f16.h"

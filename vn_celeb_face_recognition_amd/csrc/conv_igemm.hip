@@ -6,8 +6,8 @@
 //   k  = (kh, kw, c) flattened, c fastest  -> walked in 128-byte K tiles
 // A is never materialised: every 16-byte k-chunk (8 x 16-bit or 4 x f32 channels of one filter tap)
 // is gathered straight from the NHWC input (tap and channel of each lane's chunk are tracked
-// incrementally; the patch / wave-specialised / fallback kernels use the per-chunk offset table
-// ktab); padded borders and rows past M read a 16-byte zero page instead.
+// incrementally; the patch / wave-specialised kernels use the per-chunk offset table ktab);
+// padded borders and rows past M read a 16-byte zero page instead.
 //
 // Main kernel (conv_igemm_dma_kernel): both operands go global -> LDS by LDS-DMA
 // (global_load_lds_dwordx4, one 1-KiB piece = 8 rows x 128 B per wave instruction), never through
@@ -19,9 +19,6 @@
 // so bytes-in-flight per CU -- what bounds these small-K, small-N problems -- is set by LDS
 // capacity (160 KiB) instead of by register pressure.
 //
-// Fallback kernel (conv_igemm_kernel): register-staged double buffering (VNF_CONV_REG=1; the
-// first version of the core, kept as a cross-check).
-//
 // The MFMA is issued with the WEIGHT fragment as the A operand and the ACTIVATION fragment as
 // the B operand, so an accumulator register quad holds 4 consecutive output channels of one
 // pixel.  The epilogue stages fp32 accumulators through LDS and writes whole NHWC rows with
@@ -31,7 +28,6 @@
 //
 // dtype paths: bf16 / f16 -> v_mfma_f32_16x16x32_{bf16,f16}; f32 -> v_mfma_f32_16x16x4_f32
 // (exact f32 FMA chain; the <=1e-4 parity path).
-#include <cstdlib>
 #include <type_traits>
 
 #include "block35.h"
@@ -281,77 +277,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs
   conv_epilogue<T, BM, BN, WM, WN, S * STAGE>(a, acc, smem, m0, n0);
 }
 
-// ===================================================================== register-staged fallback
-template <typename T, int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256) void conv_igemm_kernel(const KArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ES = (int)sizeof(T);
-  constexpr int CH = 16 / ES, BKE = 128 / ES;
-  constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
-  constexpr int AP = BM / 32, BP = BN / 32;
-  constexpr int STAGE = (BM + BN) * 128;
-  static_assert(WM * WN == 4, "4 waves per workgroup");
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int bid = xcd_remap(blockIdx.x, a.nblk);
-  const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  const int lrow = tid >> 3, lcol = tid & 7;
-  int abase[AP], ahi[AP], awi[AP];
-  row_setup<AP, 32>(a, m0, lrow, abase, ahi, awi);
-  const char* wrow = a.w + ((size_t)(n0 + lrow) * a.Kpad + lcol * CH) * ES;
-
-  f32x4_t acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  uint4 ra[AP], rb[BP];
-  auto gload = [&](int kt) {
-    const int4 e = a.ktab[kt * 8 + lcol];
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-      const int hi = ahi[p] + e.y, wi = awi[p] + e.z;
-      const bool ok = e.w && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-      ra[p] = ok ? *reinterpret_cast<const uint4*>(a.x + (size_t)(abase[p] + e.x) * ES) : uint4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int p = 0; p < BP; ++p)
-      rb[p] = *reinterpret_cast<const uint4*>(wrow + ((size_t)(32 * p) * a.Kpad + (size_t)kt * BKE) * ES);
-  };
-  auto lstore = [&](int st) {
-    char* sA = smem + st * STAGE;
-    char* sB = sA + BM * 128;
-#pragma unroll
-    for (int p = 0; p < AP; ++p) {
-      const int row = lrow + 32 * p;
-      *reinterpret_cast<uint4*>(sA + row * 128 + ((lcol ^ (row & 7)) << 4)) = ra[p];
-    }
-#pragma unroll
-    for (int p = 0; p < BP; ++p) {
-      const int row = lrow + 32 * p;
-      *reinterpret_cast<uint4*>(sB + row * 128 + ((lcol ^ (row & 7)) << 4)) = rb[p];
-    }
-  };
-
-  gload(0);
-  lstore(0);
-  __syncthreads();
-  const int frow = lane & 15, fgrp = lane >> 4;
-  for (int kt = 0; kt < a.nkt; ++kt) {
-    const int st = kt & 1;
-    if (kt + 1 < a.nkt) gload(kt + 1);
-    const char* sA = smem + st * STAGE;
-    tile_mma<T, TM, TN>(sA, sA + BM * 128, wm * WTM, wn * WTN, frow, fgrp, a.K - kt * BKE, acc);
-    if (kt + 1 < a.nkt) lstore(st ^ 1);
-    __syncthreads();
-  }
-  conv_epilogue<T, BM, BN, WM, WN, 2 * STAGE>(a, acc, smem, m0, n0);
-}
-
 // ===================================================================== host launch
 static const char* zero_page() {  // per-device 256 zero bytes for padded / out-of-range gather sources
   static char* z[16] = {nullptr};
@@ -383,17 +308,6 @@ static hipError_t launch_dma(const KArgs& k, hipStream_t s) {
   kk.tiles_n = (k.Cout + BN - 1) / BN;
   kk.nblk = tiles_m * kk.tiles_n;
   hipLaunchKernelGGL((conv_igemm_dma_kernel<T, BM, BN, WM, WN, S>), dim3(kk.nblk), dim3(WM * WN * 64), lds, s, kk);
-  return hipGetLastError();
-}
-
-template <typename T, int BM, int BN, int WM, int WN>
-static hipError_t launch_reg(const KArgs& k, hipStream_t s) {
-  constexpr int lds = 2 * (BM + BN) * 128;
-  KArgs kk = k;
-  const int tiles_m = (k.M + BM - 1) / BM;
-  kk.tiles_n = (k.Cout + BN - 1) / BN;
-  kk.nblk = tiles_m * kk.tiles_n;
-  hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, WM, WN>), dim3(kk.nblk), dim3(256), lds, s, kk);
   return hipGetLastError();
 }
 
@@ -479,11 +393,10 @@ static hipError_t launch_cfg(int cfg, const KArgs& k, hipStream_t s) {
 
 template <typename T>
 static hipError_t launch_typed(const ConvArgs& a, const KArgs& k, hipStream_t s) {
-  static const int env_reg = getenv("VNF_CONV_REG") ? atoi(getenv("VNF_CONV_REG")) : 0;
-  if (a.cfg >= kNumCfgs + patch_num_cfgs() && !env_reg && k.zero && conv_cfg_ok(a, a.cfg))
-    return launch_ws(a, k, a.cfg - kNumCfgs - patch_num_cfgs(), s);
-  if (a.cfg >= kNumCfgs && !env_reg && k.zero && conv_cfg_ok(a, a.cfg)) return launch_patch(a, k, a.cfg - kNumCfgs, s);
-  if (a.cfg >= 0 && !env_reg && k.zero && conv_cfg_ok(a, a.cfg)) return launch_cfg<T>(a.cfg, k, s);
+  if (!k.zero) return hipErrorOutOfMemory;   // every kernel reads padded / out-of-range sources from the zero page
+  if (a.cfg >= kNumCfgs + patch_num_cfgs() && conv_cfg_ok(a, a.cfg)) return launch_ws(a, k, a.cfg - kNumCfgs - patch_num_cfgs(), s);
+  if (a.cfg >= kNumCfgs && conv_cfg_ok(a, a.cfg)) return launch_patch(a, k, a.cfg - kNumCfgs, s);
+  if (a.cfg >= 0 && conv_cfg_ok(a, a.cfg)) return launch_cfg<T>(a.cfg, k, s);
   // heuristic: BN must divide every segment boundary; keep ~2 workgroups per CU when possible
   auto fits = [&](int) { return true; };
   int bn = 128;
@@ -493,16 +406,8 @@ static hipError_t launch_typed(const ConvArgs& a, const KArgs& k, hipStream_t s)
   while (bn > 64 && blocks(128, bn) < 512) bn >>= 1;
   int bm = 128;
   if (bn <= 64 && blocks(128, bn) < 512) bm = 64;
-  if (!env_reg && k.zero) {
-    const int id = bm == 128 ? (bn == 128 ? 0 : bn == 64 ? 1 : 2) : (bn == 64 ? 3 : 4);
-    return launch_cfg<T>(id, k, s);
-  }
-  if (bm == 128 && bn == 128) return launch_reg<T, 128, 128, 2, 2>(k, s);
-  if (bm == 128 && bn == 64) return launch_reg<T, 128, 64, 2, 2>(k, s);
-  if (bm == 128 && bn == 32) return launch_reg<T, 128, 32, 4, 1>(k, s);
-  if (bm == 64 && bn == 64) return launch_reg<T, 64, 64, 2, 2>(k, s);
-  if (bm == 64 && bn == 32) return launch_reg<T, 64, 32, 2, 2>(k, s);
-  return hipErrorInvalidValue;
+  const int id = bm == 128 ? (bn == 128 ? 0 : bn == 64 ? 1 : 2) : (bn == 64 ? 3 : 4);
+  return launch_cfg<T>(id, k, s);
 }
 
 hipError_t launch_conv(const ConvArgs& a, hipStream_t s) {

@@ -143,13 +143,13 @@ ConvArgs Encoder::conv_args(const ConvLayer& L, int n0, int nn) const {
 // batch size it will see (measure, don't guess: the best tile depends on M, N, K, the number of
 // workgroups and where the operands sit in the cache hierarchy).  ~1 s at create time.
 int Encoder::autotune() {
-  static const int enabled = getenv("VNF_AUTOTUNE") ? atoi(getenv("VNF_AUTOTUNE")) : 1;
-  static const int force = getenv("VNF_FORCE_CFG") ? atoi(getenv("VNF_FORCE_CFG")) : -2;
+  const TuneEnv& te = tune_env;   // the switches as they were when the handle was created (finalize)
+  const int enabled = te.enabled, force = te.force;
   if (!enabled && force < -1) return VNF_OK;
   // VNF_TUNE_CACHE=<file>: reuse the choices of an earlier create on this device (lines "key cfg"); lets a
   // profiled run show steady-state launches only and brings create time down to the weight upload
   std::map<std::string, int> cache;
-  const char* cache_path = getenv("VNF_TUNE_CACHE");
+  const char* cache_path = te.cache.empty() ? nullptr : te.cache.c_str();
   bool cache_dirty = false;
   if (cache_path && enabled) {
     if (FILE* f = fopen(cache_path, "r")) {
@@ -162,16 +162,29 @@ int Encoder::autotune() {
   // tuning launches scribble over the activation buffers: nothing of an earlier vnf_embed may still be in flight,
   // and nothing of the tuner when the caller's launches start
   VNF_HIP(hipDeviceSynchronize());
-  hipEvent_t e0, e1;
-  VNF_HIP(hipEventCreate(&e0));
-  VNF_HIP(hipEventCreate(&e1));
+  // the timing events and lane streams, released on every way out of this function
+  struct Timers {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t lane_s[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t lane_e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Timers() {
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+      for (int l = 0; l < 4; ++l) {
+        if (lane_e[l]) (void)hipEventDestroy(lane_e[l]);
+        if (lane_s[l]) (void)hipStreamDestroy(lane_s[l]);
+      }
+    }
+  } tm;
+  VNF_HIP(hipEventCreate(&tm.e0));
+  VNF_HIP(hipEventCreate(&tm.e1));
+  hipEvent_t e0 = tm.e0, e1 = tm.e1;
+  hipStream_t* lane_s = tm.lane_s;
+  hipEvent_t* lane_e = tm.lane_e;
   // tune_lanes > 1: every candidate is timed as `tune_lanes` concurrent copies on separate streams -- the state the
   // layer actually runs in when independent batches overlap (activation contexts): alone on the GPU a small tile with
   // many workgroups looks best, beside other kernels the tile that moves fewer bytes per FLOP does
-  static const int env_lanes = getenv("VNF_TUNE_LANES") ? atoi(getenv("VNF_TUNE_LANES")) : 0;
-  const int lanes = env_lanes > 0 ? (env_lanes > 4 ? 4 : env_lanes) : (tune_lanes < 1 ? 1 : tune_lanes);
-  hipStream_t lane_s[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t lane_e[4] = {nullptr, nullptr, nullptr, nullptr};
+  const int lanes = te.lanes > 0 ? (te.lanes > 4 ? 4 : te.lanes) : (tune_lanes < 1 ? 1 : tune_lanes);
   if (lanes > 1)
     for (int l = 0; l < lanes; ++l) {
       VNF_HIP(hipStreamCreateWithFlags(&lane_s[l], hipStreamNonBlocking));
@@ -228,7 +241,7 @@ int Encoder::autotune() {
         *out_ms = ms;
         return VNF_OK;
       };
-      static const int logit = getenv("VNF_AUTOTUNE_LOG") ? atoi(getenv("VNF_AUTOTUNE_LOG")) : 0;
+      const int logit = te.log;
       for (int cfg = -1; enabled && cfg < conv_num_cfgs(); ++cfg) {
         ConvArgs a = conv_args(L, 0, nn);
         a.cfg = cfg;
@@ -243,8 +256,7 @@ int Encoder::autotune() {
       }
       // finalists: the first pass is 8 launches per candidate and two candidates a few per cent apart change places from
       // run to run; the ones within 8 % of the best are timed again, longer (VNF_TUNE_FINAL=0: first pass only)
-      static const bool finals = !(getenv("VNF_TUNE_FINAL") && atoi(getenv("VNF_TUNE_FINAL")) == 0);
-      if (finals && timed.size() > 1) {
+      if (te.finals && timed.size() > 1) {
         std::sort(timed.begin(), timed.end());
         float fbest = 1e30f;
         int fcfg = best_cfg, nfin = 0;
@@ -268,12 +280,6 @@ int Encoder::autotune() {
         if (force == -1 || conv_cfg_ok(a, force)) L.cfg = force;
       }
     }
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  for (int l = 0; l < 4; ++l) {
-    if (lane_e[l]) (void)hipEventDestroy(lane_e[l]);
-    if (lane_s[l]) (void)hipStreamDestroy(lane_s[l]);
   }
   VNF_HIP(hipDeviceSynchronize());
   if (cache_dirty) {
@@ -303,6 +309,17 @@ int Encoder::finalize() {
     if (rc != VNF_OK) return rc;
   }
   tune_dirty = true;  // the first run() picks the tiles (after any set_streams / set_contexts of the caller)
+  {
+    // the autotuner's switches, read now (at create time) although the tuning itself runs later, from run()
+    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    tune_env.enabled = env_int("VNF_AUTOTUNE", 1);
+    tune_env.force = env_int("VNF_FORCE_CFG", -2);
+    tune_env.lanes = env_int("VNF_TUNE_LANES", 0);
+    tune_env.log = env_int("VNF_AUTOTUNE_LOG", 0);
+    tune_env.finals = env_int("VNF_TUNE_FINAL", 1) != 0;
+    const char* cache = getenv("VNF_TUNE_CACHE");
+    tune_env.cache = cache ? cache : "";
+  }
   return VNF_OK;
 }
 
@@ -673,7 +690,7 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   {
     // the first convolution runs as a direct kernel on the caller's NCHW tensor (aux_kernels.hip): the layer stays
     // in `convs` for the FLOP accounting, the PACK + CONV pair of ops becomes one STEM1 op
-    static const int direct = getenv("VNF_DIRECT_STEM") ? atoi(getenv("VNF_DIRECT_STEM")) : 1;
+    const int direct = getenv("VNF_DIRECT_STEM") ? atoi(getenv("VNF_DIRECT_STEM")) : 1;
     Piece pc;
     if (direct && basic_piece(wm, "conv2d_1a", 3, 32, 3, 3, pc)) {
       std::vector<float> wt(27 * 32 + 32);
@@ -1028,21 +1045,16 @@ static void add_pool_ceil(Encoder& e, int ib, int ob, int k) {
   e.ops.push_back(op);
 }
 
-// front == true: conv1 + PReLU + pool1 are computed by the detector's own fused kernel (mtcnn.hip net_front_kernel),
-// which reads buffer 0 (the crops) and writes buffer 1 (the pooled map); the plan starts at conv2.
-// front: conv1 + pool1 come from net_front_kernel (the plan starts at conv2); mid: conv2 + pool2 as well, from
+// conv1 + PReLU + pool1 are computed by the detector's own fused kernel (mtcnn.hip net_front_kernel), which reads
+// buffer 0 (the crops) and writes buffer 1 (the pooled map); the plan starts at conv2.  mid: conv2 + pool2 as well, from
 // net_mid_kernel (mtcnn.hip: the plan starts at conv3 and reads buffer 3)
-int build_rnet(Encoder& e, WeightMap& wm, bool front, bool mid) {
+int build_rnet(Encoder& e, WeightMap& wm, bool mid) {
   e.in_size = 24;
-  const int in = e.add_buf(24, 24, 4), p1 = e.add_buf(11, 11, 32);
+  e.add_buf(24, 24, 4);
+  const int p1 = e.add_buf(11, 11, 32);
   const int c2 = e.add_buf(9, 9, 48), p2 = e.add_buf(4, 4, 48), c3 = e.add_buf(3, 3, 64), d4 = e.add_buf(1, 1, 128);
-  const int c1 = front ? -1 : e.add_buf(22, 22, 32);
   const int hd = e.add_buf(1, 1, 8);   // the heads stay the LAST buffer (mtcnn.hip reads bufs.back())
   static thread_local std::vector<float> keep;
-  if (!front) {
-    TRY(mtcnn_conv(e, wm, "conv1", "prelu1", in, 3, 4, 28, 32, 3, c1));
-    add_pool_ceil(e, c1, p1, 3);
-  }
   if (!mid) {
     TRY(mtcnn_conv(e, wm, "conv2", "prelu2", p1, 28, 32, 48, 48, 3, c2));
     add_pool_ceil(e, c2, p2, 3);
@@ -1053,18 +1065,14 @@ int build_rnet(Encoder& e, WeightMap& wm, bool front, bool mid) {
   return VNF_OK;
 }
 
-int build_onet(Encoder& e, WeightMap& wm, bool front, bool mid) {
+int build_onet(Encoder& e, WeightMap& wm, bool mid) {
   e.in_size = 48;
-  const int in = e.add_buf(48, 48, 4), p1 = e.add_buf(23, 23, 32);
+  e.add_buf(48, 48, 4);
+  const int p1 = e.add_buf(23, 23, 32);
   const int c2 = e.add_buf(21, 21, 64), p2 = e.add_buf(10, 10, 64), c3 = e.add_buf(8, 8, 64), p3 = e.add_buf(4, 4, 64);
   const int c4 = e.add_buf(3, 3, 128), d5 = e.add_buf(1, 1, 256);
-  const int c1 = front ? -1 : e.add_buf(46, 46, 32);
   const int hd = e.add_buf(1, 1, 16);
   static thread_local std::vector<float> keep;
-  if (!front) {
-    TRY(mtcnn_conv(e, wm, "conv1", "prelu1", in, 3, 4, 32, 32, 3, c1));
-    add_pool_ceil(e, c1, p1, 3);
-  }
   if (!mid) {
     TRY(mtcnn_conv(e, wm, "conv2", "prelu2", p1, 32, 32, 64, 64, 3, c2));
     add_pool_ceil(e, c2, p2, 3);
@@ -1091,7 +1099,7 @@ int build_retina_mnet(Encoder& e, WeightMap& wm, int H, int W, int head_bufs[3])
   // VNF_RETINA_FUSE=0: the early layers as plan convolutions on an NHWC4 fp32 copy of the frames (buffer 0, written by
   // the caller); default: conv0 straight from the u8 frames (Op::RSTEM) and dw+pw blocks in one kernel (Op::DWPW)
   // (bit 0: stem, bit 1: dw+pw blocks)
-  static const int fuse_env = getenv("VNF_RETINA_FUSE") ? atoi(getenv("VNF_RETINA_FUSE")) : 3;
+  const int fuse_env = getenv("VNF_RETINA_FUSE") ? atoi(getenv("VNF_RETINA_FUSE")) : 3;
   const bool fused = fuse_env & 1, fused_dw = fuse_env & 2;
   int cur = e.add_buf(fused ? 1 : H, fused ? 1 : W, 4);   // input: NHWC4 (R-104, G-117, B-123, 0); a stub when fused
   int h = H, w = W;
@@ -1338,9 +1346,7 @@ int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, s
     VNF_HIP(hipEventRecord(ctx_ev[c], s));
     return VNF_OK;
   }
-  static const int env_streams = getenv("VNF_STREAMS") ? atoi(getenv("VNF_STREAMS")) : 2;
-  int ns = env_streams < 1 ? 1 : (env_streams > 4 ? 4 : env_streams);
-  if (ns > max_streams) ns = max_streams;
+  int ns = max_streams < 2 ? max_streams : 2;
   while (ns > 1 && n / ns < 96) --ns;  // below ~100 images a part no longer fills the chip: fixed per-launch latency dominates
   if (ns == 1 || report) return run_range(x, 0, n, x_dtype, out, s, report);
   if (!side[0]) {

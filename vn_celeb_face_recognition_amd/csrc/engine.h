@@ -148,18 +148,23 @@ struct Encoder : HandleBase {
   bool tune_dirty = true;  // tiles are (re)picked lazily at the next run(): create, set_streams and set_contexts only mark
   int tune_lanes = 1;   // concurrent copies the autotuner times each candidate as (set with the context count)
   int tune_batch = 0;   // batch size the autotuner times at (0: the part size run() uses at max_batch)
+  // the autotuner's switches, read from the environment by finalize() (at create time): VNF_AUTOTUNE, VNF_FORCE_CFG,
+  // VNF_TUNE_LANES, VNF_AUTOTUNE_LOG, VNF_TUNE_FINAL (0: no finalists pass), VNF_TUNE_CACHE (file; empty: none)
+  struct TuneEnv { int enabled = 1, force = -2, lanes = 0, log = 0; bool finals = true; std::string cache; } tune_env;
   hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr}, fork_ev = nullptr;
 };
 
 int build_irv1(Encoder& e, WeightMap& wm);
 int build_ir100(Encoder& e, WeightMap& wm);
-// MTCNN R-Net / O-Net as exact-f32 MFMA plans over NHWC4 candidate crops (input buffer 0 is written by the
-// crop kernel; the last buffer holds the head outputs: 8 floats [a0,a1,reg0..3,-,-] / 16 floats [a0,a1,reg0..3,lm0..9])
 // RetinaFace (mobilenet0.25) on the exact-f32 core for an H x W input: buffer 0 = NHWC4 mean-subtracted input (written by
 // the caller), head_bufs[l] = (Hl, Wl, 32) fp32 [cls 4 | bbox 8 | landmark 20] of pyramid level l
 int build_retina_mnet(Encoder& e, WeightMap& wm, int H, int W, int head_bufs[3]);
-int build_rnet(Encoder& e, WeightMap& wm, bool front = false, bool mid = false);
-int build_onet(Encoder& e, WeightMap& wm, bool front = false, bool mid = false);
+// MTCNN R-Net / O-Net as MFMA plans (exact-f32 or split-f16) over NHWC4 candidate crops (input buffer 0 is written by
+// the crop kernel, conv1 + pool1 by the detector's net_front_kernel into buffer 1, with mid conv2 + pool2 by its
+// net_mid_kernel into buffer 3; the last buffer holds the head outputs: 8 floats [a0,a1,reg0..3,-,-] / 16 floats
+// [a0,a1,reg0..3,lm0..9])
+int build_rnet(Encoder& e, WeightMap& wm, bool mid);
+int build_onet(Encoder& e, WeightMap& wm, bool mid);
 
 }  // namespace vnf

@@ -11,13 +11,14 @@
 //
 // Kernel map:
 //   K1 pyramid_kernel        u8 frame -> all pyramid levels (adaptive-average bins, normalised)
-//   K2 pnet_conv1_pool / pnet_conv2 / pnet_conv3_heads   (all levels and frames per launch)
+//   K2 pnet_conv1_pool_direct / pnet_conv2 / pnet_conv3_heads   (all levels and frames per launch)
 //   K3 threshold + compaction fused into pnet_conv3_heads (wave-aggregated atomic slots;
 //      order restored by the sort keys, which carry the cell index)
 //   K4 nms_scale_kernel (per level x frame, IoU 0.5), nms_image_kernel (per frame, IoU 0.7,
 //      + regress, rerec, pad), stage2_post_kernel (IoU 0.7 + bbreg + rerec + pad)
 //   K5 crop_resize_kernel    box table -> N x 3 x {24,48}^2 (area bins, also up-sampling)
-//   K6 rnet_kernel / onet_kernel   one workgroup per candidate, activations resident in LDS
+//   K6 net_front_kernel (conv1 + pool1), net_mid_kernel (conv2 + pool2), then the rest of R-Net / O-Net as MFMA plans
+//      of the conv core (engine.cpp build_rnet / build_onet) over the dense batch of all frames' candidates
 //   K7 stage3_post_kernel    landmarks, bbreg, "Min" NMS, area-descending order
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -197,92 +198,14 @@ __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __rest
 }
 
 // --------------------------------------------------------------------------------------------- K2
-// mtcnn.py:39-41: conv1 3->10 (3x3) + PReLU, then MaxPool2d(2,2,ceil_mode=True); one thread per
-// pooled pixel, all 10 channels in registers.
-__global__ void pnet_conv1_pool_kernel(const float* __restrict__ lvl, LevelTable t, PNetW w, float* __restrict__ p1) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= t.tot_p1) return;
-  const int img = blockIdx.y;
-  const int li = find_level(t, idx, 1);
-  const LevelDesc L = t.l[li];
-  const int p = idx - L.off_p1, py = p / L.Wp, px = p - py * L.Wp;
-  const int Hc = L.Hs - 2, Wc = L.Ws - 2;
-  float in[3][4][4];
-  const float* src = lvl + ((size_t)img * 3) * t.tot_px + L.off_px;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        // clamped address, no predicate: the 48 loads issue back to back instead of one exec-masked round
-        // trip each.  A clamped (out-of-level) value only reaches conv outputs beyond (Hc, Wc), which the
-        // window test below skips, so it never contributes.
-        const int yy = min(2 * py + dy, L.Hs - 1), xx = min(2 * px + dx, L.Ws - 1);
-        in[c][dy][dx] = src[(size_t)c * t.tot_px + yy * L.Ws + xx];
-      }
-  // the four conv positions of the pooling window advance together, tap by tap: every weight is fetched once per
-  // thread (they are wave-uniform scalar loads whose latency the FMAs of the previous tap cover), not once per position.
-  // Positions outside (Hc, Wc) are computed on clamped inputs and discarded below.
-  float2_t acc2[4][5];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) acc2[q][j] = float2_t{w.b1[2 * j], w.b1[2 * j + 1]};
-  // software-pipelined by hand: tap i+1's ten weights are requested before tap i's 20 packed FMAs; the per-tap
-  // barriers keep the compiler from hoisting all 270 scalar loads to the top (they do not fit the SGPR file: it
-  // spilled them to VGPR lanes and paid 3 780 v_readlane for 540 FMAs)
-  float2_t wv[2][5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) wv[0][j] = float2_t{w.w1[2 * j], w.w1[2 * j + 1]};
-#pragma unroll
-  for (int tap = 0; tap < 27; ++tap) {
-    const int c = tap / 9, kh = (tap % 9) / 3, kw = tap % 3;
-    if (tap + 1 < 27) {
-      const float* ww = w.w1 + (tap + 1) * 10;
-#pragma unroll
-      for (int j = 0; j < 5; ++j) wv[(tap + 1) & 1][j] = float2_t{ww[2 * j], ww[2 * j + 1]};
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float v = in[c][(q >> 1) + kh][(q & 1) + kw];
-      const float2_t v2 = {v, v};
-#pragma unroll
-      for (int j = 0; j < 5; ++j) acc2[q][j] = __builtin_elementwise_fma(v2, wv[tap & 1][j], acc2[q][j]);
-    }
-    // every accumulator is made opaque here, so the tap's 20 FMAs cannot be sunk into per-output chains
-    // (LLVM otherwise finishes one accumulator over all 27 taps before starting the next, re-reading every weight)
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int j = 0; j < 5; ++j) asm volatile("" : "+v"(acc2[q][j]));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  float best[10];
-#pragma unroll
-  for (int co = 0; co < 10; ++co) best[co] = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bool ok = 2 * py + (q >> 1) < Hc && 2 * px + (q & 1) < Wc;
-#pragma unroll
-    for (int co = 0; co < 10; ++co) {
-      const float av = acc2[q][co >> 1][co & 1];
-      const float a = av > 0.f ? av : av * w.a1[co];
-      best[co] = ok ? fmaxf(best[co], a) : best[co];
-    }
-  }
-  float* o = p1 + ((size_t)img * 10) * t.tot_p1 + L.off_p1 + p;
-#pragma unroll
-  for (int co = 0; co < 10; ++co) o[(size_t)co * t.tot_p1] = best[co];
-}
-
-// K2 on the matrix pipe.  The per-pixel kernel above needs its 270 weights as wave-uniform scalars at every tap; they
-// do not fit the SGPR file, so each wave fetches them again and again and waits on that (measured: 134 us per 16
-// frames, 30 us with the weights held fixed).  Here the weights are an MFMA operand: 9 VGPRs per lane, loaded once.
-// One workgroup per (pooled row of any level, frame): the four input rows go to LDS, a wave takes tiles of
-// 2 conv rows x 8 conv columns = 16 pixels, one v_mfma_f32_16x16x4_f32 per tap (A = weights [16 ch pad][4 ch pad],
-// B = pixels, accumulator preset with the bias), PReLU, the 2x2 max over the lane quartet {l, l^1, l^8, l^9} by DPP,
-// pooled values staged in LDS and written as whole rows per channel.
+// mtcnn.py:39-41: conv1 3->10 (3x3) + PReLU, then MaxPool2d(2,2,ceil_mode=True), on the matrix pipe: the 270 weights
+// are an MFMA operand (9 VGPRs per lane, loaded once), not wave-uniform scalars (those do not fit the SGPR file, and a
+// per-pixel VALU kernel waits on fetching them again and again).  One workgroup per (pooled row of any level, frame); a
+// wave takes tiles of 2 conv rows x 8 conv columns = 16 pixels, one v_mfma_f32_16x16x4_f32 per tap (A = weights [16 ch
+// pad][4 ch pad], B = pixels, accumulator preset with the bias), PReLU, the 2x2 max over the lane quartet {l, l^1, l^8,
+// l^9} by DPP.  Every lane fetches its nine B values straight from the level (the 9-fold reuse between taps and the
+// 2-column overlap of neighbouring tiles are L1 hits), two tiles in flight per wave so the two accumulator chains
+// interleave, the next pair's loads issued before the current pair's MFMAs.  No barrier at all.
 typedef float f32x4p_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float dpp_xor1(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
@@ -290,84 +213,6 @@ __device__ __forceinline__ float dpp_xor1(float v) {
 __device__ __forceinline__ float dpp_xor8(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));  // row_ror:8
 }
-__device__ __forceinline__ int pnet_row_stride(int Ws) { return ((Ws + 2 + 13) & ~31) + 18 >= Ws + 2 ? ((Ws + 2 + 13) & ~31) + 18 : ((Ws + 2 + 13) & ~31) + 50; }
-
-__global__ void __launch_bounds__(256) pnet_conv1_pool_mfma_kernel(const float* __restrict__ lvl, LevelTable t, PNetW w,
-                                                                    float* __restrict__ p1) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int li = 0, py = blockIdx.x;
-  while (li + 1 < t.n && py >= t.l[li].Hp) { py -= t.l[li].Hp; ++li; }
-  const LevelDesc L = t.l[li];
-  const int img = blockIdx.y, tid = threadIdx.x;
-  const int Hc = L.Hs - 2, Wc = L.Ws - 2;
-  const int Wsp = pnet_row_stride(L.Ws);            // LDS row stride: = 18 mod 32 floats, so the (row, channel) lane groups
-  float* s_in = reinterpret_cast<float*>(smem);     // [3 ch][4 rows][Wsp]            spread over the banks
-  float* s_out = s_in + 12 * Wsp;                   // [10][Wp]
-  const float* src = lvl + ((size_t)img * 3) * t.tot_px + L.off_px;
-  for (int i = tid; i < 12 * L.Ws; i += 256) {
-    const int rr = i / L.Ws, x = i - rr * L.Ws, c = rr >> 2, dy = rr & 3;
-    const int yy = min(2 * py + dy, L.Hs - 1);       // a clamped row only feeds conv rows >= Hc, which are masked
-    s_in[rr * Wsp + x] = src[(size_t)c * t.tot_px + yy * L.Ws + x];
-  }
-  const int wave = tid >> 6, lane = tid & 63, lg = lane >> 4, lm = lane & 15, dy = lm >> 3, dx = lm & 7;
-  float wa[9];
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) wa[tap] = (lm < 10 && lg < 3) ? w.w1[(lg * 9 + tap) * 10 + lm] : 0.f;
-  float bias[4], slope[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int ch = lg * 4 + e;
-    bias[e] = ch < 10 ? w.b1[ch] : 0.f;
-    slope[e] = ch < 10 ? w.a1[ch] : 0.f;
-  }
-  __syncthreads();
-  const int cg = min(lg, 2);                          // channel 3 is the zero pad of the k dimension (its weights are 0)
-  const bool row_ok = 2 * py + dy < Hc;
-  const int ntile = (L.Wp + 3) >> 2;
-  for (int tx = wave; tx < ntile; tx += 8) {          // tiles tx and tx + 4 together: two accumulator chains interleave
-    f32x4p_t acc[2];
-    float xb[2][9];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int x0 = min(8 * (tx + 4 * u) + dx, L.Ws - 3);   // clamped columns only feed conv columns >= Wc (masked)
-      const float* b0 = s_in + (cg * 4 + dy) * Wsp + x0;
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) xb[u][kh * 3 + kw] = b0[kh * Wsp + kw];
-      acc[u] = f32x4p_t{bias[0], bias[1], bias[2], bias[3]};
-    }
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[tap], xb[0][tap], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[tap], xb[1][tap], acc[1], 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int txu = tx + 4 * u;
-      const bool ok = row_ok && 8 * txu + dx < Wc;
-      const int pxx = 4 * txu + (dx >> 1);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = acc[u][e] > 0.f ? acc[u][e] : acc[u][e] * slope[e];
-        v = ok ? v : -INFINITY;
-        v = fmaxf(v, dpp_xor1(v));
-        v = fmaxf(v, dpp_xor8(v));
-        if ((lm & 9) == 0 && pxx < L.Wp && lg * 4 + e < 10) s_out[(lg * 4 + e) * L.Wp + pxx] = v;
-      }
-    }
-  }
-  __syncthreads();
-  float* o = p1 + ((size_t)img * 10) * t.tot_p1 + L.off_p1 + (size_t)py * L.Wp;
-  for (int i = tid; i < 10 * L.Wp; i += 256) {
-    const int ch = i / L.Wp, x = i - ch * L.Wp;
-    o[(size_t)ch * t.tot_p1 + x] = s_out[i];
-  }
-}
-
-// Same arithmetic without the LDS stage: every lane fetches its nine B values straight from the level (the 9-fold
-// reuse between taps and the 2-column overlap of neighbouring tiles are L1 hits), two tiles in flight per wave so the
-// two accumulator chains interleave, the next pair's loads issued before the current pair's MFMAs.  No barrier at all.
 __global__ void __launch_bounds__(256) pnet_conv1_pool_direct_kernel(const float* __restrict__ lvl, LevelTable t, PNetW w,
                                                                       float* __restrict__ p1) {
   int li = 0, py = blockIdx.y;   // frame on x: one XCD (and its L2) per frame, see pyramid_rows_kernel
@@ -700,11 +545,11 @@ __global__ void __launch_bounds__(256) nms_image_kernel(const Cand* __restrict__
 
 // --------------------------------------------------------------------------------------------- K5
 // detect_face.py:109-114 / 138-143: imgs[i, :, y-1:ey, x-1:ex] -> imresample(S,S) -> normalise.
-// One workgroup per candidate; output NCHW fp32 (3,S,S).  Degenerate rectangles (the reference
-// silently drops them from im_data, which would desynchronise its tables) are flagged and zeroed.
-// Output addressing of the crop kernels.  Planar: (3,S,S) per candidate at [img][KEEP] (the LDS-resident
-// nets).  Compact NHWC4: candidate offs[img]+k-c0 of a dense batch, 4 floats per pixel (RGB + 0), the
-// input layout of the MFMA R/O-Net plans; candidates outside [c0, c0+cap) are skipped.
+// One workgroup per candidate.  Degenerate rectangles (the reference silently drops them from im_data,
+// which would desynchronise its tables) are flagged and zeroed.
+// Output addressing of the crop kernels.  Compact NHWC4: candidate offs[img]+k-c0 of a dense batch, 4 floats
+// per pixel (RGB + 0), the input layout of the MFMA R/O-Net plans; candidates outside [c0, c0+cap) are skipped.
+// (offs == nullptr selects a planar (3,S,S) table at [img][KR]; the host no longer asks for it.)
 struct CropDst {
   float* base;      // nullptr: candidate not in this chunk
   int cs, ps;       // channel stride, pixel stride (floats)
@@ -909,23 +754,23 @@ __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __
 // R-Net / O-Net front: conv1 (3 -> 28 / 32, 3x3) + PReLU + MaxPool(3, 2, ceil_mode) in one kernel (mtcnn.py:84-87 /
 // 138-141).  The conv1 map is the largest tensor of the cascade (46x46x32 floats per O-Net candidate, 208 MB for 767
 // candidates); here it only ever exists in LDS.  One workgroup per (band of BANDP pooled rows, candidate): the crop
-// rows the band needs go to LDS, every wave computes all 32 output channels of 16 conv pixels per round on the exact-fp32 MFMA (weights stay
-// in 18 registers per lane), the PReLU outputs are parked in LDS as
-// [pixel][32] with the 16-byte chunk index XOR-swizzled by the pixel, and the pooled rows are reduced from there and
-// written as whole NHWC rows.
+// rows the band needs go to LDS, every wave computes all 32 output channels of 16 conv pixels per round on the MFMA
+// (weights stay in registers), the PReLU outputs are parked in LDS as [pixel][32] with the 16-byte chunk index
+// XOR-swizzled by the pixel, and the pooled rows are reduced from there and written as whole NHWC rows.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 struct FrontW { const float* w; const float* b; const float* a; };   // [32][9 taps][4 channels (3 + zero)], [32], [32]
 
-// SPLIT: the pooled map is written as split-f16 (hi, lo) pairs, the storage of the F16X2 plans (split_f16.h).
 __device__ __forceinline__ float split_pack(float v) {
   const sf16 h(v);
   return __builtin_bit_cast(float, h);
 }
-// MM16 (with SPLIT): conv1 itself on the 16-bit MFMA with split-f16 operands -- the crop pixels are split once when
+// SPLIT (the split-f16 plans): the pooled map is written as split-f16 (hi, lo) pairs, the storage of the F16X2 plans
+// (split_f16.h), and conv1 itself runs on the 16-bit MFMA with split-f16 operands -- the crop pixels are split once when
 // they are copied to LDS (a pixel's 3 + 1 channels as four (hi, lo) pairs are the same 16 bytes as its four floats), a
 // k block is four taps x four channels, so the 9 taps are three MFMA pairs per 16-channel tile (96 cycles) instead of
-// nine f32 MFMAs (288); ~22 significant bits per operand like every later layer of the split plans.
-template <int S, int BANDP, int NT, bool SPLIT, bool MM16 = false>
+// nine f32 MFMAs (288); ~22 significant bits per operand like every later layer of the split plans.  Without SPLIT (the
+// exact-f32 plans) conv1 is nine exact-fp32 MFMAs per tile and the pooled map stays fp32.
+template <int S, int BANDP, int NT, bool SPLIT>
 __global__ void __launch_bounds__(NT) net_front_kernel(const float* __restrict__ crops, FrontW fw, float* __restrict__ p1) {
   constexpr int C = S - 2;                 // conv1 rows / cols
   constexpr int P = (C - 3 + 1) / 2 + 1;   // ceil((C - 3) / 2) + 1
@@ -940,7 +785,7 @@ __global__ void __launch_bounds__(NT) net_front_kernel(const float* __restrict__
   const float4* src = reinterpret_cast<const float4*>(crops) + ((size_t)cand * S + cr0) * S;
   for (int i = t; i < nir * S; i += NT) {
     float4 v = src[i];
-    if constexpr (MM16) v = float4{split_pack(v.x), split_pack(v.y), split_pack(v.z), split_pack(v.w)};
+    if constexpr (SPLIT) v = float4{split_pack(v.x), split_pack(v.y), split_pack(v.z), split_pack(v.w)};
     s_in[i] = v;
   }
   __syncthreads();
@@ -948,9 +793,9 @@ __global__ void __launch_bounds__(NT) net_front_kernel(const float* __restrict__
   // B = crop pixels (lane: pixel l&15, input channel l>>4; channel 3 is the zero pad), D = 4 consecutive output
   // channels of one pixel per lane.  Same k order as the plan's implicit-GEMM conv (tap-major), bias after the sum.
   const int wave = t >> 6, lane = t & 63, lg = lane >> 4, lm = lane & 15;
-  float wa[2][MM16 ? 1 : 9];
-  uint4 ws[2][MM16 ? 3 : 1];   // MM16: A fragments, lane (channel lm, group lg) = tap 4 blk + lg, input channels 0..3 as (hi, lo) pairs
-  if constexpr (MM16) {
+  float wa[2][SPLIT ? 1 : 9];
+  uint4 ws[2][SPLIT ? 3 : 1];   // SPLIT: A fragments, lane (channel lm, group lg) = tap 4 blk + lg, input channels 0..3 as (hi, lo) pairs
+  if constexpr (SPLIT) {
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -978,7 +823,7 @@ __global__ void __launch_bounds__(NT) net_front_kernel(const float* __restrict__
     const int px = tile * 16 + lm, pxc = min(px, npx - 1);
     const int r = pxc / C, x = pxc - r * C;
     f32x4_t acc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
-    if constexpr (MM16) {
+    if constexpr (SPLIT) {
       typedef _Float16 f16x8f_t __attribute__((ext_vector_type(8)));
       const uint4* s_inu = reinterpret_cast<const uint4*>(s_in);
 #pragma unroll
@@ -1139,221 +984,6 @@ __global__ void __launch_bounds__(NWAVE * 64) net_mid_kernel(const float* __rest
   }
 }
 
-// --------------------------------------------------------------------------------------------- K6 building blocks
-// Direct convolution / pooling / dense layers over activations resident in LDS (CHW fp32),
-// weights in their PyTorch layout read through L1/L2 (shared by every workgroup).
-__device__ __forceinline__ float prelu(float v, float a) { return v > 0.f ? v : v * a; }
-
-// Register-tiled direct convolution: a thread computes COB output channels x PXB consecutive pixels,
-// so each LDS input value feeds COB*KS FMAs and each weight PXB FMAs.  wt is the layer's weight
-// transposed to [CIN][KS][KS][ldw] (output channel fastest), so the COB weights of one tap are one
-// or two 16-byte loads, identical across the lanes that share a channel block (L1 broadcast).
-// Per output the FMA order is (c, kh, kw), as in the reference's direct statement of the conv.
-template <int CIN, int KS, int COB, int PXB>
-__device__ void lds_conv_prelu(const float* __restrict__ in, int Hi, int Wi, float* __restrict__ out, int cout,
-                               const float* __restrict__ wt, int ldw, const float* __restrict__ b,
-                               const float* __restrict__ a) {
-  const int Ho = Hi - KS + 1, Wo = Wi - KS + 1;
-  const int xg = (Wo + PXB - 1) / PXB, per_cb = Ho * xg, n = (cout / COB) * per_cb;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int cb = i / per_cb, p = i - cb * per_cb, y = p / xg, x0 = (p - y * xg) * PXB;
-    float acc[COB][PXB];
-#pragma unroll
-    for (int co = 0; co < COB; ++co)
-#pragma unroll
-      for (int px = 0; px < PXB; ++px) acc[co][px] = b[cb * COB + co];
-#pragma unroll 1
-    for (int c = 0; c < CIN; ++c) {
-#pragma unroll
-      for (int kh = 0; kh < KS; ++kh) {
-        const float* ir = in + c * Hi * Wi + (y + kh) * Wi + x0;
-        float v[PXB + KS - 1];
-#pragma unroll
-        for (int j = 0; j < PXB + KS - 1; ++j) v[j] = (x0 + j < Wi) ? ir[j] : 0.f;
-#pragma unroll
-        for (int kw = 0; kw < KS; ++kw) {
-          const float* ww = wt + (size_t)((c * KS + kh) * KS + kw) * ldw + cb * COB;
-#pragma unroll
-          for (int co = 0; co < COB; ++co)
-#pragma unroll
-            for (int px = 0; px < PXB; ++px) acc[co][px] = fmaf(v[px + kw], ww[co], acc[co][px]);
-        }
-      }
-    }
-#pragma unroll
-    for (int co = 0; co < COB; ++co)
-#pragma unroll
-      for (int px = 0; px < PXB; ++px)
-        if (x0 + px < Wo) out[(cb * COB + co) * Ho * Wo + y * Wo + x0 + px] = prelu(acc[co][px], a[cb * COB + co]);
-  }
-}
-
-// The same register-tiled convolution with the weights of ONE input channel at a time staged in
-// LDS (double-buffered, one barrier per input channel): the inner loop then touches no global
-// memory, which matters at one workgroup per CU where nothing else hides an L2 round trip.
-// Every thread owns NTILE output tiles for the whole channel loop.  wbuf: 2 * KS*KS * cout floats.
-template <int CIN, int KS, int COB, int PXB, int NTILE>
-__device__ void lds_conv_prelu_ws(const float* __restrict__ in, int Hi, int Wi, float* __restrict__ out, int cout,
-                                  const float* __restrict__ wt, int ldw, const float* __restrict__ b,
-                                  const float* __restrict__ a, float* __restrict__ wbuf) {
-  const int Ho = Hi - KS + 1, Wo = Wi - KS + 1;
-  const int xg = (Wo + PXB - 1) / PXB, per_cb = Ho * xg, n = (cout / COB) * per_cb;
-  const int wn = KS * KS * cout;  // floats of one input channel's weights
-  float acc[NTILE][COB][PXB];
-  int tcb[NTILE], ty[NTILE], tx[NTILE];
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t) {
-    const int i = threadIdx.x + t * blockDim.x;
-    const int ii = i < n ? i : 0;
-    tcb[t] = ii / per_cb;
-    const int p = ii - tcb[t] * per_cb;
-    ty[t] = p / xg;
-    tx[t] = (p - ty[t] * xg) * PXB;
-    if (i >= n) tcb[t] = -1;
-#pragma unroll
-    for (int co = 0; co < COB; ++co)
-#pragma unroll
-      for (int px = 0; px < PXB; ++px) acc[t][co][px] = tcb[t] >= 0 ? b[tcb[t] * COB + co] : 0.f;
-  }
-  // stage channel 0
-  for (int i = threadIdx.x; i < wn; i += blockDim.x) wbuf[i] = wt[(size_t)(i / cout) * ldw + (i % cout)];
-  __syncthreads();
-#pragma unroll 1
-  for (int c = 0; c < CIN; ++c) {
-    float* wcur = wbuf + (c & 1) * wn;
-    float* wnxt = wbuf + ((c + 1) & 1) * wn;
-    // prefetch the next channel's weights into registers (<= 3 per thread), park them after the math
-    float pre[3];
-    const bool more = c + 1 < CIN;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int i = threadIdx.x + u * blockDim.x;
-      pre[u] = (more && i < wn) ? wt[(size_t)((c + 1) * KS * KS + i / cout) * ldw + (i % cout)] : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t) {
-      if (tcb[t] >= 0) {
-#pragma unroll
-        for (int kh = 0; kh < KS; ++kh) {
-          const float* ir = in + c * Hi * Wi + (ty[t] + kh) * Wi + tx[t];
-          float v[PXB + KS - 1];
-#pragma unroll
-          for (int j = 0; j < PXB + KS - 1; ++j) v[j] = (tx[t] + j < Wi) ? ir[j] : 0.f;
-#pragma unroll
-          for (int kw = 0; kw < KS; ++kw) {
-            const float* ww = wcur + (kh * KS + kw) * cout + tcb[t] * COB;
-#pragma unroll
-            for (int co = 0; co < COB; ++co)
-#pragma unroll
-              for (int px = 0; px < PXB; ++px) acc[t][co][px] = fmaf(v[px + kw], ww[co], acc[t][co][px]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int i = threadIdx.x + u * blockDim.x;
-      if (more && i < wn) wnxt[i] = pre[u];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int t = 0; t < NTILE; ++t)
-    if (tcb[t] >= 0) {
-#pragma unroll
-      for (int co = 0; co < COB; ++co)
-#pragma unroll
-        for (int px = 0; px < PXB; ++px)
-          if (tx[t] + px < Wo)
-            out[(tcb[t] * COB + co) * Ho * Wo + ty[t] * Wo + tx[t] + px] = prelu(acc[t][co][px], a[tcb[t] * COB + co]);
-    }
-}
-
-// conv + PReLU + MaxPool(PK, 2, ceil_mode=True) fused (recomputes the conv under overlapping windows):
-// used where the un-pooled map would not fit LDS.
-template <int CIN, int KS, int PK>
-__device__ void lds_conv_prelu_pool(const float* __restrict__ in, int Hi, int Wi, float* __restrict__ out, int cout,
-                                    const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ a) {
-  const int Hc = Hi - KS + 1, Wc = Wi - KS + 1;
-  const int Hp = (Hc - PK + 1) / 2 + 1, Wp = (Wc - PK + 1) / 2 + 1;  // ceil((Hc-PK)/2)+1
-  const int n = cout * Hp * Wp;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int co = i / (Hp * Wp), p = i - co * (Hp * Wp), py = p / Wp, px = p - py * Wp;
-    const float* wc = w + (size_t)co * CIN * KS * KS;
-    float best = -INFINITY;
-    for (int oy = 0; oy < PK; ++oy)
-      for (int ox = 0; ox < PK; ++ox) {
-        const int y = 2 * py + oy, x = 2 * px + ox;
-        if (y < Hc && x < Wc) {
-          float acc = b[co];
-#pragma unroll 1
-          for (int c = 0; c < CIN; ++c) {
-            const float* ic = in + c * Hi * Wi + y * Wi + x;
-#pragma unroll
-            for (int kh = 0; kh < KS; ++kh)
-#pragma unroll
-              for (int kw = 0; kw < KS; ++kw) acc = fmaf(ic[kh * Wi + kw], wc[(c * KS + kh) * KS + kw], acc);
-          }
-          best = fmaxf(best, prelu(acc, a[co]));
-        }
-      }
-    out[i] = best;
-  }
-}
-
-template <int PK>
-__device__ void lds_maxpool_ceil(const float* __restrict__ in, int C, int Hi, int Wi, float* __restrict__ out) {
-  const int Hp = (Hi - PK + 1) / 2 + 1, Wp = (Wi - PK + 1) / 2 + 1;
-  for (int i = threadIdx.x; i < C * Hp * Wp; i += blockDim.x) {
-    const int c = i / (Hp * Wp), p = i - c * (Hp * Wp), py = p / Wp, px = p - py * Wp;
-    float best = -INFINITY;
-    for (int oy = 0; oy < PK; ++oy)
-      for (int ox = 0; ox < PK; ++ox) {
-        const int y = 2 * py + oy, x = 2 * px + ox;
-        if (y < Hi && x < Wi) best = fmaxf(best, in[c * Hi * Wi + y * Wi + x]);
-      }
-    out[i] = best;
-  }
-}
-
-// dense layer on x.permute(0,3,2,1) flattened (mtcnn.py:93-94,150-151): feature f = (w*H + h)*C + c.
-// `feat` receives the permuted input (nin floats, LDS); wt is the weight transposed to [nin][nout]
-// so consecutive threads read consecutive outputs (coalesced).  With more threads than outputs the
-// reduction is split over KSPLIT thread groups and combined through `part` (LDS, KSPLIT*nout floats).
-__device__ void lds_dense_permuted_prelu(const float* __restrict__ in, int C, int Hh, int Ww, float* __restrict__ feat,
-                                         float* __restrict__ part, float* __restrict__ out, int nout,
-                                         const float* __restrict__ wt, const float* __restrict__ b,
-                                         const float* __restrict__ a) {
-  const int nin = C * Hh * Ww;
-  for (int f = threadIdx.x; f < nin; f += blockDim.x) {
-    const int c = f % C, hw = f / C, h = hw % Hh, w_ = hw / Hh;
-    feat[f] = in[c * Hh * Ww + h * Ww + w_];
-  }
-  __syncthreads();
-  const int ksplit = blockDim.x / nout;  // >= 1 (nout <= blockDim)
-  const int o = threadIdx.x % nout, g = threadIdx.x / nout;
-  if (g < ksplit) {
-    const int f0 = (nin * g) / ksplit, f1 = (nin * (g + 1)) / ksplit;
-    float acc = 0.f;
-    for (int f = f0; f < f1; ++f) acc = fmaf(feat[f], wt[(size_t)f * nout + o], acc);
-    part[g * nout + o] = acc;
-  }
-  __syncthreads();
-  if (threadIdx.x < nout) {
-    float acc = b[threadIdx.x];
-    for (int g2 = 0; g2 < ksplit; ++g2) acc += part[g2 * nout + threadIdx.x];
-    out[threadIdx.x] = prelu(acc, a[threadIdx.x]);
-  }
-}
-
-struct RNetW {
-  const float *c1w, *c1b, *a1, *c2w, *c2b, *a2, *c3w, *c3b, *a3, *d4w, *d4b, *a4, *d51w, *d51b, *d52w, *d52b;
-};
-struct ONetW {
-  const float *c1w, *c1b, *a1, *c2w, *c2b, *a2, *c3w, *c3b, *a3, *c4w, *c4b, *a4, *d5w, *d5b, *a5, *d61w, *d61b, *d62w,
-      *d62b, *d63w, *d63b;
-};
-
 // exclusive prefix of the per-frame candidate counts: compact batch index of (img, k) = offs[img] + k
 __global__ void prefix_offsets_kernel(const int* __restrict__ cnt, int B, int* __restrict__ offs) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -1379,98 +1009,6 @@ __global__ void heads_scatter_kernel(const float* __restrict__ heads, int hw, co
   const float e0 = expf(a0 - m), e1 = expf(a1 - m);
   o[0] = e1 / (e0 + e1);
   for (int i = 1; i < nf; ++i) o[i] = val(1 + i);
-}
-
-// mtcnn.py:84-99.  out: [score, reg0..3] per candidate.
-__global__ void __launch_bounds__(256) rnet_kernel(const float* __restrict__ crops, const int* __restrict__ row_cnt,
-                                                    RNetW w, float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int k = blockIdx.x, img = blockIdx.y;
-  if (k >= row_cnt[img]) return;
-  float* A = reinterpret_cast<float*>(smem);            // 28*22*22 = 13552 floats
-  float* Bf = A + 13552;                                // 28*11*11 = 3388 floats (>= 3*24*24 = 1728)
-  float* Wb = Bf + 3388;                                // 2 * 9 * 48 = 864 floats: staged weights
-  const float* src = crops + ((size_t)img * KEEP + k) * 3 * 24 * 24;
-  for (int i = threadIdx.x; i < 1728; i += blockDim.x) Bf[i] = src[i];
-  __syncthreads();
-  lds_conv_prelu_ws<3, 3, 4, 4, 4>(Bf, 24, 24, A, 28, w.c1w, 28, w.c1b, w.a1, Wb);   // 28 x 22 x 22
-  __syncthreads();
-  lds_maxpool_ceil<3>(A, 28, 22, 22, Bf);                                            // 28 x 11 x 11
-  __syncthreads();
-  lds_conv_prelu_ws<28, 3, 4, 3, 2>(Bf, 11, 11, A, 48, w.c2w, 48, w.c2b, w.a2, Wb);  // 48 x 9 x 9
-  __syncthreads();
-  lds_maxpool_ceil<3>(A, 48, 9, 9, Bf);                                              // 48 x 4 x 4
-  __syncthreads();
-  lds_conv_prelu_ws<48, 2, 4, 1, 1>(Bf, 4, 4, A, 64, w.c3w, 64, w.c3b, w.a3, Wb);    // 64 x 3 x 3
-  __syncthreads();
-  lds_dense_permuted_prelu(A, 64, 3, 3, A + 1024, A + 2048, Bf, 128, w.d4w, w.d4b, w.a4);
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int o = threadIdx.x;
-    const float* wr = o < 2 ? w.d51w + o * 128 : w.d52w + (o - 2) * 128;
-    float acc = o < 2 ? w.d51b[o] : w.d52b[o - 2];
-    for (int f = 0; f < 128; ++f) acc = fmaf(Bf[f], wr[f], acc);
-    A[o] = acc;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float m = fmaxf(A[0], A[1]);
-    const float e0 = expf(A[0] - m), e1 = expf(A[1] - m);
-    float* o = out + ((size_t)img * KEEP + k) * 5;
-    o[0] = e1 / (e0 + e1);
-    o[1] = A[2]; o[2] = A[3]; o[3] = A[4]; o[4] = A[5];
-  }
-}
-
-// mtcnn.py:138-157.  out: [score, reg0..3, lm0..9] per candidate.
-__global__ void __launch_bounds__(512) onet_kernel(const float* __restrict__ crops, const int* __restrict__ row_cnt,
-                                                    ONetW w, float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int k = blockIdx.x, img = blockIdx.y;
-  if (k >= row_cnt[img]) return;
-  float* X = reinterpret_cast<float*>(smem);   // 32*23*23 = 16928 floats
-  float* Wk = X + 16928;                       // 14112 floats: conv1 round (4*46*46 = 8464) / conv2 half (32*21*21)
-  float* Q = Wk + 14112;                       // 6912 floats: input (3*48*48), later the 64x10x10 pooled map
-  float* Wb = Q + 6912;                        // 2 * 9 * 64 = 1152 floats: staged weights
-  const float* src = crops + ((size_t)img * KEEP + k) * 3 * 48 * 48;
-  for (int i = threadIdx.x; i < 6912; i += blockDim.x) Q[i] = src[i];
-  __syncthreads();
-  for (int rd = 0; rd < 8; ++rd) {  // conv1 3->32 in rounds of 4 channels: the full 32x46x46 map would not fit LDS
-    lds_conv_prelu_ws<3, 3, 4, 4, 2>(Q, 48, 48, Wk, 4, w.c1w + rd * 4, 32, w.c1b + rd * 4, w.a1 + rd * 4, Wb);
-    __syncthreads();
-    lds_maxpool_ceil<3>(Wk, 4, 46, 46, X + rd * 4 * 529);                 // -> 32 x 23 x 23
-    __syncthreads();
-  }
-  for (int half = 0; half < 2; ++half) {  // conv2 32->64 in two 32-channel halves
-    lds_conv_prelu_ws<32, 3, 8, 4, 1>(X, 23, 23, Wk, 32, w.c2w + half * 32, 64, w.c2b + half * 32, w.a2 + half * 32, Wb);
-    __syncthreads();
-    lds_maxpool_ceil<3>(Wk, 32, 21, 21, Q + half * 32 * 100);             // -> 64 x 10 x 10
-    __syncthreads();
-  }
-  lds_conv_prelu_ws<64, 3, 4, 2, 1>(Q, 10, 10, Wk, 64, w.c3w, 64, w.c3b, w.a3, Wb);    // 64 x 8 x 8
-  __syncthreads();
-  lds_maxpool_ceil<2>(Wk, 64, 8, 8, X);                                   // 64 x 4 x 4
-  __syncthreads();
-  lds_conv_prelu_ws<64, 2, 4, 1, 1>(X, 4, 4, Wk, 128, w.c4w, 128, w.c4b, w.a4, Wb);    // 128 x 3 x 3
-  __syncthreads();
-  float* Y = Wk;
-  lds_dense_permuted_prelu(Wk, 128, 3, 3, Q, Q + 1152, X, 256, w.d5w, w.d5b, w.a5);
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    const int o = threadIdx.x;
-    const float* wr = o < 2 ? w.d61w + o * 256 : o < 6 ? w.d62w + (o - 2) * 256 : w.d63w + (o - 6) * 256;
-    float acc = o < 2 ? w.d61b[o] : o < 6 ? w.d62b[o - 2] : w.d63b[o - 6];
-    for (int f = 0; f < 256; ++f) acc = fmaf(X[f], wr[f], acc);
-    Y[o] = acc;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float m = fmaxf(Y[0], Y[1]);
-    const float e0 = expf(Y[0] - m), e1 = expf(Y[1] - m);
-    float* o = out + ((size_t)img * KEEP + k) * 15;
-    o[0] = e1 / (e0 + e1);
-    for (int i = 0; i < 14; ++i) o[1 + i] = Y[2 + i];
-  }
 }
 
 // --------------------------------------------------------------------------------------------- stage-2 post
@@ -1626,10 +1164,15 @@ __global__ void __launch_bounds__(256) stage3_post_kernel(const Row* __restrict_
 // =============================================================================================
 // host side
 constexpr int FIN_FAST = 32;  // faces per frame covered by the one-copy read-back (VNF_FIN_FAST lowers it: test hook)
+// dynamic LDS (bytes) of the launches that take some: the NMS kernels of stage 1, the post kernels of stages 2 / 3, the
+// fronts ((crop rows of a band * S + conv rows of a band * C * 8) float4) and the mids (input map + conv map)
+constexpr int LDS_NMS = CAP_LDS_KEYS * 8 + KEEP * 20 + 256 * 20, LDS_POST = KEEP * 44 + 256 * 20;
+constexpr int LDS_RFRONT = (25 * 24 + 22 * 22 * 8) * 16, LDS_OFRONT = (11 * 48 + 9 * 46 * 8) * 16;
+constexpr int LDS_RMID = 11 * 11 * 128 + 9 * 9 * 12 * 16, LDS_OMID = 23 * 23 * 128 + 21 * 21 * 8 * 16;
 
 struct Mtcnn : HandleBase {
   vnf_mtcnn_cfg cfg;
-  PNetW pw; RNetW rw; ONetW ow;
+  PNetW pw;
   LevelTable cap_table;  // geometry at (max_height, max_width): sizes the buffers
   float *lvl = nullptr, *p1 = nullptr, *c2 = nullptr;
   Cand* cand = nullptr;                       // stage-1 records, dense by cell: [frame][cap_out]
@@ -1638,14 +1181,12 @@ struct Mtcnn : HandleBase {
   NmsScratch scratch{};                       // global-memory fallback of the NMS kernels
   int *cand_cnt = nullptr, *keep1_cnt = nullptr, *row_cnt = nullptr, *row3_cnt = nullptr, *fin_cnt = nullptr, *status = nullptr;
   Row *rows = nullptr, *rows3 = nullptr;
-  float *crops = nullptr, *rout = nullptr, *oout = nullptr, *fin = nullptr;
+  float *rout = nullptr, *oout = nullptr, *fin = nullptr;
   float *prob_dbg = nullptr, *reg_dbg = nullptr;
-  Encoder *renc = nullptr, *oenc = nullptr;  // R-Net / O-Net plans on the exact-f32 MFMA core (candidates = batch)
+  Encoder *renc = nullptr, *oenc = nullptr;  // R-Net / O-Net plans on the MFMA core (candidates = batch)
   int* row_order = nullptr;                   // pyramid dispatch order (device), rebuilt when the frame size changes
   int row_order_h = 0, row_order_w = 0, row_order_cap = 0;
-  int pnet1_lds = 0;                          // dynamic LDS granted to pnet_conv1_pool_mfma_kernel
-  bool front = false;                         // conv1 + PReLU + pool1 of both nets by net_front_kernel (plans start at conv2)
-  FrontW rfw{}, ofw{};
+  FrontW rfw{}, ofw{};                        // conv1 + PReLU + pool1 of both nets by net_front_kernel (plans start at conv2)
   bool mid = false;                           // conv2 + PReLU + pool2 by net_mid_kernel (split-f16 plans start at conv3)
   MidW rmw{}, omw{};
   int r_cap = 0, o_cap = 0;
@@ -1654,7 +1195,10 @@ struct Mtcnn : HandleBase {
   // one D2H copy into pinned memory, one host synchronisation (a frame with more faces takes the 2-D copy)
   float* stage = nullptr;
   int* h_pin = nullptr;
-  int fin_fast = FIN_FAST;
+  // switches of the environment, read once at create time so that every handle keeps the ones it was made with
+  int fin_fast = FIN_FAST;                    // VNF_FIN_FAST
+  bool spec_on = true;                        // VNF_MTCNN_SPEC: size stages 2 / 3 from the previous call's counts
+  bool layers = false;                        // VNF_MTCNN_LAYERS (diagnostic): per-layer table of the plans on stderr
   int last_b = 0;  // frames of the last vnf_mtcnn_detect (vnf_mtcnn_results_device)
   struct Spec { bool valid = false; int b = 0, H = 0, W = 0, max2 = 0, total2 = 0, max3 = 0, total3 = 0; } spec;   // launch sizes of stages 2 / 3 from the previous call
   long long spec_misses = 0;
@@ -1767,108 +1311,78 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
       m->pw.w41 = up_transposed(*m, c41, 2, 32, 1); m->pw.b41 = UP(b41, 2);
       m->pw.w42 = up_transposed(*m, c42, 4, 32, 1); m->pw.b42 = UP(b42, 4);
     }
+    // switches of the environment: read here, once per handle
+    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    // VNF_MTCNN_DTYPE=f32 keeps the R/O-Net plans (and conv1 in net_front_kernel) on the exact-f32 MFMA; the default is
+    // split-f16 (two 16-bit MFMAs per product, ~22 significant bits) for every layer of both nets
+    const bool plans_f32 = getenv("VNF_MTCNN_DTYPE") && !strcmp(getenv("VNF_MTCNN_DTYPE"), "f32");
+    const bool mid_env = env_int("VNF_MTCNN_MID", 1) != 0;
+    m->spec_on = env_int("VNF_MTCNN_SPEC", 1) != 0;
+    m->layers = getenv("VNF_MTCNN_LAYERS") != nullptr;
+    m->fin_fast = std::max(0, std::min(FIN_FAST, env_int("VNF_FIN_FAST", FIN_FAST)));
     {
-      GETW(c1, wr, "conv1.weight", 756) GETW(b1, wr, "conv1.bias", 28) GETW(a1, wr, "prelu1.weight", 28)
-      GETW(c2, wr, "conv2.weight", 12096) GETW(b2, wr, "conv2.bias", 48) GETW(a2, wr, "prelu2.weight", 48)
-      GETW(c3, wr, "conv3.weight", 12288) GETW(b3, wr, "conv3.bias", 64) GETW(a3, wr, "prelu3.weight", 64)
-      GETW(d4, wr, "dense4.weight", 73728) GETW(d4b, wr, "dense4.bias", 128) GETW(a4, wr, "prelu4.weight", 128)
-      GETW(d51, wr, "dense5_1.weight", 256) GETW(d51b, wr, "dense5_1.bias", 2)
-      GETW(d52, wr, "dense5_2.weight", 512) GETW(d52b, wr, "dense5_2.bias", 4)
-      m->rw = RNetW{up_transposed(*m, c1, 28, 3, 3), UP(b1, 28), UP(a1, 28), up_transposed(*m, c2, 48, 28, 3), UP(b2, 48),
-                    UP(a2, 48), up_transposed(*m, c3, 64, 48, 2), UP(b3, 64), UP(a3, 64), up_transposed(*m, d4, 128, 576, 1),
-                    UP(d4b, 128), UP(a4, 128), UP(d51, 256), UP(d51b, 2), UP(d52, 512), UP(d52b, 4)};
-    }
-    {
-      GETW(c1, wo, "conv1.weight", 864) GETW(b1, wo, "conv1.bias", 32) GETW(a1, wo, "prelu1.weight", 32)
-      GETW(c2, wo, "conv2.weight", 18432) GETW(b2, wo, "conv2.bias", 64) GETW(a2, wo, "prelu2.weight", 64)
-      GETW(c3, wo, "conv3.weight", 36864) GETW(b3, wo, "conv3.bias", 64) GETW(a3, wo, "prelu3.weight", 64)
-      GETW(c4, wo, "conv4.weight", 32768) GETW(b4, wo, "conv4.bias", 128) GETW(a4, wo, "prelu4.weight", 128)
-      GETW(d5, wo, "dense5.weight", 294912) GETW(d5b, wo, "dense5.bias", 256) GETW(a5, wo, "prelu5.weight", 256)
-      GETW(d61, wo, "dense6_1.weight", 512) GETW(d61b, wo, "dense6_1.bias", 2)
-      GETW(d62, wo, "dense6_2.weight", 1024) GETW(d62b, wo, "dense6_2.bias", 4)
-      GETW(d63, wo, "dense6_3.weight", 2560) GETW(d63b, wo, "dense6_3.bias", 10)
-      m->ow = ONetW{up_transposed(*m, c1, 32, 3, 3), UP(b1, 32), UP(a1, 32), up_transposed(*m, c2, 64, 32, 3), UP(b2, 64), UP(a2, 64),
-                    up_transposed(*m, c3, 64, 64, 3), UP(b3, 64), UP(a3, 64), up_transposed(*m, c4, 128, 64, 2), UP(b4, 128),
-                    UP(a4, 128), up_transposed(*m, d5, 256, 1152, 1), UP(d5b, 256), UP(a5, 256),
-                    UP(d61, 512), UP(d61b, 2), UP(d62, 1024), UP(d62b, 4), UP(d63, 2560), UP(d63b, 10)};
-    }
-    {
-      static const int lds_nets = getenv("VNF_MTCNN_LDSNETS") ? atoi(getenv("VNF_MTCNN_LDSNETS")) : 0;
-      if (!lds_nets) {
-        m->r_cap = std::min(cfg->max_batch * KEEP, 8192);
-        m->o_cap = std::min(cfg->max_batch * KEEP, 2048);
-        m->renc = new Encoder();
-        m->renc->max_streams = 1;  // the detector shares the GPU with the embedding stream: no forks of its own
-        m->renc->tune_batch = std::max(1, m->r_cap / 2);  // typical stage-2 load, not the capacity
-        // VNF_MTCNN_DTYPE=f32 keeps the R/O-Net plans (and conv1 in net_front_kernel) on the exact-f32 MFMA; the default is
-        // split-f16 (two 16-bit MFMAs per product, ~22 significant bits) for every layer of both nets
-        static const bool plans_f32 = getenv("VNF_MTCNN_DTYPE") && !strcmp(getenv("VNF_MTCNN_DTYPE"), "f32");
-        m->renc->kind = 1; m->renc->arch = -2; m->renc->dtype = F32; m->renc->max_batch = m->r_cap;
-        static const bool front_env = !getenv("VNF_MTCNN_FRONT") || atoi(getenv("VNF_MTCNN_FRONT")) != 0;
-        m->front = front_env;
-        if (m->front && !plans_f32) m->renc->dtype = F16X2;
-        if (m->front) {
-          auto pack_front = [&](WeightMap& wm, int cout, FrontW& fw) -> bool {
-            const float* c1 = wm.get("conv1.weight", (int64_t)cout * 27);
-            const float* b1 = wm.get("conv1.bias", cout);
-            const float* a1 = wm.get("prelu1.weight", cout);
-            if (!c1 || !b1 || !a1) return false;
-            std::vector<float> w(32 * 36, 0.f), b(32, 0.f), a(32, 0.f);
-            for (int co = 0; co < cout; ++co) {
-              for (int c = 0; c < 3; ++c)
-                for (int kh = 0; kh < 3; ++kh)
-                  for (int kw = 0; kw < 3; ++kw) w[(co * 9 + kh * 3 + kw) * 4 + c] = c1[((co * 3 + c) * 3 + kh) * 3 + kw];
-              b[co] = b1[co]; a[co] = a1[co];
-            }
-            fw.w = (const float*)m->upload(w.data(), w.size() * 4);
-            fw.b = (const float*)m->upload(b.data(), b.size() * 4);
-            fw.a = (const float*)m->upload(a.data(), a.size() * 4);
-            return fw.w && fw.b && fw.a;
-          };
-          if (!pack_front(wr, 28, m->rfw) || !pack_front(wo, 32, m->ofw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv1 weights"); }
+      m->r_cap = std::min(cfg->max_batch * KEEP, 8192);
+      m->o_cap = std::min(cfg->max_batch * KEEP, 2048);
+      m->renc = new Encoder();
+      m->renc->max_streams = 1;  // the detector shares the GPU with the embedding stream: no forks of its own
+      m->renc->tune_batch = std::max(1, m->r_cap / 2);  // typical stage-2 load, not the capacity
+      m->renc->kind = 1; m->renc->arch = -2; m->renc->dtype = plans_f32 ? F32 : F16X2; m->renc->max_batch = m->r_cap;
+      auto pack_front = [&](WeightMap& wm, int cout, FrontW& fw) -> bool {
+        const float* c1 = wm.get("conv1.weight", (int64_t)cout * 27);
+        const float* b1 = wm.get("conv1.bias", cout);
+        const float* a1 = wm.get("prelu1.weight", cout);
+        if (!c1 || !b1 || !a1) return false;
+        std::vector<float> w(32 * 36, 0.f), b(32, 0.f), a(32, 0.f);
+        for (int co = 0; co < cout; ++co) {
+          for (int c = 0; c < 3; ++c)
+            for (int kh = 0; kh < 3; ++kh)
+              for (int kw = 0; kw < 3; ++kw) w[(co * 9 + kh * 3 + kw) * 4 + c] = c1[((co * 3 + c) * 3 + kh) * 3 + kw];
+          b[co] = b1[co]; a[co] = a1[co];
         }
-        const bool mid_env = !getenv("VNF_MTCNN_MID") || atoi(getenv("VNF_MTCNN_MID")) != 0;   // read per handle
-        m->mid = mid_env && m->front && m->renc->dtype == F16X2;
-        if (m->mid) {
-          // conv2 weights [cout][cin][3][3] -> MFMA A-fragments of interleaved split-f16: fragment (ct, kb = 2 tap + half),
-          // lane (row r, group g) = the 4 k values (channels 16 half + 4 g .. + 3 of the tap) of output channel 16 ct + r
-          // as (hi, lo) pairs; input channels beyond cin (R-Net: 28 of 32) are zero
-          auto pack_mid = [&](WeightMap& wm, int cout, int cin, MidW& mw) -> bool {
-            const float* c2 = wm.get("conv2.weight", (int64_t)cout * cin * 9);
-            const float* b2 = wm.get("conv2.bias", cout);
-            const float* a2 = wm.get("prelu2.weight", cout);
-            if (!c2 || !b2 || !a2) return false;
-            std::vector<uint32_t> w((size_t)(cout / 16) * 18 * 64 * 4, 0u);
-            for (int ct = 0; ct < cout / 16; ++ct)
-              for (int kb = 0; kb < 18; ++kb)
-                for (int l = 0; l < 64; ++l)
-                  for (int e = 0; e < 4; ++e) {
-                    const int co = 16 * ct + (l & 15), c = 16 * (kb & 1) + 4 * (l >> 4) + e, tap = kb >> 1;
-                    const float v = c < cin ? c2[((size_t)(co * cin + c) * 3 + tap / 3) * 3 + tap % 3] : 0.f;
-                    const sf16 sv(v);
-                    uint32_t bits;
-                    memcpy(&bits, &sv, 4);
-                    w[(((size_t)ct * 18 + kb) * 64 + l) * 4 + e] = bits;
-                  }
-            mw.w = (const uint4*)m->upload(w.data(), w.size() * 4);
-            mw.b = (const float*)m->upload(b2, (size_t)cout * 4);
-            mw.a = (const float*)m->upload(a2, (size_t)cout * 4);
-            return mw.w && mw.b && mw.a;
-          };
-          if (!pack_mid(wr, 48, 28, m->rmw) || !pack_mid(wo, 64, 32, m->omw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv2 weights"); }
-          (void)hipFuncSetAttribute((const void*)net_mid_kernel<23, 64, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 23 * 23 * 128 + 21 * 21 * 8 * 16);
-          (void)hipGetLastError();
-        }
-        int rr = build_rnet(*m->renc, wr, m->front, m->mid);
-        if (rr == VNF_OK) rr = m->renc->finalize();
-        m->oenc = new Encoder();
-        m->oenc->max_streams = 1;
-        m->oenc->tune_batch = std::max(1, m->o_cap / 4);
-        m->oenc->kind = 1; m->oenc->arch = -3; m->oenc->dtype = m->renc->dtype; m->oenc->max_batch = m->o_cap;
-        if (rr == VNF_OK) rr = build_onet(*m->oenc, wo, m->front, m->mid);
-        if (rr == VNF_OK) rr = m->oenc->finalize();
-        if (rr != VNF_OK) { delete m; return rr; }
+        fw.w = (const float*)m->upload(w.data(), w.size() * 4);
+        fw.b = (const float*)m->upload(b.data(), b.size() * 4);
+        fw.a = (const float*)m->upload(a.data(), a.size() * 4);
+        return fw.w && fw.b && fw.a;
+      };
+      if (!pack_front(wr, 28, m->rfw) || !pack_front(wo, 32, m->ofw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv1 weights"); }
+      m->mid = mid_env && m->renc->dtype == F16X2;
+      if (m->mid) {
+        // conv2 weights [cout][cin][3][3] -> MFMA A-fragments of interleaved split-f16: fragment (ct, kb = 2 tap + half),
+        // lane (row r, group g) = the 4 k values (channels 16 half + 4 g .. + 3 of the tap) of output channel 16 ct + r
+        // as (hi, lo) pairs; input channels beyond cin (R-Net: 28 of 32) are zero
+        auto pack_mid = [&](WeightMap& wm, int cout, int cin, MidW& mw) -> bool {
+          const float* c2 = wm.get("conv2.weight", (int64_t)cout * cin * 9);
+          const float* b2 = wm.get("conv2.bias", cout);
+          const float* a2 = wm.get("prelu2.weight", cout);
+          if (!c2 || !b2 || !a2) return false;
+          std::vector<uint32_t> w((size_t)(cout / 16) * 18 * 64 * 4, 0u);
+          for (int ct = 0; ct < cout / 16; ++ct)
+            for (int kb = 0; kb < 18; ++kb)
+              for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 4; ++e) {
+                  const int co = 16 * ct + (l & 15), c = 16 * (kb & 1) + 4 * (l >> 4) + e, tap = kb >> 1;
+                  const float v = c < cin ? c2[((size_t)(co * cin + c) * 3 + tap / 3) * 3 + tap % 3] : 0.f;
+                  const sf16 sv(v);
+                  uint32_t bits;
+                  memcpy(&bits, &sv, 4);
+                  w[(((size_t)ct * 18 + kb) * 64 + l) * 4 + e] = bits;
+                }
+          mw.w = (const uint4*)m->upload(w.data(), w.size() * 4);
+          mw.b = (const float*)m->upload(b2, (size_t)cout * 4);
+          mw.a = (const float*)m->upload(a2, (size_t)cout * 4);
+          return mw.w && mw.b && mw.a;
+        };
+        if (!pack_mid(wr, 48, 28, m->rmw) || !pack_mid(wo, 64, 32, m->omw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv2 weights"); }
       }
+      int rr = build_rnet(*m->renc, wr, m->mid);
+      if (rr == VNF_OK) rr = m->renc->finalize();
+      m->oenc = new Encoder();
+      m->oenc->max_streams = 1;
+      m->oenc->tune_batch = std::max(1, m->o_cap / 4);
+      m->oenc->kind = 1; m->oenc->arch = -3; m->oenc->dtype = m->renc->dtype; m->oenc->max_batch = m->o_cap;
+      if (rr == VNF_OK) rr = build_onet(*m->oenc, wo, m->mid);
+      if (rr == VNF_OK) rr = m->oenc->finalize();
+      if (rr != VNF_OK) { delete m; return rr; }
     }
     const int B = cfg->max_batch;
     m->cap_table = make_levels(cfg->max_height, cfg->max_width, cfg->min_face_size, (double)cfg->factor);
@@ -1888,7 +1402,6 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
     const size_t nseg = (size_t)MAX_LEVELS * B;
     // rows per frame of the stage-2 / stage-3 tables: run-time (max_candidates), at least the LDS fast-path size
     m->keep = std::max(KEEP, cfg->max_candidates);
-    if (!m->renc && m->keep != KEEP) { delete m; return fail(VNF_E_INVALID, "mtcnn: the LDS-resident nets (VNF_MTCNN_LDSNETS) keep the 2048-row tables"); }
     const size_t KR = (size_t)m->keep;
     m->cand = (Cand*)m->dalloc((size_t)B * m->cap_out * sizeof(Cand));
     m->cells = (int*)m->dalloc((size_t)B * m->cap_out * 4);
@@ -1901,7 +1414,6 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
     m->status = m->fin_cnt + B;
     m->rows = (Row*)m->dalloc((size_t)B * KR * sizeof(Row));
     m->rows3 = (Row*)m->dalloc((size_t)B * KR * sizeof(Row));
-    m->crops = m->renc ? (float*)m->dalloc(16) : (float*)m->dalloc((size_t)B * KEEP * 3 * 48 * 48 * 4);   // planar crops: LDS-resident nets only
     m->rout = (float*)m->dalloc((size_t)B * KR * 5 * 4);
     m->oout = (float*)m->dalloc((size_t)B * KR * 15 * 4);
     m->fin = (float*)m->dalloc((size_t)B * KR * 15 * 4);
@@ -1920,41 +1432,34 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
       m->stage = (float*)m->dalloc(sb);
       if (hipHostMalloc((void**)&m->h_pin, sb, hipHostMallocDefault) != hipSuccess) m->h_pin = nullptr;
       if (!m->stage || !m->h_pin) { delete m; return fail(VNF_E_HIP, "mtcnn: read-back buffers"); }
-      if (const char* ff = getenv("VNF_FIN_FAST")) m->fin_fast = std::max(0, std::min(FIN_FAST, atoi(ff)));
     }
     m->offs = (int*)m->dalloc((size_t)(B + 1) * 4);
-    if (!m->lvl || !m->p1 || !m->c2 || !m->cand || !m->cand_cnt || !m->rows || !m->rows3 || !m->crops ||
-        !m->rout || !m->oout || !m->fin || !m->pw.w1 || !m->ow.d63b) {
+    if (!m->lvl || !m->p1 || !m->c2 || !m->cand || !m->cand_cnt || !m->rows || !m->rows3 ||
+        !m->rout || !m->oout || !m->fin || !m->pw.w1) {
       delete m;
       return VNF_E_HIP;
     }
-    // Dynamic LDS above 64 KiB: opt in with the exact sizes (gfx950 has 160 KiB per workgroup).
+    // Dynamic LDS of every launch that requests some: opt in with the exact sizes (above 64 KiB this is needed; gfx950
+    // has 160 KiB per workgroup).  pyramid_rows_kernel takes the fast path only up to 64 KiB.
     // The attribute call is advisory on some ROCm builds; launch errors are checked at run time.
     {
       int lds_max = 0;
       VNF_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device));
-      const int need_img = CAP_LDS_KEYS * 8 + KEEP * 20 + 256 * 20, need_scale = need_img;
-      const int need_post = KEEP * 44 + 256 * 20, need_r = (13552 + 3388 + 864) * 4, need_o = (16928 + 14112 + 6912 + 1152) * 4;
-      (void)hipFuncSetAttribute((const void*)nms_image_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_img);
-      (void)hipFuncSetAttribute((const void*)net_front_kernel<24, 11, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-      (void)hipFuncSetAttribute((const void*)net_front_kernel<24, 11, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-      {
-        int wmax = 0;
-        for (int l = 0; l < m->cap_table.n; ++l) wmax = std::max(wmax, m->cap_table.l[l].Ws);
-        wmax = (int)(wmax * 1.1) + 64;   // same head-room as the level buffers
-        const int need_p1 = std::min((12 * (wmax + 64) + 10 * ((wmax - 1) / 2)) * 4, 160 * 1024);
-        if (hipFuncSetAttribute((const void*)pnet_conv1_pool_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_p1) == hipSuccess)
-          m->pnet1_lds = need_p1;
+      const std::pair<const void*, int> need[] = {
+          {(const void*)nms_scale_kernel, LDS_NMS}, {(const void*)nms_image_kernel, LDS_NMS},
+          {(const void*)stage2_post_kernel, LDS_POST}, {(const void*)stage3_post_kernel, LDS_POST},
+          {(const void*)net_front_kernel<24, 11, 512, true>, LDS_RFRONT}, {(const void*)net_front_kernel<24, 11, 512, false>, LDS_RFRONT},
+          {(const void*)net_front_kernel<48, 4, 512, true>, LDS_OFRONT}, {(const void*)net_front_kernel<48, 4, 512, false>, LDS_OFRONT},
+          {(const void*)net_mid_kernel<11, 48, 6, 1>, LDS_RMID}, {(const void*)net_mid_kernel<23, 64, 8, 2>, LDS_OMID}};
+      int need_max = 0;
+      for (const auto& kn : need) {
+        (void)hipFuncSetAttribute(kn.first, hipFuncAttributeMaxDynamicSharedMemorySize, kn.second);
+        need_max = std::max(need_max, kn.second);
       }
-      (void)hipFuncSetAttribute((const void*)nms_scale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_scale);
-      (void)hipFuncSetAttribute((const void*)stage2_post_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_post);
-      (void)hipFuncSetAttribute((const void*)stage3_post_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_post);
-      (void)hipFuncSetAttribute((const void*)rnet_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_r);
-      (void)hipFuncSetAttribute((const void*)onet_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, need_o);
       (void)hipGetLastError();
-      if (lds_max < need_o) {
+      if (lds_max < need_max) {
         delete m;
-        return fail(VNF_E_INVALID, "mtcnn: device reports " + std::to_string(lds_max) + " B of LDS per workgroup, need " + std::to_string(need_o));
+        return fail(VNF_E_INVALID, "mtcnn: device reports " + std::to_string(lds_max) + " B of LDS per workgroup, need " + std::to_string(need_max));
       }
     }
     VNF_HIP(hipDeviceSynchronize());
@@ -2027,16 +1532,9 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
   const double fB = (double)B;
   mark("pyramid", fB * ((double)H * W * 3 + (double)t.tot_px * 12));
   {
-    int rows = 0, wmax = 0;
-    for (int l = 0; l < t.n; ++l) { rows += t.l[l].Hp; wmax = std::max(wmax, t.l[l].Ws); }
-    const size_t lds = ((size_t)12 * (wmax + 64) + (size_t)10 * ((wmax - 1) / 2)) * 4;
-    static const int p1_mode = getenv("VNF_PNET1") ? atoi(getenv("VNF_PNET1")) : 2;   // 0 VALU, 1 MFMA via LDS, 2 MFMA direct
-    if (p1_mode == 2)
-      hipLaunchKernelGGL(pnet_conv1_pool_direct_kernel, dim3(B, rows), dim3(256), 0, s, m->lvl, t, m->pw, m->p1);
-    else if (p1_mode == 1 && lds <= (size_t)m->pnet1_lds)
-      hipLaunchKernelGGL(pnet_conv1_pool_mfma_kernel, dim3(rows, B), dim3(256), lds, s, m->lvl, t, m->pw, m->p1);
-    else
-      hipLaunchKernelGGL(pnet_conv1_pool_kernel, dim3((t.tot_p1 + 255) / 256, B), dim3(256), 0, s, m->lvl, t, m->pw, m->p1);
+    int rows = 0;
+    for (int l = 0; l < t.n; ++l) rows += t.l[l].Hp;
+    hipLaunchKernelGGL(pnet_conv1_pool_direct_kernel, dim3(B, rows), dim3(256), 0, s, m->lvl, t, m->pw, m->p1);
   }
   mark("pnet_conv1_pool", fB * ((double)t.tot_px * 12 + (double)t.tot_p1 * 40));
   hipLaunchKernelGGL(pnet_conv2_kernel, dim3(B, (t.tot_c2 + 255) / 256), dim3(256), 0, s, m->p1, t, m->pw, m->c2);
@@ -2045,10 +1543,9 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
   hipLaunchKernelGGL(pnet_conv3_heads_kernel, dim3((t.tot_out + 255) / 256, B), dim3(256), 0, s, m->c2, t, m->pw,
                      cfg.thresholds[0], B, cap_out, m->cand, m->cells, m->cand_cnt, m->prob_dbg, m->reg_dbg);
   mark("pnet_conv3_heads", fB * (double)t.tot_c2 * 64);
-  const size_t lds_nms = (size_t)CAP_LDS_KEYS * 8 + KEEP * 20 + 256 * 20;
-  hipLaunchKernelGGL(nms_scale_kernel, dim3(t.n, B), dim3(256), lds_nms, s, m->cand, m->cells, m->cand_cnt, t, B, cap_out, 0.5f,
+  hipLaunchKernelGGL(nms_scale_kernel, dim3(t.n, B), dim3(256), LDS_NMS, s, m->cand, m->cells, m->cand_cnt, t, B, cap_out, 0.5f,
                      m->keep1c, m->keep1_cnt, m->status, m->scratch);
-  hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(256), lds_nms, s, m->cand, m->keep1c, m->keep1_cnt, t, B, cap_out, 0.7f, W, H,
+  hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(256), LDS_NMS, s, m->cand, m->keep1c, m->keep1_cnt, t, B, cap_out, 0.7f, W, H,
                      KR, m->rows, m->row_cnt, m->status, m->scratch);
   VNF_HIP(hipGetLastError());
   mark("nms_stage1", 0);
@@ -2083,32 +1580,25 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
       const int n = std::min(cap, total - c0);
       crop(rws, cntp, maxc, S, (float*)enc->bufs[0].ptr, m->offs, c0, n);
       mark(S == 24 ? "crop_resize_24" : "crop_resize_48", (double)n * S * S * 16);  // output bytes only (NHWC4 fp32)
-      if (m->front) {
-        const bool split = enc->dtype == F16X2;
-        const float* cin = (const float*)enc->bufs[0].ptr;
-        float* pout = (float*)enc->bufs[1].ptr;
-        const size_t lr = (25 * 24 + 22 * 22 * 8) * 16, lo = (11 * 48 + 9 * 46 * 8) * 16;   // (IR * S + conv rows * C * 8) float4
-        // R-Net: the whole candidate in one workgroup of 8 waves (no band overlap to recompute; measured 0.065 ms against
-        // 0.074 for two bands x 4 waves); O-Net: bands of 4 pooled rows x 8 waves (larger bands / 16 waves were slower)
-        // conv1 of the split-f16 plans on the 16-bit MFMA as well (VNF_MTCNN_FRONT16=0: exact-fp32 conv1, three times the
-        // MFMA time); the f32 plans (VNF_MTCNN_DTYPE=f32) always take the exact kernel
-        static const bool mm16 = !getenv("VNF_MTCNN_FRONT16") || atoi(getenv("VNF_MTCNN_FRONT16")) != 0;
-        if (S == 24 && split && mm16) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, true, true>), dim3(1, n), dim3(512), lr, s, cin, m->rfw, pout);
-        else if (S == 48 && split && mm16) hipLaunchKernelGGL((net_front_kernel<48, 4, 512, true, true>), dim3(6, n), dim3(512), lo, s, cin, m->ofw, pout);
-        else if (S == 24 && split) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, true>), dim3(1, n), dim3(512), lr, s, cin, m->rfw, pout);
-        else if (S == 24) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, false>), dim3(1, n), dim3(512), lr, s, cin, m->rfw, pout);
-        else if (split) hipLaunchKernelGGL((net_front_kernel<48, 4, 512, true>), dim3(6, n), dim3(512), lo, s, cin, m->ofw, pout);
-        else hipLaunchKernelGGL((net_front_kernel<48, 4, 512, false>), dim3(6, n), dim3(512), lo, s, cin, m->ofw, pout);
-        mark(S == 24 ? "rnet_front" : "onet_front", 0);
-        if (m->mid) {   // conv2 + PReLU + pool2: buffer 1 -> buffer 3 (the plan starts at conv3)
-          float* p2o = (float*)enc->bufs[3].ptr;
-          if (S == 24) hipLaunchKernelGGL((net_mid_kernel<11, 48, 6, 1>), dim3(n), dim3(384), 11 * 11 * 128 + 9 * 9 * 12 * 16, s, pout, m->rmw, p2o);
-          else hipLaunchKernelGGL((net_mid_kernel<23, 64, 8, 2>), dim3(n), dim3(512), 23 * 23 * 128 + 21 * 21 * 8 * 16, s, pout, m->omw, p2o);
-        }
+      const bool split = enc->dtype == F16X2;
+      const float* cin = (const float*)enc->bufs[0].ptr;
+      float* pout = (float*)enc->bufs[1].ptr;
+      // R-Net: the whole candidate in one workgroup of 8 waves (no band overlap to recompute; measured 0.065 ms against
+      // 0.074 for two bands x 4 waves); O-Net: bands of 4 pooled rows x 8 waves (larger bands / 16 waves were slower)
+      if (S == 24 && split) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, true>), dim3(1, n), dim3(512), LDS_RFRONT, s, cin, m->rfw, pout);
+      else if (S == 24) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, false>), dim3(1, n), dim3(512), LDS_RFRONT, s, cin, m->rfw, pout);
+      else if (split) hipLaunchKernelGGL((net_front_kernel<48, 4, 512, true>), dim3(6, n), dim3(512), LDS_OFRONT, s, cin, m->ofw, pout);
+      else hipLaunchKernelGGL((net_front_kernel<48, 4, 512, false>), dim3(6, n), dim3(512), LDS_OFRONT, s, cin, m->ofw, pout);
+      VNF_HIP(hipGetLastError());
+      mark(S == 24 ? "rnet_front" : "onet_front", 0);
+      if (m->mid) {   // conv2 + PReLU + pool2: buffer 1 -> buffer 3 (the plan starts at conv3)
+        float* p2o = (float*)enc->bufs[3].ptr;
+        if (S == 24) hipLaunchKernelGGL((net_mid_kernel<11, 48, 6, 1>), dim3(n), dim3(384), LDS_RMID, s, pout, m->rmw, p2o);
+        else hipLaunchKernelGGL((net_mid_kernel<23, 64, 8, 2>), dim3(n), dim3(512), LDS_OMID, s, pout, m->omw, p2o);
+        VNF_HIP(hipGetLastError());
       }
-      static const bool layers = getenv("VNF_MTCNN_LAYERS") != nullptr;   // diagnostic: per-layer table on stderr
       std::string rep;
-      int rc = enc->run(nullptr, n, VNF_F32, nullptr, s, prof && layers ? &rep : nullptr);
+      int rc = enc->run(nullptr, n, VNF_F32, nullptr, s, prof && m->layers ? &rep : nullptr);
       if (rc != VNF_OK) return rc;
       if (!rep.empty()) fprintf(stderr, "%s n=%d\n%s", S == 24 ? "rnet" : "onet", n, rep.c_str());
       mark(S == 24 ? "rnet" : "onet", 0);
@@ -2117,30 +1607,19 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
     }
     return VNF_OK;
   };
-  const size_t lds_post = (size_t)KEEP * 28 + 256 * 20 + KEEP * 16;
   auto stage2 = [&](int max2, int total2) -> int {
-    if (m->renc) {
-      const int rc = run_net(m->renc, m->r_cap, m->rows, m->row_cnt, max2, total2, 24, 8, m->rout, 5);
-      if (rc != VNF_OK) return rc;
-    } else {
-      crop(m->rows, m->row_cnt, max2, 24, m->crops, nullptr, 0, 0);
-      hipLaunchKernelGGL(rnet_kernel, dim3(max2, B), dim3(256), (13552 + 3388 + 864) * 4, s, m->crops, m->row_cnt, m->rw, m->rout);
-    }
-    hipLaunchKernelGGL(stage2_post_kernel, dim3(B), dim3(256), lds_post, s, m->rows, m->row_cnt, m->rout, cfg.thresholds[1], 0.7f,
+    const int rc = run_net(m->renc, m->r_cap, m->rows, m->row_cnt, max2, total2, 24, 8, m->rout, 5);
+    if (rc != VNF_OK) return rc;
+    hipLaunchKernelGGL(stage2_post_kernel, dim3(B), dim3(256), LDS_POST, s, m->rows, m->row_cnt, m->rout, cfg.thresholds[1], 0.7f,
                        W, H, KR, m->rows3, m->row3_cnt, m->status, m->scratch);
     VNF_HIP(hipGetLastError());
     mark("stage2_post", 0);
     return VNF_OK;
   };
   auto stage3 = [&](int max3, int total3) -> int {
-    if (m->oenc) {
-      const int rc = run_net(m->oenc, m->o_cap, m->rows3, m->row3_cnt, max3, total3, 48, 16, m->oout, 15);
-      if (rc != VNF_OK) return rc;
-    } else {
-      crop(m->rows3, m->row3_cnt, max3, 48, m->crops, nullptr, 0, 0);
-      hipLaunchKernelGGL(onet_kernel, dim3(max3, B), dim3(512), (16928 + 14112 + 6912 + 1152) * 4, s, m->crops, m->row3_cnt, m->ow, m->oout);
-    }
-    hipLaunchKernelGGL(stage3_post_kernel, dim3(B), dim3(256), lds_post, s, m->rows3, m->row3_cnt, m->oout, cfg.thresholds[2], 0.7f,
+    const int rc = run_net(m->oenc, m->o_cap, m->rows3, m->row3_cnt, max3, total3, 48, 16, m->oout, 15);
+    if (rc != VNF_OK) return rc;
+    hipLaunchKernelGGL(stage3_post_kernel, dim3(B), dim3(256), LDS_POST, s, m->rows3, m->row3_cnt, m->oout, cfg.thresholds[2], 0.7f,
                        cfg.select_largest, KR, m->fin, m->fin_cnt, m->status, m->scratch);
     m->last_b = B;
     hipLaunchKernelGGL(pack_results_kernel, dim3(B), dim3(256), 0, s, m->row_cnt, ncnt, m->fin, m->fin_cnt, B, KR, m->stage);
@@ -2169,11 +1648,10 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
   // head room size this call's launches, and the one read-back at the end tells whether they covered it.  If not (or on
   // the first call of a frame size) stage-1's counts are read and stages 2 / 3 run with exact bounds: stage 2 by its
   // own counts, stage 3 by stage 2's (it only filters stage-2 rows) -- never a second mid-cascade synchronisation.
-  static const int spec_on = getenv("VNF_MTCNN_SPEC") ? atoi(getenv("VNF_MTCNN_SPEC")) : 1;
   Mtcnn::Spec& sp = m->spec;
   int r = VNF_OK;
   bool exact_needed = true;
-  if (spec_on && sp.valid && sp.b == B && sp.H == H && sp.W == W) {
+  if (m->spec_on && sp.valid && sp.b == B && sp.H == H && sp.W == W) {
     r = stage2(sp.max2, sp.total2);
     if (r == VNF_OK) r = stage3(sp.max3, sp.total3);
     if (r == VNF_OK) r = readback();
@@ -2322,8 +1800,7 @@ extern "C" int vnf_mtcnn_debug_stage3(vnf_handle h, const float* boxes, const fl
     VNF_HIP(hipMemcpyAsync(m->oout, onet_out, (size_t)n * 15 * 4, hipMemcpyHostToDevice, s));
     VNF_HIP(hipMemcpyAsync(m->row3_cnt, &n, 4, hipMemcpyHostToDevice, s));
     VNF_HIP(hipMemsetAsync(m->status, 0, 4, s));
-    const size_t lds_post = (size_t)KEEP * 28 + 256 * 20 + KEEP * 16;
-    hipLaunchKernelGGL(stage3_post_kernel, dim3(1), dim3(256), lds_post, s, m->rows3, m->row3_cnt, m->oout, m->cfg.thresholds[2],
+    hipLaunchKernelGGL(stage3_post_kernel, dim3(1), dim3(256), LDS_POST, s, m->rows3, m->row3_cnt, m->oout, m->cfg.thresholds[2],
                        0.7f, m->cfg.select_largest, m->keep, m->fin, m->fin_cnt, m->status, m->scratch);
     VNF_HIP(hipGetLastError());
     int nk = 0;

@@ -316,8 +316,9 @@ class FacePipeline:
         """Throughput mode: enqueue one frame batch and return a ticket without waiting for it.  `ready`: event after
         which frames_dev is resident (upload.FrameUploader's copy stream); default: the caller's current stream.
 
-        Detection runs on a detection stream (it synchronises with the host three times to size the candidate
-        tables: detect_face.py's own stage boundaries); alignment + embedding (+ classification) run on the
+        Detection runs on a detection stream (it synchronises with the host once when the previous call's candidate
+        counts cover this batch's, twice otherwise, plus once per new frame size for the pyramid row order -- where
+        detect_face.py stops at its own stage boundaries); alignment + embedding (+ classification) run on the
         embedding stream, so the embedding of batch i overlaps the detection of batch i+1.  With several
         detector handles (`FacePipeline(detector=[d0, d1], ...)`) each gets a host thread and a stream, so
         detections also overlap each other across their host synchronisations; batches go round-robin and
