@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box: print a digest of the IRv1 embeddings of a fixed batch (compare plans: VNF_FUSE17=0/1, VNF_FORCE_CFG=...)."""
+"""GPU box: print a digest of the IRv1 embeddings of a fixed batch (compare plans: VNF_FUSE=0/31, VNF_FORCE_CFG=...)."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: VNF_PATCH_STAMP=<file> python tools/stamp_patch.py -> in-kernel cycle stamps of the patch kernel's
-{256,192,4,2,3} bf16 launches (conv2d_4a), see conv_patch.hip launch_patch_stamped."""
+{256,192,4,2,3} bf16 launches (conv2d_4a), see conv_patch.hip launch_patch_stamped.  Needs the library built with
+python -m vn_celeb_face_recognition_amd.build --stamps; the default build ignores the variable."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""GPU box: VNF_WS_STAMP=<file> VNF_AUTOTUNE=0 VNF_FORCE_CFG=56 python tools/stamp_ws.py -> in-kernel stamps of the
-wave-specialised kernel on the layers it fits (see conv_ws.hip launch_stamped)."""
+"""GPU box: VNF_WS_STAMP=<file> VNF_AUTOTUNE=0 VNF_FORCE_CFG=64 python tools/stamp_ws.py -> in-kernel stamps of the
+wave-specialised kernel on the layers it fits (see conv_ws.hip launch_stamped).  Needs the library built with
+python -m vn_celeb_face_recognition_amd.build --stamps; the default build ignores the variable."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

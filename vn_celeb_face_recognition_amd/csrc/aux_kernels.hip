@@ -220,9 +220,7 @@ __global__ void __launch_bounds__(256) stem_conv1a_mfma_kernel(const TI* __restr
 }
 
 template <typename TI>
-static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, int n, const float* wt, hipStream_t s) {
-  const char* e1a = getenv("VNF_STEM1A_MFMA");   // read per launch: the parity test flips it inside one process
-  const bool mfma = !(e1a && atoi(e1a) == 0);
+static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, int n, const float* wt, bool mfma, hipStream_t s) {
   if (mfma && n > 0 && (dtype == BF16 || dtype == F16 || dtype == F16P)) {
     const unsigned ngroups = ((unsigned)n * 79 * 79 + 15) / 16;
     const int blocks = (int)((ngroups + 15) / 16 < 2048 ? (ngroups + 15) / 16 : 2048);   // 4 waves x 4 groups per block round
@@ -244,11 +242,12 @@ static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, 
   return hipGetLastError();
 }
 
-hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, hipStream_t s) {
+hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, bool mfma,
+                              hipStream_t s) {
   switch (x_dtype) {
-    case F32: return stem_dispatch_out<float>(x, y, ldy, dtype, n, wt, s);
-    case BF16: return stem_dispatch_out<__bf16>(x, y, ldy, dtype, n, wt, s);
-    case F16: return stem_dispatch_out<_Float16>(x, y, ldy, dtype, n, wt, s);
+    case F32: return stem_dispatch_out<float>(x, y, ldy, dtype, n, wt, mfma, s);
+    case BF16: return stem_dispatch_out<__bf16>(x, y, ldy, dtype, n, wt, mfma, s);
+    case F16: return stem_dispatch_out<_Float16>(x, y, ldy, dtype, n, wt, mfma, s);
   }
   return hipErrorInvalidValue;
 }

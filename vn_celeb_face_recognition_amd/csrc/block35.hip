@@ -346,20 +346,9 @@ hipError_t block35_repack(const Block35Pack& p, void* out, hipStream_t s) {
 
 hipError_t launch_block35(const Block35Args& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)block35_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, B35_LDS);
-    (void)hipFuncSetAttribute((const void*)block35_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, B35_LDS);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
-  if (dtype == BF16)
-    hipLaunchKernelGGL(block35_kernel<__bf16>, dim3(a.n), dim3(512), B35_LDS, s, a);
-  else if (dtype == F16)
-    hipLaunchKernelGGL(block35_kernel<_Float16>, dim3(a.n), dim3(512), B35_LDS, s, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  if (dtype == BF16) return launch_with_lds<block35_kernel<__bf16>>(a.n, 512, B35_LDS, s, a);
+  if (dtype == F16) return launch_with_lds<block35_kernel<_Float16>>(a.n, 512, B35_LDS, s, a);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf

@@ -390,12 +390,7 @@ hipError_t block35s_repack(const Block35Pack& p, void* out, hipStream_t s) {
 
 hipError_t launch_block35s(const Block35Args& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)block35_split_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, S35_LDS);
-  (void)attr;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(block35_split_kernel, dim3(a.n), dim3(512), S35_LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds<block35_split_kernel>(a.n, 512, S35_LDS, s, a);
 }
 
 }  // namespace vnf

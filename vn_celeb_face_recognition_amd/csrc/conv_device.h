@@ -1,6 +1,8 @@
 // Device-side building blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip: LDS-DMA ring
 // kernel; conv_patch.hip: LDS-resident input patch kernel).
 #pragma once
+#include <atomic>
+
 #include "kernels.h"
 #include "split_f16.h"
 
@@ -33,6 +35,30 @@ struct KArgs {  // device-side copy of ConvArgs (POD)
   int lds_bytes;  // patch kernel: dynamic LDS of the launch (what the epilogue may stage into)
   long long* dbg;  // in-kernel stamp buffer of the instrumented build (tools), else null
 };
+
+// Host side, in front of every launch that asks for more dynamic LDS than the default: opt `Kernel` in to `bytes`, once
+// per (kernel instantiation, device).  Steady state: hipGetDevice and one atomic load, no lock; threads that race to be
+// first on a device each set the attribute, which is harmless.  The attribute is advisory on this ROCm, so its status is
+// dropped and the sticky error cleared: the launch error is what the callers check.
+template <auto Kernel>
+inline void allow_dynamic_lds(int bytes) {
+  static std::atomic<unsigned> done{0};   // bit d: set on device d
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const unsigned bit = (unsigned)dev < 16 ? 1u << dev : 0;   // past 16 devices: set on every launch
+  if (done.load(std::memory_order_acquire) & bit) return;
+  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)hipGetLastError();
+  done.fetch_or(bit, std::memory_order_release);
+}
+
+// the fused kernels: opt in to the launch's own dynamic LDS, launch, return the launch status
+template <auto Kernel, class Args>
+inline hipError_t launch_with_lds(int grid, int block, int lds, hipStream_t s, const Args& a) {
+  allow_dynamic_lds<Kernel>(lds);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, s, a);
+  return hipGetLastError();
+}
 
 template <typename T>
 __device__ __forceinline__ void mma_chunk(f32x4_t& acc, const uint4& wf, const uint4& xf);

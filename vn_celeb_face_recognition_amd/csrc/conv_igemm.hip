@@ -28,6 +28,7 @@
 //
 // dtype paths: bf16 / f16 -> v_mfma_f32_16x16x32_{bf16,f16}; f32 -> v_mfma_f32_16x16x4_f32
 // (exact f32 FMA chain; the <=1e-4 parity path).
+#include <mutex>
 #include <type_traits>
 
 #include "block35.h"
@@ -280,13 +281,16 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs
 // ===================================================================== host launch
 static const char* zero_page() {  // per-device 256 zero bytes for padded / out-of-range gather sources
   static char* z[16] = {nullptr};
+  static std::once_flag once[16];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  if (!z[dev]) {
-    if (hipMalloc((void**)&z[dev], 256) != hipSuccess) return nullptr;
-    (void)hipMemset(z[dev], 0, 256);
+  std::call_once(once[dev], [dev] {
+    char* p = nullptr;
+    if (hipMalloc((void**)&p, 256) != hipSuccess) return;
+    (void)hipMemset(p, 0, 256);
     (void)hipDeviceSynchronize();  // once per device: the page must be zero before any stream reads it
-  }
+    z[dev] = p;
+  });
   return z[dev];
 }
 
@@ -294,16 +298,9 @@ const char* conv_zero_page() { return zero_page(); }
 
 template <typename T, int BM, int BN, int WM, int WN, int S>
 static hipError_t launch_dma(const KArgs& k, hipStream_t s) {
-  constexpr int ring = S * (BM + BN) * 128;
-  static bool attr_done = false;
+  allow_dynamic_lds<conv_igemm_dma_kernel<T, BM, BN, WM, WN, S>>(160 * 1024);
   KArgs kk = k;
-  const int lds = ring;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<T, BM, BN, WM, WN, S>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
+  const int lds = S * (BM + BN) * 128;
   const int tiles_m = (k.M + BM - 1) / BM;
   kk.tiles_n = (k.Cout + BN - 1) / BN;
   kk.nblk = tiles_m * kk.tiles_n;

@@ -18,14 +18,13 @@
 //   patch + ((vb(p)-v0 + kh)*Wp + ox(p) + kw)*PP*16 + cc*16  =  pb[p] + ptab[k-chunk]
 // -- one add per fragment read, the table is built from the layer's ktab.  K tiles, MFMA operand
 // roles and the epilogue are those of conv_igemm.hip, so results are bit-identical to it.
-#include <cstdio>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <tuple>
 #include <type_traits>
 
 #include "conv_device.h"
+#include "stamp.h"
 
 namespace vnf {
 
@@ -333,13 +332,7 @@ bool patch_cfg_ok(const ConvArgs& a, int pcfg) {
 
 template <typename T, int BM, int BN, int WM, int WN, int S>
 static hipError_t launch_one(const KArgs& k, int lds, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_patch_kernel<T, BM, BN, WM, WN, S>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
+  allow_dynamic_lds<conv_patch_kernel<T, BM, BN, WM, WN, S>>(160 * 1024);
   KArgs kk = k;
   const int tiles_m = (k.M + BM - 1) / BM;
   kk.tiles_n = (k.Cout + BN - 1) / BN;
@@ -382,33 +375,28 @@ static hipError_t launch_patch_typed(int pcfg, const KArgs& k, int lds, hipStrea
 // Instrumented launch (tools/stamp_patch.py): VNF_PATCH_STAMP=<file> dumps cycle stamps of workgroup 700 of every bf16
 // {256,192,4,2,3} launch with more than 700 workgroups: start, prologue issued, before / after the barrier of every K
 // tile, K loop done, epilogue barrier, end.
+#ifdef VNF_STAMPS
 static hipError_t launch_patch_stamped(const KArgs& k, int lds, hipStream_t s) {
-  static long long* dbuf = nullptr;
-  const int n = 8 * 40;
-  if (!dbuf && hipMalloc((void**)&dbuf, n * 8) != hipSuccess) return hipErrorOutOfMemory;
-  (void)hipMemsetAsync(dbuf, 0, n * 8, s);
   KArgs kk = k;
-  kk.dbg = dbuf;
   kk.tiles_n = (k.Cout + 191) / 192;
   kk.nblk = ((k.M + 255) / 256) * kk.tiles_n;
-  (void)hipFuncSetAttribute((const void*)conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  static long long host[8 * 40];
-  (void)hipMemcpy(host, dbuf, n * 8, hipMemcpyDeviceToHost);
-  if (FILE* f = fopen(getenv("VNF_PATCH_STAMP"), "a")) {
-    fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
-    for (int w = 0; w < 8; ++w) {
-      fprintf(f, "%d", w);
-      for (int i = 0; i < 40; ++i) fprintf(f, " %lld", host[w * 40 + i] ? host[w * 40 + i] - host[0] : -1LL);
-      fprintf(f, "\n");
-    }
-    fclose(f);
-  }
-  return hipSuccess;
+  return stamped_launch(
+      "VNF_PATCH_STAMP", 8 * 40, s,
+      [&](long long* dbuf) {
+        kk.dbg = dbuf;
+        allow_dynamic_lds<conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>>(160 * 1024);
+        hipLaunchKernelGGL((conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
+      },
+      [&](FILE* f, const long long* host) {
+        fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
+        for (int w = 0; w < 8; ++w) {
+          fprintf(f, "%d", w);
+          for (int i = 0; i < 40; ++i) fprintf(f, " %lld", host[w * 40 + i] ? host[w * 40 + i] - host[0] : -1LL);
+          fprintf(f, "\n");
+        }
+      });
 }
+#endif
 
 hipError_t launch_patch(const ConvArgs& a, const KArgs& k, int pcfg, hipStream_t s) {
   if (!patch_cfg_ok(a, pcfg) || !k.zero) return hipErrorInvalidValue;
@@ -417,8 +405,10 @@ hipError_t launch_patch(const ConvArgs& a, const KArgs& k, int pcfg, hipStream_t
   KArgs kk = k;
   kk.KH = a.KH; kk.KW = a.KW; kk.Cin = a.Cin;
   kk.pp = g.pp; kk.Wp = g.Wp; kk.Hv = g.Hv; kk.patch_bytes = g.patch_bytes; kk.lds_bytes = g.lds;
+#ifdef VNF_STAMPS
   if (getenv("VNF_PATCH_STAMP") && pcfg == 7 && a.dtype == BF16 && ((k.M + 255) / 256) * ((k.Cout + 191) / 192) > 700)
     return launch_patch_stamped(kk, g.lds, s);
+#endif
   switch (a.dtype) {
     case BF16: return launch_patch_typed<__bf16>(pcfg, kk, g.lds, s);
     case F16: return launch_patch_typed<_Float16>(pcfg, kk, g.lds, s);

@@ -13,11 +13,10 @@
 // for it) and stage (kt-1) % S is free (the consumers drained their reads of it), so the loaders
 // refill it while the consumers multiply tile kt.  Same K order, operand roles and epilogue as the
 // ring kernel, so results are bit-identical to it.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_device.h"
+#include "stamp.h"
 
 namespace vnf {
 
@@ -615,13 +614,7 @@ bool ws_cfg_ok(const ConvArgs& a, int wcfg) {
 
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW>
 static hipError_t launch_one_tile(const KArgs& k, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_ws_kernel<T, BM, BN, WM, WN, S, LW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
+  allow_dynamic_lds<conv_igemm_ws_kernel<T, BM, BN, WM, WN, S, LW>>(160 * 1024);
   KArgs kk = k;
   const int lds = S * (BM + BN) * 128 + k.nkt * 8 * 16;
   const int tiles_m = (k.M + BM - 1) / BM;
@@ -632,32 +625,25 @@ static hipError_t launch_one_tile(const KArgs& k, hipStream_t s) {
   return hipGetLastError();
 }
 
-static int cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-    n = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  return n;
+static int cu_count() {   // of the current device
+  static std::atomic<int> n[16];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+  int c = n[dev].load(std::memory_order_relaxed);
+  if (c) return c;
+  hipDeviceProp_t p;
+  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
+  n[dev].store(c = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256, std::memory_order_relaxed);
+  return c;
 }
 
-// the persistent form (bias + ReLU layers of the 2-byte plans; VNF_WS_PERSIST=0 keeps one tile per workgroup)
-static bool ws_persistent(const KArgs& k) {
-  const char* e = getenv("VNF_WS_PERSIST");   // read per launch: the parity test flips it inside one process
-  return !(e && atoi(e) == 0) && k.ncls == 1 && !k.out_f32;
-}
+// the persistent form (bias + ReLU layers of the 2-byte plans; ConvArgs::ws_persist = 0, from VNF_WS_PERSIST=0 at the
+// handle's create, keeps one tile per workgroup)
+static bool ws_persistent(const ConvArgs& a, const KArgs& k) { return a.ws_persist && k.ncls == 1 && !k.out_f32; }
 
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW, bool RES>
 static hipError_t launch_persistent(const KArgs& k, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_wsp_kernel<T, BM, BN, WM, WN, S, LW, RES>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
+  allow_dynamic_lds<conv_igemm_wsp_kernel<T, BM, BN, WM, WN, S, LW, RES>>(160 * 1024);
   KArgs kk = k;
   const int lds = S * (BM + BN) * 128 + k.nkt * 8 * 16;
   kk.tiles_n = (k.Cout + BN - 1) / BN;
@@ -665,7 +651,8 @@ static hipError_t launch_persistent(const KArgs& k, hipStream_t s) {
   // one workgroup per CU per LDS-resident copy; whole rounds of 8 workgroups keep the blockIdx -> XCD map of xcd_remap
   // (tile t runs on XCD t % 8)
   const int per_cu = lds <= 80 * 1024 ? 2 : 1;
-  int grid = kk.nblk < cu_count() * per_cu ? kk.nblk : (cu_count() * per_cu) & ~7;
+  const int slots = cu_count() * per_cu;
+  int grid = kk.nblk < slots ? kk.nblk : slots & ~7;
   if (grid < 1) grid = kk.nblk;
   hipLaunchKernelGGL((conv_igemm_wsp_kernel<T, BM, BN, WM, WN, S, LW, RES>), dim3(grid), dim3((WM * WN + LW) * 64), lds, s,
                      kk);
@@ -673,9 +660,9 @@ static hipError_t launch_persistent(const KArgs& k, hipStream_t s) {
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW>
-static hipError_t launch_one(const KArgs& k, hipStream_t s) {
+static hipError_t launch_one(const ConvArgs& a, const KArgs& k, hipStream_t s) {
   if constexpr ((sizeof(T) == 2 || is_planar<T>::value) && (BN / WN / 16) % 2 == 0) {
-    if (ws_persistent(k)) {
+    if (ws_persistent(a, k)) {
       if (!k.res) return launch_persistent<T, BM, BN, WM, WN, S, LW, false>(k, s);
       // residual chunks live in registers for the whole K loop: small tiles only
       if constexpr (sizeof(T) == 2 && (BM / WM / 16) * (BN / WN / 32) <= 8)
@@ -686,72 +673,69 @@ static hipError_t launch_one(const KArgs& k, hipStream_t s) {
 }
 
 template <typename T>
-static hipError_t launch_ws_typed(int wcfg, const KArgs& k, hipStream_t s) {
+static hipError_t launch_ws_typed(int wcfg, const ConvArgs& a, const KArgs& k, hipStream_t s) {
   switch (wcfg) {
-    case 0: return launch_one<T, 256, 128, 2, 2, 3, 4>(k, s);
-    case 1: return launch_one<T, 256, 128, 4, 1, 3, 4>(k, s);
-    case 2: return launch_one<T, 128, 128, 2, 2, 3, 4>(k, s);
-    case 3: return launch_one<T, 128, 128, 2, 2, 4, 4>(k, s);
-    case 4: return launch_one<T, 256, 64, 4, 1, 3, 4>(k, s);
-    case 5: return launch_one<T, 128, 192, 2, 2, 3, 4>(k, s);
-    case 6: return launch_one<T, 128, 256, 2, 2, 3, 4>(k, s);
-    case 7: return launch_one<T, 128, 64, 2, 2, 4, 4>(k, s);
-    case 8: return launch_one<T, 256, 128, 2, 2, 3, 2>(k, s);
-    case 9: return launch_one<T, 128, 128, 2, 2, 4, 2>(k, s);
-    case 10: return launch_one<T, 128, 192, 2, 2, 3, 2>(k, s);
-    case 11: return launch_one<T, 192, 128, 2, 2, 3, 4>(k, s);
-    case 12: return launch_one<T, 160, 256, 2, 2, 3, 4>(k, s);
-    case 13: return launch_one<T, 160, 192, 2, 2, 3, 4>(k, s);
-    case 14: return launch_one<T, 64, 64, 2, 2, 4, 4>(k, s);
-    case 15: return launch_one<T, 64, 128, 2, 2, 4, 4>(k, s);
-    case 16: return launch_one<T, 32, 64, 2, 2, 6, 4>(k, s);
-    case 17: return launch_one<T, 32, 128, 2, 2, 4, 4>(k, s);
-    case 18: return launch_one<T, 64, 64, 2, 2, 8, 4>(k, s);
+    case 0: return launch_one<T, 256, 128, 2, 2, 3, 4>(a, k, s);
+    case 1: return launch_one<T, 256, 128, 4, 1, 3, 4>(a, k, s);
+    case 2: return launch_one<T, 128, 128, 2, 2, 3, 4>(a, k, s);
+    case 3: return launch_one<T, 128, 128, 2, 2, 4, 4>(a, k, s);
+    case 4: return launch_one<T, 256, 64, 4, 1, 3, 4>(a, k, s);
+    case 5: return launch_one<T, 128, 192, 2, 2, 3, 4>(a, k, s);
+    case 6: return launch_one<T, 128, 256, 2, 2, 3, 4>(a, k, s);
+    case 7: return launch_one<T, 128, 64, 2, 2, 4, 4>(a, k, s);
+    case 8: return launch_one<T, 256, 128, 2, 2, 3, 2>(a, k, s);
+    case 9: return launch_one<T, 128, 128, 2, 2, 4, 2>(a, k, s);
+    case 10: return launch_one<T, 128, 192, 2, 2, 3, 2>(a, k, s);
+    case 11: return launch_one<T, 192, 128, 2, 2, 3, 4>(a, k, s);
+    case 12: return launch_one<T, 160, 256, 2, 2, 3, 4>(a, k, s);
+    case 13: return launch_one<T, 160, 192, 2, 2, 3, 4>(a, k, s);
+    case 14: return launch_one<T, 64, 64, 2, 2, 4, 4>(a, k, s);
+    case 15: return launch_one<T, 64, 128, 2, 2, 4, 4>(a, k, s);
+    case 16: return launch_one<T, 32, 64, 2, 2, 6, 4>(a, k, s);
+    case 17: return launch_one<T, 32, 128, 2, 2, 4, 4>(a, k, s);
+    case 18: return launch_one<T, 64, 64, 2, 2, 8, 4>(a, k, s);
   }
   return hipErrorInvalidValue;
 }
 
 // Instrumented launch (tools/stamp_ws.py): VNF_WS_STAMP=<file> dumps per-K-tile s_memtime stamps of workgroup 600
 // of every bf16 {128,192,2,2,3,4} launch with more than 600 workgroups.
+#ifdef VNF_STAMPS
 static hipError_t launch_stamped(const KArgs& k, hipStream_t s) {
-  static long long* dbuf = nullptr;
-  const int n = 8 * 64 * 4;
-  if (!dbuf && hipMalloc((void**)&dbuf, n * 8) != hipSuccess) return hipErrorOutOfMemory;
-  (void)hipMemsetAsync(dbuf, 0, n * 8, s);
   KArgs kk = k;
-  kk.dbg = dbuf;
   const int lds = 3 * (128 + 192) * 128 + k.nkt * 8 * 16;
   const int tiles_m = (k.M + 127) / 128;
   kk.tiles_n = (k.Cout + 191) / 192;
   kk.nblk = tiles_m * kk.tiles_n;
-  (void)hipFuncSetAttribute((const void*)conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL((conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  static long long host[8 * 64 * 4];
-  (void)hipMemcpy(host, dbuf, n * 8, hipMemcpyDeviceToHost);
-  if (FILE* f = fopen(getenv("VNF_WS_STAMP"), "a")) {
-    fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
-    for (int w = 0; w < 8; ++w)
-      for (int kt = 0; kt < k.nkt && kt < 64; ++kt)
-        fprintf(f, "%d %d %lld %lld %lld %lld\n", w, kt, host[(w * 64 + kt) * 4], host[(w * 64 + kt) * 4 + 1],
-                host[(w * 64 + kt) * 4 + 2], host[(w * 64 + kt) * 4 + 3]);
-    fclose(f);
-  }
-  return hipSuccess;
+  return stamped_launch(
+      "VNF_WS_STAMP", 8 * 64 * 4, s,
+      [&](long long* dbuf) {
+        kk.dbg = dbuf;
+        allow_dynamic_lds<conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>>(160 * 1024);
+        hipLaunchKernelGGL((conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
+      },
+      [&](FILE* f, const long long* host) {
+        fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
+        for (int w = 0; w < 8; ++w)
+          for (int kt = 0; kt < k.nkt && kt < 64; ++kt)
+            fprintf(f, "%d %d %lld %lld %lld %lld\n", w, kt, host[(w * 64 + kt) * 4], host[(w * 64 + kt) * 4 + 1],
+                    host[(w * 64 + kt) * 4 + 2], host[(w * 64 + kt) * 4 + 3]);
+      });
 }
+#endif
 
 hipError_t launch_ws(const ConvArgs& a, const KArgs& k, int wcfg, hipStream_t s) {
   if (!ws_cfg_ok(a, wcfg) || !k.zero) return hipErrorInvalidValue;
+#ifdef VNF_STAMPS
   if (getenv("VNF_WS_STAMP") && wcfg == 5 && a.dtype == BF16 && (k.M + 127) / 128 * ((k.Cout + 191) / 192) > 600)
     return launch_stamped(k, s);
+#endif
   switch (a.dtype) {
-    case BF16: return launch_ws_typed<__bf16>(wcfg, k, s);
-    case F16: return launch_ws_typed<_Float16>(wcfg, k, s);
-    case F32: return launch_ws_typed<float>(wcfg, k, s);
-    case F16X2: return launch_ws_typed<sf16>(wcfg, k, s);
-    case F16P: return launch_ws_typed<pf16>(wcfg, k, s);
+    case BF16: return launch_ws_typed<__bf16>(wcfg, a, k, s);
+    case F16: return launch_ws_typed<_Float16>(wcfg, a, k, s);
+    case F32: return launch_ws_typed<float>(wcfg, a, k, s);
+    case F16X2: return launch_ws_typed<sf16>(wcfg, a, k, s);
+    case F16P: return launch_ws_typed<pf16>(wcfg, a, k, s);
   }
   return hipErrorInvalidValue;
 }

@@ -136,6 +136,7 @@ ConvArgs Encoder::conv_args(const ConvLayer& L, int n0, int nn) const {
   }
   a.act = L.act; a.slope = L.slope; a.out_f32 = L.out_f32;
   a.cfg = L.cfg;
+  a.ws_persist = env.ws_persist;
   return a;
 }
 
@@ -143,13 +144,12 @@ ConvArgs Encoder::conv_args(const ConvLayer& L, int n0, int nn) const {
 // batch size it will see (measure, don't guess: the best tile depends on M, N, K, the number of
 // workgroups and where the operands sit in the cache hierarchy).  ~1 s at create time.
 int Encoder::autotune() {
-  const TuneEnv& te = tune_env;   // the switches as they were when the handle was created (finalize)
-  const int enabled = te.enabled, force = te.force;
+  const int enabled = env.autotune, force = env.force_cfg;   // the switches as they were when the handle was created
   if (!enabled && force < -1) return VNF_OK;
   // VNF_TUNE_CACHE=<file>: reuse the choices of an earlier create on this device (lines "key cfg"); lets a
   // profiled run show steady-state launches only and brings create time down to the weight upload
   std::map<std::string, int> cache;
-  const char* cache_path = te.cache.empty() ? nullptr : te.cache.c_str();
+  const char* cache_path = env.tune_cache.empty() ? nullptr : env.tune_cache.c_str();
   bool cache_dirty = false;
   if (cache_path && enabled) {
     if (FILE* f = fopen(cache_path, "r")) {
@@ -184,7 +184,7 @@ int Encoder::autotune() {
   // tune_lanes > 1: every candidate is timed as `tune_lanes` concurrent copies on separate streams -- the state the
   // layer actually runs in when independent batches overlap (activation contexts): alone on the GPU a small tile with
   // many workgroups looks best, beside other kernels the tile that moves fewer bytes per FLOP does
-  const int lanes = te.lanes > 0 ? (te.lanes > 4 ? 4 : te.lanes) : (tune_lanes < 1 ? 1 : tune_lanes);
+  const int lanes = env.tune_lanes > 0 ? (env.tune_lanes > 4 ? 4 : env.tune_lanes) : (tune_lanes < 1 ? 1 : tune_lanes);
   if (lanes > 1)
     for (int l = 0; l < lanes; ++l) {
       VNF_HIP(hipStreamCreateWithFlags(&lane_s[l], hipStreamNonBlocking));
@@ -241,7 +241,7 @@ int Encoder::autotune() {
         *out_ms = ms;
         return VNF_OK;
       };
-      const int logit = te.log;
+      const int logit = env.autotune_log;
       for (int cfg = -1; enabled && cfg < conv_num_cfgs(); ++cfg) {
         ConvArgs a = conv_args(L, 0, nn);
         a.cfg = cfg;
@@ -256,7 +256,7 @@ int Encoder::autotune() {
       }
       // finalists: the first pass is 8 launches per candidate and two candidates a few per cent apart change places from
       // run to run; the ones within 8 % of the best are timed again, longer (VNF_TUNE_FINAL=0: first pass only)
-      if (te.finals && timed.size() > 1) {
+      if (env.tune_final && timed.size() > 1) {
         std::sort(timed.begin(), timed.end());
         float fbest = 1e30f;
         int fcfg = best_cfg, nfin = 0;
@@ -309,18 +309,27 @@ int Encoder::finalize() {
     if (rc != VNF_OK) return rc;
   }
   tune_dirty = true;  // the first run() picks the tiles (after any set_streams / set_contexts of the caller)
-  {
-    // the autotuner's switches, read now (at create time) although the tuning itself runs later, from run()
-    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-    tune_env.enabled = env_int("VNF_AUTOTUNE", 1);
-    tune_env.force = env_int("VNF_FORCE_CFG", -2);
-    tune_env.lanes = env_int("VNF_TUNE_LANES", 0);
-    tune_env.log = env_int("VNF_AUTOTUNE_LOG", 0);
-    tune_env.finals = env_int("VNF_TUNE_FINAL", 1) != 0;
-    const char* cache = getenv("VNF_TUNE_CACHE");
-    tune_env.cache = cache ? cache : "";
-  }
   return VNF_OK;
+}
+
+EncoderEnv EncoderEnv::read() {
+  auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+  EncoderEnv e;
+  e.fuse = env_int("VNF_FUSE", e.fuse);
+  e.direct_stem = env_int("VNF_DIRECT_STEM", e.direct_stem);
+  e.stem1a_mfma = env_int("VNF_STEM1A_MFMA", e.stem1a_mfma);
+  e.stem_chunk = env_int("VNF_STEM_CHUNK", e.stem_chunk);
+  e.ir100_chunk1 = env_int("VNF_IR100_CHUNK1", e.ir100_chunk1);
+  e.ir100_chunk2 = env_int("VNF_IR100_CHUNK2", e.ir100_chunk2);
+  e.retina_fuse = env_int("VNF_RETINA_FUSE", e.retina_fuse);
+  e.ws_persist = env_int("VNF_WS_PERSIST", e.ws_persist);
+  e.autotune = env_int("VNF_AUTOTUNE", e.autotune);
+  e.force_cfg = env_int("VNF_FORCE_CFG", e.force_cfg);
+  e.tune_lanes = env_int("VNF_TUNE_LANES", e.tune_lanes);
+  e.autotune_log = env_int("VNF_AUTOTUNE_LOG", e.autotune_log);
+  e.tune_final = env_int("VNF_TUNE_FINAL", 1) != 0;
+  if (const char* cache = getenv("VNF_TUNE_CACHE")) e.tune_cache = cache;
+  return e;
 }
 
 // Fused stacks: the per-wave weight streams are gathered on the device from the packed per-convolution weights the
@@ -328,8 +337,8 @@ int Encoder::finalize() {
 int Encoder::prepare_fused() {
   // bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4: the five
   // Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
-  // mixed_6a.branch1.0 inside that launch; read at create time
-  const int enabled = getenv("VNF_FUSE") ? atoi(getenv("VNF_FUSE")) : 31;
+  // mixed_6a.branch1.0 inside that launch
+  const int enabled = env.fuse;
   for (FusedStack& f : fused) {
     f.active = false;
     if (!enabled || (dtype != BF16 && dtype != F16 && dtype != F16P) || f.nblocks < 1 || f.nblocks > T17_MAX_BLOCKS) continue;
@@ -690,7 +699,7 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   {
     // the first convolution runs as a direct kernel on the caller's NCHW tensor (aux_kernels.hip): the layer stays
     // in `convs` for the FLOP accounting, the PACK + CONV pair of ops becomes one STEM1 op
-    const int direct = getenv("VNF_DIRECT_STEM") ? atoi(getenv("VNF_DIRECT_STEM")) : 1;
+    const int direct = e.env.direct_stem;
     Piece pc;
     if (direct && basic_piece(wm, "conv2d_1a", 3, 32, 3, 3, pc)) {
       std::vector<float> wt(27 * 32 + 32);
@@ -827,9 +836,9 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   // unfused, the stem runs in sub-batches of 128 images so its big producer -> consumer tensors stay inside the
   // Infinity Cache; with conv2d_2a/2b/maxpool fused (one workgroup per image, no big intermediate) a sub-batch would
   // only leave half the CUs without a workgroup
-  const int fuse_mask = getenv("VNF_FUSE") ? atoi(getenv("VNF_FUSE")) : 31;
+  const int fuse_mask = e.env.fuse;
   int chunk = ((fuse_mask & 4) && (e.dtype == BF16 || e.dtype == F16 || (e.dtype == F16P && (fuse_mask & 8)))) ? 256 : 128;
-  if (const char* c = getenv("VNF_STEM_CHUNK")) chunk = atoi(c) > 0 ? atoi(c) : chunk;
+  if (e.env.stem_chunk > 0) chunk = e.env.stem_chunk;
   e.groups.push_back({0, stem_end, chunk});
   e.groups.push_back({stem_end, (int)e.ops.size(), 1 << 30});
   return VNF_OK;
@@ -965,8 +974,8 @@ int build_ir100(Encoder& e, WeightMap& wm) {
   }
   { Op op; op.kind = Op::COPYOUT; e.ops.push_back(op); }
   int c1 = 32, c2 = 64;
-  if (const char* c = getenv("VNF_IR100_CHUNK1")) c1 = atoi(c) > 0 ? atoi(c) : c1;
-  if (const char* c = getenv("VNF_IR100_CHUNK2")) c2 = atoi(c) > 0 ? atoi(c) : c2;
+  if (e.env.ir100_chunk1 > 0) c1 = e.env.ir100_chunk1;
+  if (e.env.ir100_chunk2 > 0) c2 = e.env.ir100_chunk2;
   e.groups.push_back({0, stage_end[0], c1});
   e.groups.push_back({stage_end[0], stage_end[1], c2});
   e.groups.push_back({stage_end[1], (int)e.ops.size(), 1 << 30});
@@ -1099,7 +1108,7 @@ int build_retina_mnet(Encoder& e, WeightMap& wm, int H, int W, int head_bufs[3])
   // VNF_RETINA_FUSE=0: the early layers as plan convolutions on an NHWC4 fp32 copy of the frames (buffer 0, written by
   // the caller); default: conv0 straight from the u8 frames (Op::RSTEM) and dw+pw blocks in one kernel (Op::DWPW)
   // (bit 0: stem, bit 1: dw+pw blocks)
-  const int fuse_env = getenv("VNF_RETINA_FUSE") ? atoi(getenv("VNF_RETINA_FUSE")) : 3;
+  const int fuse_env = e.env.retina_fuse;
   const bool fused = fuse_env & 1, fused_dw = fuse_env & 2;
   int cur = e.add_buf(fused ? 1 : H, fused ? 1 : W, 4);   // input: NHWC4 (R-104, G-117, B-123, 0); a stub when fused
   int h = H, w = W;
@@ -1480,7 +1489,7 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
             const Buf& ob = bufs[op.b];
             const char* src = (const char*)x + (size_t)n0 * 3 * in_size * in_size * xes;
             VNF_HIP(launch_stem_conv1a(src, x_dtype, ob.ptr + (size_t)n0 * ob.elems_per_image() * es, ob.C, dtype, nn,
-                                       stem_wt, s));
+                                       stem_wt, env.stem1a_mfma != 0, s));
             break;
           }
           case Op::MAXPOOL: {

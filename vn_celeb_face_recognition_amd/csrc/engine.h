@@ -112,6 +112,17 @@ struct FusedStack {
 
 struct Tap { int buf, coff, C; };
 
+// Every switch an encoder takes from the environment (VNF_<FIELD NAME>; INTEGRATION.md has the table), read once, when
+// the Encoder is constructed.  Plans, fused stacks, the autotuner and the launchers take their values from here.
+struct EncoderEnv {
+  int fuse = 31, direct_stem = 1, stem1a_mfma = 1, retina_fuse = 3, ws_persist = 1;
+  int stem_chunk = 0, ir100_chunk1 = 0, ir100_chunk2 = 0;   // sub-batch of the leading op groups (<= 0: the plan's default)
+  int autotune = 1, force_cfg = -2, tune_lanes = 0, autotune_log = 0;
+  bool tune_final = true;   // 0: no finalists pass
+  std::string tune_cache;   // file; empty: none
+  static EncoderEnv read();
+};
+
 struct Encoder : HandleBase {
   ~Encoder() override;  // side streams, fork/join and context events (device buffers: HandleBase)
   int arch, dtype, max_batch, in_size;
@@ -148,9 +159,7 @@ struct Encoder : HandleBase {
   bool tune_dirty = true;  // tiles are (re)picked lazily at the next run(): create, set_streams and set_contexts only mark
   int tune_lanes = 1;   // concurrent copies the autotuner times each candidate as (set with the context count)
   int tune_batch = 0;   // batch size the autotuner times at (0: the part size run() uses at max_batch)
-  // the autotuner's switches, read from the environment by finalize() (at create time): VNF_AUTOTUNE, VNF_FORCE_CFG,
-  // VNF_TUNE_LANES, VNF_AUTOTUNE_LOG, VNF_TUNE_FINAL (0: no finalists pass), VNF_TUNE_CACHE (file; empty: none)
-  struct TuneEnv { int enabled = 1, force = -2, lanes = 0, log = 0; bool finals = true; std::string cache; } tune_env;
+  const EncoderEnv env = EncoderEnv::read();
   hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr}, fork_ev = nullptr;
 };

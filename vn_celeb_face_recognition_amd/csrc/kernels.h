@@ -45,6 +45,7 @@ struct ConvArgs {
   const float* slope;   // PReLU slopes [Cout_pad]
   int out_f32;          // store fp32 instead of dtype
   int cfg;              // tile configuration id (conv_cfg_ok), -1 = heuristic
+  int ws_persist;       // wave-specialised kernel: the persistent form where the layer allows it (VNF_WS_PERSIST; host side only)
 };
 
 hipError_t launch_conv(const ConvArgs& a, hipStream_t s);
@@ -55,8 +56,10 @@ bool conv_cfg_ok(const ConvArgs& a, int cfg);  // is tile configuration `cfg` us
 hipError_t launch_pack_input(const void* x, int x_dtype, void* out, int dtype, int n, int hw, hipStream_t s);
 
 // IRv1 stem: NCHW (n,3,160,160) of x_dtype -> conv2d_1a (3x3 s2, folded BN, ReLU) NHWC (n,79,79,32) of dtype;
-// wt = fp32 [27][32] folded weights (k = (c*3+kh)*3+kw) followed by 32 biases
-hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, hipStream_t s);
+// wt = fp32 [27][32] folded weights (k = (c*3+kh)*3+kw) followed by 32 biases; mfma: the 16-bit / planar outputs on the
+// f32 MFMA (VNF_STEM1A_MFMA, default) instead of the VALU kernel, bitwise the same result
+hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, bool mfma,
+                              hipStream_t s);
 
 // 3x3 stride-2 max pool, floor mode, NHWC slice -> NHWC slice
 hipError_t launch_maxpool3s2(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C,

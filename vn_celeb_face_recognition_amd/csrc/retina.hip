@@ -164,6 +164,7 @@ __global__ void __launch_bounds__(256) retina_select_kernel(RetinaGeom g, const 
 struct Retina : HandleBase {
   vnf_retina_cfg cfg;
   Encoder* enc = nullptr;
+  bool layers = false;   // VNF_RETINA_LAYERS (diagnostic): per-layer table of the plan on stderr
   RetinaGeom geom;
   int head_bufs[3];
   RCand* cand = nullptr;
@@ -205,6 +206,7 @@ extern "C" int vnf_retina_create(const vnf_tensor_desc* weights, int n_weights, 
     Retina* r = new Retina();
     r->kind = 5;
     r->cfg = *cfg;
+    r->layers = getenv("VNF_RETINA_LAYERS") != nullptr;
     (void)hipGetDevice(&r->device);
     WeightMap wm(weights, n_weights);
     r->enc = new Encoder();
@@ -268,9 +270,8 @@ extern "C" int vnf_retina_detect(vnf_handle h, const uint8_t* frames, int b, int
                          (float*)e.bufs[0].ptr, npix, e.dtype == F16X2 ? 1 : 0);
       VNF_HIP(hipGetLastError());
     }
-    static const bool layers = getenv("VNF_RETINA_LAYERS") != nullptr;   // diagnostic: per-layer table on stderr
     std::string rep;
-    int rc = e.run(stem_in_plan ? frames : nullptr, b, VNF_F32, nullptr, s, layers ? &rep : nullptr);
+    int rc = e.run(stem_in_plan ? frames : nullptr, b, VNF_F32, nullptr, s, r->layers ? &rep : nullptr);
     if (rc != VNF_OK) return rc;
     if (!rep.empty()) fprintf(stderr, "%s", rep.c_str());
     VNF_HIP(hipMemsetAsync(r->cnt, 0, (2 * (size_t)r->cfg.max_batch + 8) * 4, s));

@@ -27,11 +27,10 @@
 //              issue the DMA
 // Rounding points and summation order are those of the unfused plan (16-bit rows after each conv, fp32 accumulate over
 // (kh,kw,c) in order, bias added after the sum), so the result is bit-identical to it.
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv_device.h"
+#include "stamp.h"
 #include "stem_mid.h"
 
 namespace vnf {
@@ -419,44 +418,29 @@ hipError_t stem_mid_repack(const StemMidPack& p, void* out, hipStream_t s) {
 
 hipError_t launch_stem_mid(const StemMidArgs& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)stem_mid_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS);
-    (void)hipFuncSetAttribute((const void*)stem_mid_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
-  if (dtype == BF16 && a.n > 100 && getenv("VNF_STEM_STAMP")) {
-    // instrumented launch: appends workgroup 100's per-wave segment sums (see the kernel) to the named file
-    static long long* dbuf = nullptr;
-    if (!dbuf && hipMalloc((void**)&dbuf, 64 * 8) != hipSuccess) return hipErrorOutOfMemory;
-    (void)hipMemsetAsync(dbuf, 0, 64 * 8, s);
-    StemMidArgs aa = a;
-    aa.dbg = dbuf;
-    (void)hipFuncSetAttribute((const void*)stem_mid_kernel<__bf16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS);
-    hipLaunchKernelGGL((stem_mid_kernel<__bf16, true>), dim3(a.n), dim3(512), SM_LDS, s, aa);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    long long host[64];
-    (void)hipMemcpy(host, dbuf, 64 * 8, hipMemcpyDeviceToHost);
-    if (FILE* f = fopen(getenv("VNF_STEM_STAMP"), "a")) {
-      fprintf(f, "launch n=%d 3b=%d\n", a.n, a.w3b != nullptr);
-      for (int w = 0; w < 8; ++w) {
-        fprintf(f, "%d", w);
-        for (int i = 0; i < 8; ++i) fprintf(f, " %lld", host[w * 8 + i]);
-        fprintf(f, "\n");
-      }
-      fclose(f);
-    }
-    return hipSuccess;
-  }
-  if (dtype == BF16)
-    hipLaunchKernelGGL(stem_mid_kernel<__bf16>, dim3(a.n), dim3(512), SM_LDS, s, a);
-  else if (dtype == F16)
-    hipLaunchKernelGGL(stem_mid_kernel<_Float16>, dim3(a.n), dim3(512), SM_LDS, s, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+#ifdef VNF_STAMPS
+  // instrumented launch: appends workgroup 100's per-wave segment sums (see the kernel) to the named file
+  if (dtype == BF16 && a.n > 100 && getenv("VNF_STEM_STAMP"))
+    return stamped_launch(
+        "VNF_STEM_STAMP", 64, s,
+        [&](long long* dbuf) {
+          StemMidArgs aa = a;
+          aa.dbg = dbuf;
+          allow_dynamic_lds<stem_mid_kernel<__bf16, true>>(SM_LDS);
+          hipLaunchKernelGGL((stem_mid_kernel<__bf16, true>), dim3(a.n), dim3(512), SM_LDS, s, aa);
+        },
+        [&](FILE* f, const long long* host) {
+          fprintf(f, "launch n=%d 3b=%d\n", a.n, a.w3b != nullptr);
+          for (int w = 0; w < 8; ++w) {
+            fprintf(f, "%d", w);
+            for (int i = 0; i < 8; ++i) fprintf(f, " %lld", host[w * 8 + i]);
+            fprintf(f, "\n");
+          }
+        });
+#endif
+  if (dtype == BF16) return launch_with_lds<stem_mid_kernel<__bf16>>(a.n, 512, SM_LDS, s, a);
+  if (dtype == F16) return launch_with_lds<stem_mid_kernel<_Float16>>(a.n, 512, SM_LDS, s, a);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf

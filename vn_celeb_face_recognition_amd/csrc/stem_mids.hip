@@ -346,12 +346,7 @@ hipError_t stem_mids_repack(const StemMidPack& p, void* out, hipStream_t s) {
 hipError_t launch_stem_mids(const StemMidArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (!a.w3b || !a.b3b) return hipErrorInvalidValue;   // the split kernel always carries conv2d_3b
-  static const hipError_t attr = hipFuncSetAttribute((const void*)stem_mid_split_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, SMS_LDS);
-  (void)attr;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(stem_mid_split_kernel, dim3(a.n), dim3(512), SMS_LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds<stem_mid_split_kernel>(a.n, 512, SMS_LDS, s, a);
 }
 
 }  // namespace vnf

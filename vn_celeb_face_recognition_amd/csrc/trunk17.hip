@@ -304,20 +304,9 @@ hipError_t trunk17_repack(const Trunk17Pack& p, void* out, hipStream_t s) {
 
 hipError_t launch_trunk17(const Trunk17Args& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)block17_trunk_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, T17_LDS);
-    (void)hipFuncSetAttribute((const void*)block17_trunk_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, T17_LDS);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
-  if (dtype == BF16)
-    hipLaunchKernelGGL(block17_trunk_kernel<__bf16>, dim3(a.n), dim3(512), T17_LDS, s, a);
-  else if (dtype == F16)
-    hipLaunchKernelGGL(block17_trunk_kernel<_Float16>, dim3(a.n), dim3(512), T17_LDS, s, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  if (dtype == BF16) return launch_with_lds<block17_trunk_kernel<__bf16>>(a.n, 512, T17_LDS, s, a);
+  if (dtype == F16) return launch_with_lds<block17_trunk_kernel<_Float16>>(a.n, 512, T17_LDS, s, a);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf

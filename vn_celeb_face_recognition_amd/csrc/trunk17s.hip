@@ -424,12 +424,7 @@ hipError_t trunk17s_repack(const Trunk17Pack& p, void* out, hipStream_t s) {
 
 hipError_t launch_trunk17s(const Trunk17Args& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)block17_trunk_split_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, S17_LDS);
-  (void)attr;
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(block17_trunk_split_kernel, dim3(a.n), dim3(512), S17_LDS, s, a);
-  return hipGetLastError();
+  return launch_with_lds<block17_trunk_split_kernel>(a.n, 512, S17_LDS, s, a);
 }
 
 }  // namespace vnf

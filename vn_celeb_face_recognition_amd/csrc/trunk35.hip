@@ -26,12 +26,11 @@
 //   [49152, 98304)     W5 (up, 48 fragments), loaded under phases A-D
 //   [98304, 135168)    two 3x3 weight buffers (18 fragments each): W2 | W3 prefetched under phase E, W4 under phase C
 //   [135168, 139264)   the blocks' 448 fp32 biases, double-buffered by block parity
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "block35.h"
 #include "conv_device.h"
+#include "stamp.h"
 
 namespace vnf {
 
@@ -472,30 +471,26 @@ __global__ __launch_bounds__(512, 2) void block35_stack_kernel(const Block35Stac
 // Instrumented launch: VNF_T35_STAMP=<file> appends the stamps of workgroup 100 (bf16, n > 100): per wave
 //   start | x loaded, weights issued | first barrier | per block: A done, barrier, images written, barrier, then for
 //   B, C, D: phase done, barrier; E done, barrier
+#ifdef VNF_STAMPS
 static hipError_t launch_stack_stamped(const Block35StackArgs& a, hipStream_t s) {
-  static long long* dbuf = nullptr;
-  const int n = 8 * 64;
-  if (!dbuf && hipMalloc((void**)&dbuf, n * 8) != hipSuccess) return hipErrorOutOfMemory;
-  (void)hipMemsetAsync(dbuf, 0, n * 8, s);
-  Block35StackArgs aa = a;
-  aa.dbg = dbuf;
-  (void)hipFuncSetAttribute((const void*)block35_stack_kernel<__bf16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T35_LDS);
-  hipLaunchKernelGGL((block35_stack_kernel<__bf16, true>), dim3(a.n), dim3(512), T35_LDS, s, aa);
-  hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  static long long host[8 * 64];
-  (void)hipMemcpy(host, dbuf, n * 8, hipMemcpyDeviceToHost);
-  if (FILE* f = fopen(getenv("VNF_T35_STAMP"), "a")) {
-    fprintf(f, "launch n=%d nblocks=%d\n", a.n, a.nblocks);
-    for (int w = 0; w < 8; ++w) {
-      fprintf(f, "%d", w);
-      for (int i = 0; i < 10; ++i) fprintf(f, " %lld", host[w * 64 + i]);
-      fprintf(f, "\n");
-    }
-    fclose(f);
-  }
-  return hipSuccess;
+  return stamped_launch(
+      "VNF_T35_STAMP", 8 * 64, s,
+      [&](long long* dbuf) {
+        Block35StackArgs aa = a;
+        aa.dbg = dbuf;
+        allow_dynamic_lds<block35_stack_kernel<__bf16, true>>(T35_LDS);
+        hipLaunchKernelGGL((block35_stack_kernel<__bf16, true>), dim3(a.n), dim3(512), T35_LDS, s, aa);
+      },
+      [&](FILE* f, const long long* host) {
+        fprintf(f, "launch n=%d nblocks=%d\n", a.n, a.nblocks);
+        for (int w = 0; w < 8; ++w) {
+          fprintf(f, "%d", w);
+          for (int i = 0; i < 10; ++i) fprintf(f, " %lld", host[w * 64 + i]);
+          fprintf(f, "\n");
+        }
+      });
 }
+#endif
 
 // mixed_6a.branch1.0's packed engine weights [192 rows][kpad] -> 96 MFMA A-fragments (f = ks * 12 + j: rows 16 j .. + 15,
 // k = 32 ks + 8 (lane >> 4) .. + 7) and a last KiB with the 192 fp32 biases
@@ -520,21 +515,12 @@ hipError_t block35_tail_repack(const void* w, int kpad, const float* bias, void*
 
 hipError_t launch_block35_stack(const Block35StackArgs& a, int dtype, hipStream_t s) {
   if (a.n <= 0 || a.nblocks <= 0) return hipSuccess;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)block35_stack_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, T35_LDS);
-    (void)hipFuncSetAttribute((const void*)block35_stack_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, T35_LDS);
-    (void)hipGetLastError();
-    attr_done = true;
-  }
+#ifdef VNF_STAMPS
   if (dtype == BF16 && a.n > 100 && getenv("VNF_T35_STAMP")) return launch_stack_stamped(a, s);
-  if (dtype == BF16)
-    hipLaunchKernelGGL(block35_stack_kernel<__bf16>, dim3(a.n), dim3(512), T35_LDS, s, a);
-  else if (dtype == F16)
-    hipLaunchKernelGGL(block35_stack_kernel<_Float16>, dim3(a.n), dim3(512), T35_LDS, s, a);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+#endif
+  if (dtype == BF16) return launch_with_lds<block35_stack_kernel<__bf16>>(a.n, 512, T35_LDS, s, a);
+  if (dtype == F16) return launch_with_lds<block35_stack_kernel<_Float16>>(a.n, 512, T35_LDS, s, a);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf
