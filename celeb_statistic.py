@@ -9,7 +9,8 @@ re-used, l.393-399) and summarised into the interval JSON (`dynamic_itv` / `fixe
 The recognition itself is the resident MI355X pipeline in throughput mode (FacePipeline.submit: detection and
 embedding streams overlap, faces of consecutive batches embedded together).  Input: a directory of frames or a
 .npy array of (T,H,W,3) RGB frames with -fps (OpenCV / pafy are not installed: no container decode, no YouTube);
---recog_emotion and seq_fd_vs_aln are outside the hot path and refused."""
+--recog_emotion (carried by demo_image.py only: the frame stream's multi-rank exchange does not pass emotions on) and
+seq_fd_vs_aln (outside the hot path) are refused."""
 import os
 import time
 

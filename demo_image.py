@@ -9,9 +9,10 @@ import numpy as np
 
 from vn_celeb_face_recognition_amd import models as model_md
 from vn_celeb_face_recognition_amd.classifier import load_model_classify
-from vn_celeb_face_recognition_amd.cli_utils import draw_boxes_on_image, read_json, read_label2name, read_rgb, write_rgb
+from vn_celeb_face_recognition_amd.cli_utils import (draw_boxes_on_image, draw_emotions, load_etag2idx, read_json,
+                                                     read_label2name, read_rgb, write_rgb)
 from vn_celeb_face_recognition_amd.pipeline import (center_point_dict, parallel_detect_and_align, recognize_celeb,
-                                                    transforms_default)
+                                                    recognize_emotion, trans_emotion_inf, transforms_default)
 
 
 def build_parser(desc):
@@ -41,12 +42,14 @@ def build_parser(desc):
     return p
 
 
-def build_models(args, device):
-    """demo_image.py:359-376 / demo_video.py:257-275."""
+def build_models(args, device, allow_emotion=False):
+    """demo_image.py:359-376 / demo_video.py:257-275.  The emotion model is built separately (build_emotion), by the
+    CLI that carries its results: demo_image.py."""
     if args.device != 'GPU':
         raise SystemExit("this build runs on MI355X only: use -dv GPU (there is no CPU path)")
-    if args.recog_emotion:
-        raise SystemExit("--recog_emotion: the emotion network is outside the hot path (SURVEY.md section 8)")
+    if args.recog_emotion and not allow_emotion:
+        raise SystemExit("--recog_emotion is carried by demo_image.py only: the video stream's multi-rank exchange does "
+                         "not pass emotions on yet")
     label2name_df = read_label2name(args.label2name)
     det_args = read_json(args.detection_args)
     det_args['device'] = device
@@ -59,13 +62,22 @@ def build_models(args, device):
     return label2name_df, detection_md, emb_model, classify_model
 
 
+def build_emotion(args, device):
+    """demo_image.py:378-382: (index -> tag table, emotion model on `device`)."""
+    idx2etag = load_etag2idx(args.etag2idx_file)['idx2key']
+    emt_model = getattr(model_md, args.emotion)(**read_json(args.emotion_args)).to(device)
+    return idx2etag, emt_model
+
+
 if __name__ == '__main__':
     args_parser = build_parser('Face recognition on a image')
     args_parser.add_argument('-i', '--image_path', default='demo.png', type=str)
     args_parser.add_argument('-o', '--output_path', default='demo_recognition.png', type=str)
     args = args_parser.parse_args()
     device = 'cuda:0'
-    label2name_df, detection_md, emb_model, classify_model = build_models(args, device)
+    label2name_df, detection_md, emb_model, classify_model = build_models(args, device, allow_emotion=True)
+    if args.recog_emotion:
+        idx2etag, emt_model = build_emotion(args, device)
     target_fs = (args.target_face_size, args.target_face_size)
     center_point = center_point_dict[str(target_fs)]
     rgb_image = read_rgb(args.image_path)
@@ -80,5 +92,12 @@ if __name__ == '__main__':
     bth_names = recognize_celeb(bth_alg_faces, device, emb_model, classify_model, transforms_default, label2name_df,
                                 args.recog_threshold)
     np_image_recog = draw_boxes_on_image(rgb_image, bth_chosen_boxes[0], bth_names[0])
+    if args.recog_emotion:   # demo_image.py:416-422
+        map_func = np.vectorize(lambda x: idx2etag[x])
+        bth_emotions, bth_probs = recognize_emotion(bth_alg_faces, device, emt_model, trans_emotion_inf, map_func,
+                                                    args.topk_emotions)
+        np_image_recog = draw_emotions(np_image_recog, bth_chosen_boxes[0], bth_emotions[0], bth_probs[0])
+        for name, tags, percents in zip(bth_names[0], bth_emotions[0], bth_probs[0]):
+            print('{}: {}'.format(name, ', '.join('{} - {:.2f}%'.format(t, p * 100) for t, p in zip(tags, percents))))
     write_rgb(args.output_path, np_image_recog)
     print('Face recognized image saved at {} ...'.format(args.output_path))

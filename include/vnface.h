@@ -18,6 +18,11 @@
  *                                    align_face.py:51-57 (crop, move landmarks, Umeyama,
  *                                    cv2.warpAffine) + data_loader/__init__.py:27-34,52-56
  *                                    (transforms_default, fused)
+ *   vnf_emotion_create / vnf_emotion_forward
+ *                                    models/resnet_2_branch.py:12-89 (ResNet2Branch, resnet_2branch_50)
+ *   vnf_emotion_prep                 data_loader/__init__.py:74-81 (trans_emotion_inf)
+ *   vnf_softmax_topk                 demo_image.py:37-47 (find_emotion, after the forward)
+ *   vnf_emotion_recognize            demo_image.py:79-110 (recognize_emotion: transform, forward, top-k)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -58,6 +63,7 @@ extern "C" {
 /* encoder architectures */
 #define VNF_ARCH_IRV1 0   /* InceptionResnetV1, 160x160 input, L2-normalised 512-d output */
 #define VNF_ARCH_IR100 1  /* IResNet-100 (ArcFace), 112x112 input, 512-d BN1d features */
+#define VNF_ARCH_RN50_2B 2 /* ResNet-50 with class + projection heads (emotions), 224x224 input: vnf_emotion_create only */
 
 typedef struct vnf_handle_s* vnf_handle;
 
@@ -108,6 +114,40 @@ int vnf_encoder_set_streams(vnf_handle h, int max_streams);
  * Each call stays ordered on the stream it was given.  Extra sets are allocated at first use (~2 GB for IRv1 at
  * max_batch 256).  Default 1. */
 int vnf_encoder_set_contexts(vnf_handle h, int n);
+
+/* emotion network --------------------------------------------------------------------------- */
+/* models/resnet_2_branch.py:12-89: ResNet-50 (Bottleneck 3-4-6-3) on 224x224 inputs with two linear heads, fc
+ * (2048 -> num_classes) and proj (2048 -> num_projections).  weights: the reference state_dict (conv1, bn1,
+ * layer1..4, fc, proj; a DataParallel "module." prefix is stripped by the caller).  compute_dtype as for the
+ * encoders.  The handle is an encoder handle: vnf_encoder_tap ("stem", "maxpool", "layer1".."layer4", "avgpool"),
+ * vnf_encoder_profile (its emb_out is the (N,num_classes) class head), vnf_encoder_flops and
+ * vnf_encoder_set_streams work on it; vnf_embed and vnf_encoder_set_contexts refuse it. */
+int vnf_emotion_create(const vnf_tensor_desc* weights, int n_weights, int num_classes, int num_projections,
+                       int compute_dtype, int max_batch, vnf_handle* out);
+/* ResNet2Branch.forward (resnet_2_branch.py:55-70).  x: device (N,3,224,224) NCHW, already normalised, dtype
+ * VNF_F32 | VNF_BF16 | VNF_F16.  cls_out: device (N,num_classes) fp32, proj_out: device (N,num_projections) fp32;
+ * either may be NULL.  N > max_batch: VNF_E_CAPACITY; N == 0: no-op. */
+int vnf_emotion_forward(vnf_handle h, const void* x, int n, int x_dtype, float* cls_out, float* proj_out,
+                        void* stream);
+/* recognize_emotion's device part (demo_image.py:79-110): aligned faces -> trans_emotion_inf -> network -> top-k in
+ * one enqueue, nothing returns to the host in between.  faces_u8: device (N,S,S,3) RGB bytes, S <= 224; k in 1..16,
+ * k <= num_classes.  idx_out: device (N,k) int32, prob_out: device (N,k) fp32 (see vnf_softmax_topk); cls_out:
+ * device (N,num_classes) fp32 logits, may be NULL. */
+int vnf_emotion_recognize(vnf_handle h, const uint8_t* faces_u8, int n, int s, int k, int32_t* idx_out,
+                          float* prob_out, float* cls_out, void* stream);
+/* trans_emotion_inf (data_loader/__init__.py:74-81) for square faces: Resize(224) with Pillow's bilinear resampling
+ * (byte-exact: two 8-bit passes, 22-bit fixed-point coefficients), ToTensor, Normalize(ImageNet mean / std).
+ * faces_u8: device (N,S,S,3), S <= 224; x_out: device (N,3,224,224) of out_dtype VNF_F32 | VNF_BF16 | VNF_F16. */
+int vnf_emotion_prep(const uint8_t* faces_u8, int n, int s, void* x_out, int out_dtype, void* stream);
+/* find_emotion after the forward (demo_image.py:41-47): per row of logits (N,C) fp32 the indices of the k largest
+ * in descending order and their softmax values.  Exact ties come out lower index first (numpy's argsort leaves
+ * their order undefined).  k in 1..16; k > C: VNF_E_INVALID.  idx: device (N,k) int32, prob: device (N,k) fp32. */
+int vnf_softmax_topk(const float* logits, int n, int c, int k, int32_t* idx, float* prob, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet_2_branch.py:21) on its own, for staged parity of the
+ * plan's pool: x device NHWC (N,H,W,C) -> y device NHWC (N,(H-1)/2+1,(W-1)/2+1,C) in one of the plans' storage
+ * layouts: dtype VNF_F32 | VNF_BF16 | VNF_F16 (C % 4 / 8 / 8 == 0) or VNF_F16X2 (4-byte (hi, lo) pairs, C % 4 == 0;
+ * planar != 0: 8-channel units [8 hi][8 lo], C % 8 == 0, what the encoders keep).  Padding compares as -inf. */
+int vnf_maxpool3s2p1(const void* x, int dtype, int planar, int n, int h, int w, int c, void* y, void* stream);
 
 /* classifier ------------------------------------------------------------------------------- */
 int vnf_mlp_create(const vnf_tensor_desc* weights, int n_weights, int input_dim, int num_classes,

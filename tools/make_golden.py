@@ -192,6 +192,39 @@ def golden_ir100():
     print("ir100:", y.shape, y.abs().mean().item())
 
 
+def golden_emotion():
+    """ResNet2Branch (the emotion network) on generator weights: two seeded images, both heads and the reference's
+    top-6 (find_emotion's argsort / sort / flip).  The input seed is the first for which, in every row, consecutive
+    logits among the seven largest are >= 1e-3 x max|logit| apart -- ten times the parity gate, so the tests may ask
+    for identical top-6 indices.  Also the reference's index -> tag table as plain JSON."""
+    import pickle
+    m = ref("resnet_2_branch").resnet_2branch_50(num_classes=690, num_projections=300).eval()
+    m.load_state_dict(generate_state_dict("rn50_2b", 0, as_torch=True, num_classes=690, num_projections=300), strict=True)
+    for seed in range(64):
+        x = seeded_normal((2, 3, 224, 224), seed)
+        with torch.no_grad():
+            c, p = m(x)
+        top7 = np.sort(c.numpy(), axis=1)[:, ::-1][:, :7]
+        gaps = (top7[:, :-1] - top7[:, 1:]).min(axis=1)
+        if bool((gaps >= 1e-3 * np.abs(c.numpy()).max(axis=1)).all()):
+            break
+    assert bool((gaps >= 1e-3 * np.abs(c.numpy()).max(axis=1)).all()), "no input seed with separated top-7 logits"
+    out_np = c.numpy()
+    pct = torch.nn.functional.softmax(c, dim=1).numpy()
+    idx = np.flip(np.argsort(out_np, axis=1)[:, -6:], axis=1)
+    prob = np.flip(np.sort(pct, axis=1)[:, -6:], axis=1)
+    np.savez_compressed(os.path.join(OUT, "rn50_2b_seed0.npz"), input_seed=seed, x_cls=out_np, x_proj=p.numpy(),
+                        top6_idx=np.ascontiguousarray(idx).astype(np.int32), top6_prob=np.ascontiguousarray(prob))
+    with open(os.path.join(REF, "meta_data", "emotion_recognition", "etag2idx.pkl.keep"), "rb") as f:
+        tab = pickle.load(f)
+    idx2key = tab["idx2key"]
+    names = [str(idx2key[i]) for i in range(len(idx2key))]
+    assert all(tab["key2idx"][n] == i for i, n in enumerate(names))
+    with open(os.path.join(OUT, "etag2idx.json"), "w") as f:
+        json.dump({"idx2key": names}, f, ensure_ascii=False, indent=0)
+    print("emotion: input seed", seed, "min top-7 gap", gaps.tolist(), "top-6", idx.tolist(), prob[:, :3].tolist(), len(names), "tags")
+
+
 def golden_mtcnn():
     from PIL import Image
     mt = ref("mtcnn")
@@ -479,6 +512,6 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     install_shim()
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["irv1", "mlp", "ir100", "mtcnn", "umeyama", "celeb_stat", "retina", "mlp_train"]
+    which = sys.argv[1:] or ["irv1", "mlp", "ir100", "mtcnn", "umeyama", "celeb_stat", "retina", "mlp_train", "emotion"]
     for w in which:
         globals()["golden_" + w]()

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvnface.so")
 
 VNF_F32, VNF_BF16, VNF_F16, VNF_I64, VNF_U8, VNF_F16X2 = 0, 1, 2, 3, 4, 5
-VNF_ARCH_IRV1, VNF_ARCH_IR100 = 0, 1
+VNF_ARCH_IRV1, VNF_ARCH_IR100, VNF_ARCH_RN50_2B = 0, 1, 2
 
 
 class VnfError(RuntimeError):
@@ -50,6 +50,12 @@ SIGNATURES = {
     "vnf_encoder_flops": (_I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "vnf_encoder_set_streams": (_I, [_P, _I]),
     "vnf_encoder_set_contexts": (_I, [_P, _I]),
+    "vnf_emotion_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "vnf_emotion_forward": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "vnf_emotion_recognize": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "vnf_emotion_prep": (_I, [_P, _I, _I, _P, _I, _P]),
+    "vnf_softmax_topk": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "vnf_maxpool3s2p1": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vnf_mlp_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vnf_classify": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "vnf_mlp_trainer_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float,

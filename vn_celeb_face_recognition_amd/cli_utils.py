@@ -2,6 +2,8 @@
   read_json, append_log_to_file, convert_sec_to_max_time_quantity <- /root/reference/utils/utils.py:34-38,60-64,77-82
   label2name CSV ('label,name' header)                             <- demo_image.py:359, meta_data/face_recognition/label2name.txt
   draw_boxes_on_image                                              <- demo_image.py:150-158 (PIL instead of OpenCV, which is not installed)
+  draw_emotions                                                    <- demo_image.py:161-171 (text only, drawn the same way)
+  load_etag2idx                                                    <- utils/utils.py load_pickle on meta_data/emotion_recognition/etag2idx.pkl.keep
 """
 import csv
 import json
@@ -56,6 +58,53 @@ def draw_boxes_on_image(rgb_image, boxes, list_names):
         d.rectangle([float(box[0]), float(box[1]), float(box[2]), float(box[3])], outline=(0, 255, 0), width=2)
         d.text((float(box[2]), float(box[1])), str(name), fill=(0, 255, 0))
     return np.asarray(im)
+
+
+def draw_emotions(rgb_image, bboxes, emotion_tags, emotion_percent):
+    """'<tag> - <percent>%' lines inside each box, 16 px apart from its top-left corner (demo_image.py:161-171)."""
+    from PIL import Image, ImageDraw
+    im = Image.fromarray(np.asarray(rgb_image, dtype=np.uint8).copy())
+    d = ImageDraw.Draw(im)
+    for idx, box in enumerate(bboxes):
+        for i, (emotion, percent) in enumerate(zip(emotion_tags[idx], emotion_percent[idx])):
+            d.text((int(box[0] + 5), int(box[1]) + i * 16 + 4), '{} - {:.2f}%'.format(emotion, percent * 100), fill=(0, 255, 0))
+    return np.asarray(im)
+
+
+def load_etag2idx(path):
+    """The emotion tag table {'key2idx': {tag: index}, 'idx2key': {index: tag}} (demo_image.py:380).  A .json file of
+    that shape (idx2key as a list or a dict, key2idx optional) or the reference's pickle, which is read by an
+    unpickler that admits builtin containers, str and int only: a pickle that names any global is refused."""
+    import io
+    import pickle
+    if str(path).lower().endswith('.json'):
+        tab = read_json(path)
+    else:
+        class _Restricted(pickle.Unpickler):
+            def find_class(self, module, name):
+                raise pickle.UnpicklingError("etag2idx pickle names the global %s.%s: only builtin containers, str and "
+                                             "int are admitted" % (module, name))
+        with open(path, 'rb') as f:
+            tab = _Restricted(io.BytesIO(f.read())).load()
+
+    def plain(x):
+        return isinstance(x, (str, int)) and not isinstance(x, bool)
+    if not isinstance(tab, dict) or 'idx2key' not in tab:
+        raise ValueError("%s: expected a dict with 'idx2key'" % (path,))
+    i2k = tab['idx2key']
+    if isinstance(i2k, (list, tuple)):
+        i2k = dict(enumerate(i2k))
+    if not isinstance(i2k, dict) or not all(plain(k) and plain(v) for k, v in i2k.items()):
+        raise ValueError("%s: idx2key must map int -> str" % (path,))
+    idx2key = {int(k): str(v) for k, v in i2k.items()}
+    k2i = tab.get('key2idx')
+    if k2i is None:
+        key2idx = {v: k for k, v in idx2key.items()}
+    else:
+        if not isinstance(k2i, dict) or not all(plain(k) and plain(v) for k, v in k2i.items()):
+            raise ValueError("%s: key2idx must map str -> int" % (path,))
+        key2idx = {str(k): int(v) for k, v in k2i.items()}
+    return {'key2idx': key2idx, 'idx2key': idx2key}
 
 
 def export_video_face_recognition(output_frame_dir, fps, output_path):

@@ -81,6 +81,7 @@ int vnf_embed(vnf_handle h, const void* x, int n, int x_dtype, float* emb_out, v
   API_GUARD_BEGIN
   Encoder* e = as_encoder(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
+  if (e->arch == VNF_ARCH_RN50_2B) return fail(VNF_E_INVALID, "emotion handle: use vnf_emotion_forward");
   if (n < 0 || (n > 0 && (!x || !emb_out))) return fail(VNF_E_INVALID, "bad argument");
   if (x_dtype != VNF_F32 && x_dtype != VNF_BF16 && x_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad x_dtype");
   return e->run(x, n, x_dtype, emb_out, (hipStream_t)stream);
@@ -154,12 +155,120 @@ int vnf_encoder_set_contexts(vnf_handle h, int n) {
   Encoder* e = as_encoder(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
   if (n < 1 || n > 4) return fail(VNF_E_INVALID, "vnf_encoder_set_contexts: 1..4");
+  if (e->arch == VNF_ARCH_RN50_2B && n != 1) return fail(VNF_E_INVALID, "vnf_encoder_set_contexts: not for the emotion network");
   e->n_ctx = n;
   e->next_ctx = 0;
   if (e->tune_lanes != n) {
     e->tune_lanes = n;
     e->tune_dirty = true;  // the next vnf_embed picks the tiles for `n` kernels sharing the GPU
   }
+  return VNF_OK;
+  API_GUARD_END
+}
+
+// ---- emotion network (ResNet-50, two heads): an Encoder of arch VNF_ARCH_RN50_2B
+int vnf_emotion_create(const vnf_tensor_desc* weights, int n_weights, int num_classes, int num_projections, int compute_dtype,
+                       int max_batch, vnf_handle* out) {
+  API_GUARD_BEGIN
+  if (!out || !weights || n_weights <= 0 || max_batch <= 0 || num_classes < 1 || num_projections < 1 || num_classes > 65536 ||
+      num_projections > 65536)
+    return fail(VNF_E_INVALID, "bad argument");
+  if (compute_dtype != VNF_F32 && compute_dtype != VNF_BF16 && compute_dtype != VNF_F16 && compute_dtype != VNF_F16X2)
+    return fail(VNF_E_INVALID, "compute_dtype must be VNF_F32, VNF_BF16, VNF_F16 or VNF_F16X2");
+  *out = nullptr;
+  Encoder* e = new Encoder();
+  e->kind = 1;
+  e->arch = VNF_ARCH_RN50_2B;
+  e->dtype = compute_dtype == VNF_F16X2 ? F16P : compute_dtype;
+  e->max_batch = max_batch;
+  (void)hipGetDevice(&e->device);
+  WeightMap wm(weights, n_weights);
+  int r = build_rn50_2b(*e, wm, num_classes, num_projections);
+  if (r == VNF_OK) r = e->finalize();
+  if (r == VNF_OK) {
+    e->cls_buf = (float*)e->dalloc((size_t)max_batch * num_classes * 4);
+    if (!e->cls_buf) r = VNF_E_HIP;
+  }
+  if (r != VNF_OK) {
+    delete e;
+    return r;
+  }
+  VNF_HIP(hipDeviceSynchronize());
+  *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(e));
+  return VNF_OK;
+  API_GUARD_END
+}
+
+static Encoder* as_emotion(vnf_handle h) {
+  Encoder* e = as_encoder(h);
+  return (e && e->arch == VNF_ARCH_RN50_2B) ? e : nullptr;
+}
+
+int vnf_emotion_forward(vnf_handle h, const void* x, int n, int x_dtype, float* cls_out, float* proj_out, void* stream) {
+  API_GUARD_BEGIN
+  Encoder* e = as_emotion(h);
+  if (!e) return fail(VNF_E_INVALID, "not an emotion handle");
+  if (n < 0 || (n > 0 && !x)) return fail(VNF_E_INVALID, "bad argument");
+  if (x_dtype != VNF_F32 && x_dtype != VNF_BF16 && x_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad x_dtype");
+  RunExtra ex;
+  ex.out2 = proj_out;
+  return e->run(x, n, x_dtype, cls_out, (hipStream_t)stream, nullptr, &ex);
+  API_GUARD_END
+}
+
+int vnf_emotion_recognize(vnf_handle h, const uint8_t* faces_u8, int n, int s, int k, int32_t* idx_out, float* prob_out,
+                          float* cls_out, void* stream) {
+  API_GUARD_BEGIN
+  Encoder* e = as_emotion(h);
+  if (!e) return fail(VNF_E_INVALID, "not an emotion handle");
+  if (n < 0 || (n > 0 && (!faces_u8 || !idx_out || !prob_out))) return fail(VNF_E_INVALID, "bad argument");
+  if (s < 1 || s > 224) return fail(VNF_E_INVALID, "face size must be 1..224");
+  if (k < 1 || k > 16 || k > e->n_cls) return fail(VNF_E_INVALID, "k must be 1..16 and <= num_classes");
+  if (n > e->max_batch) return fail(VNF_E_CAPACITY, "batch exceeds max_batch");
+  if (n == 0) return VNF_OK;
+  float* cls = cls_out ? cls_out : e->cls_buf;
+  RunExtra ex;
+  ex.prep_src = faces_u8;
+  ex.prep_s = s;
+  const int r = e->run(nullptr, n, VNF_F32, cls, (hipStream_t)stream, nullptr, &ex);
+  if (r != VNF_OK) return r;
+  VNF_HIP(launch_softmax_topk(cls, n, e->n_cls, k, idx_out, prob_out, (hipStream_t)stream));
+  return VNF_OK;
+  API_GUARD_END
+}
+
+int vnf_emotion_prep(const uint8_t* faces_u8, int n, int s, void* x_out, int out_dtype, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0 || (n > 0 && (!faces_u8 || !x_out))) return fail(VNF_E_INVALID, "bad argument");
+  if (s < 1 || s > 224) return fail(VNF_E_INVALID, "face size must be 1..224");
+  if (out_dtype != VNF_F32 && out_dtype != VNF_BF16 && out_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad out_dtype");
+  for (int n0 = 0; n0 < n; n0 += 32768) {
+    const int nn = n - n0 < 32768 ? n - n0 : 32768;
+    VNF_HIP(launch_emotion_prep(faces_u8 + (size_t)n0 * s * s * 3, nn, s,
+                                (char*)x_out + (size_t)n0 * 3 * 224 * 224 * dtype_size(out_dtype), out_dtype, false,
+                                (hipStream_t)stream));
+  }
+  return VNF_OK;
+  API_GUARD_END
+}
+
+int vnf_softmax_topk(const float* logits, int n, int c, int k, int32_t* idx, float* prob, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0 || c < 1 || (n > 0 && (!logits || !idx || !prob))) return fail(VNF_E_INVALID, "bad argument");
+  if (k < 1 || k > 16 || k > c) return fail(VNF_E_INVALID, "k must be 1..16 and <= c");
+  VNF_HIP(launch_softmax_topk(logits, n, c, k, idx, prob, (hipStream_t)stream));
+  return VNF_OK;
+  API_GUARD_END
+}
+
+int vnf_maxpool3s2p1(const void* x, int dtype, int planar, int n, int h, int w, int c, void* y, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0 || h < 1 || w < 1 || c < 1 || (n > 0 && (!x || !y))) return fail(VNF_E_INVALID, "bad argument");
+  if (dtype != VNF_F32 && dtype != VNF_BF16 && dtype != VNF_F16 && dtype != VNF_F16X2) return fail(VNF_E_INVALID, "bad dtype");
+  const int dt = dtype == VNF_F16X2 ? (planar ? F16P : F16X2) : dtype;
+  if (c % dtype_chan_align(dt)) return fail(VNF_E_INVALID, "channel count is not a multiple of the layout's 16-byte unit");
+  if ((size_t)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * (size_t)c >= ((size_t)1 << 31)) return fail(VNF_E_CAPACITY, "tensor too large");
+  VNF_HIP(launch_maxpool3s2p1(x, c, y, c, dt, n, h, w, c, (hipStream_t)stream));
   return VNF_OK;
   API_GUARD_END
 }

@@ -121,8 +121,8 @@ ConvArgs Encoder::conv_args(const ConvLayer& L, int n0, int nn) const {
   for (int i = 0; i < L.nseg; ++i) {
     a.seg[i].c0 = L.seg[i].c0; a.seg[i].c1 = L.seg[i].c1;
     if (L.seg[i].buf == -2) {
-      a.seg[i].ptr = emb_raw + (size_t)n0 * 512;
-      a.seg[i].ld = 512;
+      a.seg[i].ptr = emb_raw + (size_t)n0 * emb_ld;
+      a.seg[i].ld = emb_ld;
     } else {
       const Buf& ob = bufs[L.seg[i].buf];
       a.seg[i].ptr = ob.ptr + ((size_t)n0 * ob.elems_per_image() + L.seg[i].coff) * (L.out_f32 ? 4 : es);
@@ -299,7 +299,7 @@ int Encoder::finalize() {
     if (!b.ptr) return VNF_E_HIP;
     VNF_HIP(hipMemset(b.ptr, 0, bytes));
   }
-  emb_raw = (float*)dalloc((size_t)max_batch * 512 * 4);
+  emb_raw = (float*)dalloc((size_t)max_batch * emb_ld * 4);
   if (!emb_raw) return VNF_E_HIP;
   macs_alg = macs_exec = 0;
   for (auto& c : convs) { macs_alg += c.macs_alg; macs_exec += c.macs_exec; }
@@ -982,6 +982,101 @@ int build_ir100(Encoder& e, WeightMap& wm) {
   return VNF_OK;
 }
 
+// ResNet-50 with two linear heads (models/resnet_2_branch.py:12-70; Bottleneck: resnet_2_branch_utils/resnet.py:68-104),
+// the emotion network.  Every BatchNorm (eps 1e-5) follows its convolution, so all of them fold into scale and bias;
+// per Bottleneck three launches (1x1 -> ReLU, 3x3 carrying the stride -> ReLU, 1x1 + residual -> ReLU) plus the 1x1
+// stride-s downsample of the first block of each layer.  The stem is the generic convolution on the NHWC8 input
+// (7x7x8 = 392 k values, 147 of them real: the channel padding adds ~5 % to the plan's executed MACs, 8.61 against
+// 8.18 GFLOP per image; the stem as a whole is ~7 % of them), the heads are ONE GEMM over the pooled
+// 2048 features whose columns [0, pad8(num_classes)) and [pad8(num_classes), ...) land side by side in emb_raw.
+int build_rn50_2b(Encoder& e, WeightMap& wm, int num_classes, int num_projections) {
+  e.in_size = 224;
+  e.n_cls = num_classes; e.n_proj = num_projections;
+  const float EPS = 1e-5f;
+  const int b_in = e.add_buf(224, 224, 8);
+  { Op op; op.kind = Op::PACK; op.a = b_in; e.ops.push_back(op); }
+  auto conv_bn = [&](const std::string& name, const std::string& wname, const std::string& bn, int xb, int cin, int cin_pad, int cout,
+                     int k, int st, int pad, int ob, int res, int act) -> int {
+    ConvSpec s;
+    s.name = name; s.x_buf = xb; s.cin = cin; s.cin_pad = cin_pad; s.KH = s.KW = k; s.sh = s.sw = st; s.ph = s.pw = pad;
+    s.pieces.resize(1);
+    Piece& pc = s.pieces[0];
+    pc.w = wm.get(wname, (int64_t)cout * cin * k * k);
+    pc.cout = pc.cout_pad = cout;
+    NEED(pc.w && bn_fold(wm, bn, cout, EPS, pc.scale, pc.bias));
+    s.segs.push_back({0, cout, ob, 0});
+    s.res_buf = res;
+    s.act = act;
+    return add_conv(e, s);
+  };
+  const int b_stem = e.add_buf(112, 112, 64), b_pool = e.add_buf(56, 56, 64);
+  TRY(conv_bn("conv1", "conv1.weight", "bn1", b_in, 3, 8, 64, 7, 2, 3, b_stem, -1, ACT_RELU));
+  { Op op; op.kind = Op::MAXPOOLP; op.a = b_stem; op.b = b_pool; e.ops.push_back(op); }
+  e.taps["stem"] = {b_stem, 0, 64};
+  e.taps["maxpool"] = {b_pool, 0, 64};
+  const int planes[4] = {64, 128, 256, 512}, nblk[4] = {3, 4, 6, 3};
+  int x = b_pool, cin = 64, H = 56;
+  std::vector<int> stage_end;
+  for (int li = 0; li < 4; ++li) {
+    const int P = planes[li], st0 = li == 0 ? 1 : 2, Ho = H / st0;
+    const int t_first = e.add_buf(H, H, P);   // conv1 output of the first block (input resolution: the stride sits in conv2)
+    const int t_rest = li == 0 ? t_first : e.add_buf(Ho, Ho, P);
+    const int t2 = e.add_buf(Ho, Ho, P), dsb = e.add_buf(Ho, Ho, 4 * P);
+    const int y[2] = {e.add_buf(Ho, Ho, 4 * P), e.add_buf(Ho, Ho, 4 * P)};
+    int cur = -1;
+    for (int b = 0; b < nblk[li]; ++b) {
+      const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+      const int xin = b == 0 ? x : y[cur], xout = b == 0 ? y[0] : y[cur ^ 1];
+      const int ci = b == 0 ? cin : 4 * P, t1 = b == 0 ? t_first : t_rest, st = b == 0 ? st0 : 1;
+      TRY(conv_bn(p + ".conv1", p + ".conv1.weight", p + ".bn1", xin, ci, ci, P, 1, 1, 0, t1, -1, ACT_RELU));
+      TRY(conv_bn(p + ".conv2", p + ".conv2.weight", p + ".bn2", t1, P, P, P, 3, st, 1, t2, -1, ACT_RELU));
+      if (b == 0)
+        TRY(conv_bn(p + ".downsample", p + ".downsample.0.weight", p + ".downsample.1", xin, ci, ci, 4 * P, 1, st, 0, dsb, -1, ACT_NONE));
+      TRY(conv_bn(p + ".conv3", p + ".conv3.weight", p + ".bn3", t2, P, P, 4 * P, 1, 1, 0, xout, b == 0 ? dsb : xin, ACT_RELU));
+      cur = b == 0 ? 0 : cur ^ 1;
+    }
+    x = y[cur];
+    e.taps["layer" + std::to_string(li + 1)] = {x, 0, 4 * P};
+    cin = 4 * P;
+    H = Ho;
+    stage_end.push_back((int)e.ops.size());
+  }
+  // AvgPool2d(7) on the 7x7 map -> fc (2048 -> num_classes) and proj (2048 -> num_projections), both with bias, fp32 out
+  const int pool = e.add_buf(1, 1, 2048);
+  { Op op; op.kind = Op::AVGPOOL; op.a = x; op.b = pool; e.ops.push_back(op); }
+  e.taps["avgpool"] = {pool, 0, 2048};
+  const int cls_pad = (num_classes + 7) / 8 * 8, proj_pad = (num_projections + 7) / 8 * 8;
+  e.emb_ld = cls_pad + proj_pad;
+  {
+    ConvSpec s;
+    s.name = "fc+proj"; s.x_buf = pool; s.cin = s.cin_pad = 2048;
+    s.pieces.resize(2);
+    const char* nm[2] = {"fc", "proj"};
+    const int co[2] = {num_classes, num_projections}, cp[2] = {cls_pad, proj_pad};
+    for (int i = 0; i < 2; ++i) {
+      Piece& pc = s.pieces[i];
+      pc.w = wm.get(std::string(nm[i]) + ".weight", (int64_t)co[i] * 2048);
+      const float* fb = wm.get(std::string(nm[i]) + ".bias", co[i]);
+      NEED(pc.w && fb);
+      pc.cout = co[i]; pc.cout_pad = cp[i];
+      pc.bias.assign(fb, fb + co[i]);
+    }
+    s.segs.push_back({0, e.emb_ld, -2, 0});
+    s.act = ACT_NONE; s.out_f32 = 1;
+    TRY(add_conv(e, s));
+  }
+  { Op op; op.kind = Op::HEADS; op.a = num_classes; op.b = num_projections; op.c = cls_pad; e.ops.push_back(op); }
+  // the stem, the pool and layer1 work on the same 112x112x64 / 56x56x256 tensor sizes as IR-100's first stage, layer2 on
+  // IR-100's second: the same sub-batches (and the same switches) keep producer -> consumer tensors in the Infinity Cache
+  int c1 = 32, c2 = 64;
+  if (e.env.ir100_chunk1 > 0) c1 = e.env.ir100_chunk1;
+  if (e.env.ir100_chunk2 > 0) c2 = e.env.ir100_chunk2;
+  e.groups.push_back({0, stage_end[0], c1});
+  e.groups.push_back({stage_end[0], stage_end[1], c2});
+  e.groups.push_back({stage_end[1], (int)e.ops.size(), 1 << 30});
+  return VNF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // MTCNN R-Net (mtcnn.py:52-99) and O-Net (102-157) as plans on the exact-f32 MFMA convolution core.
 // Candidates are the batch dimension; the crop kernel writes NHWC4 fp32 crops into buffer 0.
@@ -1321,7 +1416,7 @@ int Encoder::select_ctx(hipStream_t s, int* used) {
       VNF_HIP(hipMemsetAsync(p, 0, bytes, s));
       set.push_back(p);
     }
-    float* er = (float*)dalloc((size_t)max_batch * 512 * 4);
+    float* er = (float*)dalloc((size_t)max_batch * emb_ld * 4);
     if (!er) return VNF_E_HIP;
     ctx_bufs.push_back(set);
     ctx_emb.push_back(er);
@@ -1334,7 +1429,7 @@ int Encoder::select_ctx(hipStream_t s, int* used) {
   return VNF_OK;
 }
 
-int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, std::string* report) {
+int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, std::string* report, const RunExtra* extra) {
   if (n < 0 || n > max_batch) return fail(VNF_E_CAPACITY, "batch exceeds max_batch");
   if (n == 0) return VNF_OK;
   if (tune_dirty) {
@@ -1348,7 +1443,7 @@ int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, s
     if (rc != VNF_OK) return rc;
     const int keep = n_ctx;
     n_ctx = 1;  // the body below runs once on the selected set
-    rc = run(x, n, x_dtype, out, s, report);
+    rc = run(x, n, x_dtype, out, s, report, extra);
     n_ctx = keep;
     if (rc != VNF_OK) return rc;
     if (!ctx_ev[c]) VNF_HIP(hipEventCreateWithFlags(&ctx_ev[c], hipEventDisableTiming));
@@ -1357,7 +1452,7 @@ int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, s
   }
   int ns = max_streams < 2 ? max_streams : 2;
   while (ns > 1 && n / ns < 96) --ns;  // below ~100 images a part no longer fills the chip: fixed per-launch latency dominates
-  if (ns == 1 || report) return run_range(x, 0, n, x_dtype, out, s, report);
+  if (ns == 1 || report) return run_range(x, 0, n, x_dtype, out, s, report, extra);
   if (!side[0]) {
     for (int i = 0; i < 4; ++i) {
       VNF_HIP(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
@@ -1370,14 +1465,18 @@ int Encoder::run(const void* x, int n, int x_dtype, float* out, hipStream_t s, s
   for (int i = 0; i < ns && rc == VNF_OK; ++i) {
     const int i0 = (int)((long long)n * i / ns), i1 = (int)((long long)n * (i + 1) / ns);
     VNF_HIP(hipStreamWaitEvent(side[i], fork_ev, 0));
-    rc = run_range(x, i0, i1, x_dtype, out, side[i], nullptr);
+    rc = run_range(x, i0, i1, x_dtype, out, side[i], nullptr, extra);
     VNF_HIP(hipEventRecord(join_ev[i], side[i]));
     VNF_HIP(hipStreamWaitEvent(s, join_ev[i], 0));
   }
   return rc;
 }
 
-int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, hipStream_t s, std::string* report) {
+int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, hipStream_t s, std::string* report,
+                       const RunExtra* extra) {
+  float* const out2 = extra ? extra->out2 : nullptr;
+  const uint8_t* const prep_src = extra ? extra->prep_src : nullptr;
+  const int prep_s = extra ? extra->prep_s : 0;
   const int n = i1 - i0;
   const int es = dtype_size(dtype);
   const int xes = dtype_size(x_dtype);
@@ -1473,6 +1572,11 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
         switch (op.kind) {
           case Op::PACK: {
             const Buf& b = bufs[op.a];
+            if (prep_src) {   // vnf_emotion_recognize: the face transform writes the packed input itself
+              VNF_HIP(launch_emotion_prep(prep_src + (size_t)n0 * prep_s * prep_s * 3, nn, prep_s,
+                                          b.ptr + (size_t)n0 * b.elems_per_image() * es, dtype, true, s));
+              break;
+            }
             const char* src = (const char*)x + (size_t)n0 * 3 * in_size * in_size * xes;
             VNF_HIP(launch_pack_input(src, x_dtype, b.ptr + (size_t)n0 * b.elems_per_image() * es, dtype, nn,
                                       in_size * in_size, s));
@@ -1552,6 +1656,17 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
                                         (float*)ob.ptr + (size_t)n0 * ob.elems_per_image(), ob.H, ob.W, ob.C, nn, dtype == F16X2, s));
             break;
           }
+          case Op::MAXPOOLP: {
+            const Buf& ib = bufs[op.a];
+            const Buf& ob = bufs[op.b];
+            VNF_HIP(launch_maxpool3s2p1(ib.ptr + (size_t)n0 * ib.elems_per_image() * es, ib.C,
+                                        ob.ptr + (size_t)n0 * ob.elems_per_image() * es, ob.C, dtype, nn, ib.H, ib.W, ib.C, s));
+            break;
+          }
+          case Op::HEADS:   // a = class columns, b = projection columns, c = first projection column of emb_raw
+            if (out) VNF_HIP(launch_copy_rows_f32(emb_raw + (size_t)n0 * emb_ld, emb_ld, out + (size_t)n0 * op.a, op.a, nn, op.a, s));
+            if (out2) VNF_HIP(launch_copy_rows_f32(emb_raw + (size_t)n0 * emb_ld + op.c, emb_ld, out2 + (size_t)n0 * op.b, op.b, nn, op.b, s));
+            break;
           case Op::COPYOUT:
             VNF_HIP(hipMemcpyAsync(out + (size_t)n0 * 512, emb_raw + (size_t)n0 * 512, (size_t)nn * 512 * 4,
                                    hipMemcpyDeviceToDevice, s));
@@ -1606,7 +1721,7 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
                  "3x3 s2 3->32 on the caller's tensor, exact f32 (MFMA / VALU)", ms[oi], gf, ms[oi] > 0 ? gf / ms[oi] : 0.0);
       } else {
         static const char* kn[] = {"pack", "conv", "maxpool", "avgpool", "l2norm", "copyout", "maxpool_ceil", "stem1", "dwconv3x3",
-                                   "upsample_add", "retina_stem (u8 frames -> conv0)", "dw3x3+pw1x1 fused"};
+                                   "upsample_add", "retina_stem (u8 frames -> conv0)", "dw3x3+pw1x1 fused", "maxpool_pad1", "heads"};
         snprintf(line, sizeof line, "%-28s %-8s %60s %8.4f ms\n", "", kn[op.kind], "", ms[oi]);
       }
       *report += line;

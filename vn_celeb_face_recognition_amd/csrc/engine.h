@@ -69,7 +69,7 @@ struct ConvLayer {
 };
 
 struct Op {
-  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, MAXPOOLC, STEM1, DWCONV, UPADD, RSTEM, DWPW } kind;
+  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, MAXPOOLC, STEM1, DWCONV, UPADD, RSTEM, DWPW, MAXPOOLP, HEADS } kind;
   int a = 0, b = 0, c = 0, d = 0, e = 0;  // meaning per kind (see engine.cpp)
 };
 
@@ -123,6 +123,15 @@ struct EncoderEnv {
   static EncoderEnv read();
 };
 
+// Per-call arguments of the two-head plan beyond run()'s x / out (`out` is the class head): the second output of
+// Op::HEADS, and the u8 faces (n,S,S,3) Op::PACK transforms instead of packing the caller's tensor (emotion_prep
+// straight into the plan input)
+struct RunExtra {
+  float* out2 = nullptr;
+  const uint8_t* prep_src = nullptr;
+  int prep_s = 0;
+};
+
 struct Encoder : HandleBase {
   ~Encoder() override;  // side streams, fork/join and context events (device buffers: HandleBase)
   int arch, dtype, max_batch, in_size;
@@ -137,15 +146,20 @@ struct Encoder : HandleBase {
   int prepare_fused();  // build the weight streams of the fused stacks (finalize)
   std::unordered_map<std::string, Tap> taps;
   bool buf_materialised(int buf) const;  // false: only ops that an ACTIVE fused stack replaces would write it
-  float* emb_raw = nullptr;  // (max_batch,512) fp32 before the final normalisation
+  float* emb_raw = nullptr;  // (max_batch,emb_ld) fp32 before the final normalisation
+  int emb_ld = 512;          // row length of emb_raw (the two-head plan: both heads side by side)
+  // ResNet-50 two-head plan (build_rn50_2b): head widths and the logits of vnf_emotion_recognize
+  int n_cls = 0, n_proj = 0;
+  float* cls_buf = nullptr;
   double macs_alg = 0, macs_exec = 0;
 
   int add_buf(int H, int W, int C);
   int finalize();  // allocate buffers, autotune tile configurations
   int autotune();
   ConvArgs conv_args(const ConvLayer& L, int n0, int nn) const;
-  int run(const void* x, int n, int x_dtype, float* out, hipStream_t s, std::string* report = nullptr);
-  int run_range(const void* x, int i0, int i1, int x_dtype, float* out, hipStream_t s, std::string* report);
+  int run(const void* x, int n, int x_dtype, float* out, hipStream_t s, std::string* report = nullptr,
+          const RunExtra* extra = nullptr);
+  int run_range(const void* x, int i0, int i1, int x_dtype, float* out, hipStream_t s, std::string* report, const RunExtra* extra);
   float* stem_wt = nullptr;  // IRv1: fp32 folded conv2d_1a weights + biases for the direct stem kernel (Op::STEM1)
   // activation-buffer contexts: consecutive vnf_embed calls rotate over n_ctx private buffer sets, so calls issued
   // on DIFFERENT streams may overlap on the GPU (the latency-bound tail of one batch under the throughput-bound
@@ -166,6 +180,8 @@ struct Encoder : HandleBase {
 
 int build_irv1(Encoder& e, WeightMap& wm);
 int build_ir100(Encoder& e, WeightMap& wm);
+// ResNet-50 with a class head and a projection head (models/resnet_2_branch.py:12-70), 224 x 224 input
+int build_rn50_2b(Encoder& e, WeightMap& wm, int num_classes, int num_projections);
 // RetinaFace (mobilenet0.25) on the exact-f32 core for an H x W input: buffer 0 = NHWC4 mean-subtracted input (written by
 // the caller), head_bufs[l] = (Hl, Wl, 32) fp32 [cls 4 | bbox 8 | landmark 20] of pyramid level l
 int build_retina_mnet(Encoder& e, WeightMap& wm, int H, int W, int head_bufs[3]);

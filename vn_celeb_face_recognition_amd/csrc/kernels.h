@@ -69,6 +69,21 @@ hipError_t launch_maxpool3s2(const void* x, int ldx, void* y, int ldy, int dtype
 hipError_t launch_maxpool_ceil(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, int k,
                                hipStream_t s);
 
+// 3x3 stride-2 max pool with padding 1 (padding compares as -inf; nn.MaxPool2d(3, 2, 1)), NHWC slice -> NHWC slice;
+// every storage layout the plans use (F32, BF16, F16, F16X2 pairs, F16P planar)
+hipError_t launch_maxpool3s2p1(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, hipStream_t s);
+
+// trans_emotion_inf on the device: u8 faces (n,S,S,3), S <= 224 -> Pillow-exact bilinear 224x224 -> x/255 -> (x-mean)/std,
+// written as NCHW (n,3,224,224) of F32/BF16/F16, or (packed) as the NHWC8 plan input of F32/BF16/F16/F16P
+hipError_t launch_emotion_prep(const uint8_t* faces, int n, int S, void* out, int out_dtype, bool packed, hipStream_t s);
+
+// rows of fp32 logits (n,C): indices of the k (1..16, <= C) largest in descending order (exact ties: lower index first)
+// and their softmax values
+hipError_t launch_softmax_topk(const float* logits, int n, int C, int k, int32_t* idx, float* prob, hipStream_t s);
+
+// fp32 rows (n,C): pitched copy src (row stride lds) -> dst (row stride ldd)
+hipError_t launch_copy_rows_f32(const float* src, int lds, float* dst, int ldd, int n, int C, hipStream_t s);
+
 // global average pool NHWC (n,HW,C) -> (n,C)
 hipError_t launch_avgpool(const void* x, int ldx, void* y, int dtype, int n, int HW, int C, hipStream_t s);
 

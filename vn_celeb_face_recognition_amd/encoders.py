@@ -41,6 +41,7 @@ class _Encoder:
     _arch = None
     _arch_name = None
     input_size = None
+    _out_dim = 512      # columns of the tensor vnf_encoder_profile writes
 
     def __init__(self, device=None, compute_dtype="f16x2", max_batch=256):
         self._sd = None
@@ -117,11 +118,13 @@ class _Encoder:
             _lib.check(lib.vnf_init(dev))
             descs, n, keep = _lib.make_descs(self._sd)
             h = ctypes.c_void_p()
-            _lib.check(lib.vnf_encoder_create(self._arch, descs, n, _DTYPES[self.compute_dtype], self.max_batch,
-                                              ctypes.byref(h)))
+            _lib.check(self._create(lib, descs, n, h))
             del keep
         self._handle, self._handle_key = h, key
         return h
+
+    def _create(self, lib, descs, n, h):
+        return lib.vnf_encoder_create(self._arch, descs, n, _DTYPES[self.compute_dtype], self.max_batch, ctypes.byref(h))
 
     def __call__(self, x):
         return self.forward(x)
@@ -201,7 +204,7 @@ class _Encoder:
         """Per-launch device-time table of one forward (text)."""
         h = self._ensure_handle()
         x = x.contiguous()
-        out = torch.empty((x.shape[0], 512), dtype=torch.float32, device=x.device)
+        out = torch.empty((x.shape[0], self._out_dim), dtype=torch.float32, device=x.device)
         buf = ctypes.create_string_buffer(1 << 16)
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().vnf_encoder_profile(h, ctypes.c_void_p(x.data_ptr()), x.shape[0],

@@ -5,6 +5,8 @@ behaviour), with the arithmetic in libvnface.so:
   transforms_default                <- /root/reference/data_loader/__init__.py:27-34,52-56
   find_embedding                    <- /root/reference/demo_image.py:30-34
   recognize_celeb                   <- /root/reference/demo_image.py:50-76
+  trans_emotion_inf                 <- data_loader/__init__.py:74-81
+  find_emotion, recognize_emotion   <- demo_image.py:37-47, 79-110
   identify_person                   <- /root/reference/demo_image.py:113-147
   get_face_from_boxes               <- /root/reference/demo_image.py:174-199
   move_landmark_to_box              <- /root/reference/demo_image.py:236-239
@@ -141,13 +143,94 @@ def recognize_celeb(bth_alg_face_list, device, emb_model, classify_model, transf
     return bth_names
 
 
+def trans_emotion_inf(face):
+    """data_loader/__init__.py:74-81 for a square face ((S,S,3) u8 array or PIL image): Resize(224) (Pillow's bilinear
+    resampling, restated in NumPy), ToTensor, Normalize.  Host tensor (3,224,224) fp32, as the reference returns; the
+    device form of the same transform is vnf_emotion_prep."""
+    from .emotion import EMOTION_MEAN, EMOTION_STD, pillow_bilinear_resize
+    a = np.asarray(face)
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] != a.shape[1] or a.dtype != np.uint8:
+        raise ValueError("trans_emotion_inf expects a square (S,S,3) uint8 face, got %s %s" % (a.shape, a.dtype))
+    x = torch.from_numpy(pillow_bilinear_resize(a).transpose(2, 0, 1).copy()).float().div(255)
+    mean = torch.tensor(EMOTION_MEAN, dtype=torch.float32).view(3, 1, 1)
+    std = torch.tensor(EMOTION_STD, dtype=torch.float32).view(3, 1, 1)
+    return x.sub_(mean).div_(std)
+
+
+def find_emotion(image_tensor, emotion_model, topk=6):
+    """demo_image.py:37-47: (indices (N,k) of the k largest class logits in descending order, their softmax values),
+    as host arrays.  Exact ties come out lower index first (numpy's default argsort, which the reference uses, leaves
+    their order undefined).  Logits on the device go through vnf_softmax_topk; a model that returns host tensors (a
+    caller's own) is ranked on the host with the same rule."""
+    emotion_model.eval()
+    with torch.no_grad():
+        output, _ = emotion_model(image_tensor)
+    topk = int(topk)
+    if topk < 1 or topk > output.shape[1]:
+        raise ValueError("topk must be in 1..%d, got %d" % (output.shape[1], topk))
+    if output.is_cuda:
+        from .emotion import softmax_topk_device
+        idx, prob = softmax_topk_device(output, topk)
+        return idx.cpu().numpy().astype(np.int64), prob.cpu().numpy()
+    output_np = output.detach().float().numpy()
+    percent_np = torch.softmax(output.detach().float(), dim=1).numpy()
+    chosen_idx = np.argsort(-output_np, axis=1, kind="stable")[:, :topk]
+    return chosen_idx, np.take_along_axis(percent_np, chosen_idx, axis=1)
+
+
+def _split_per_frame(bth_alg_face_list, emotions_cls, probs, map_label_func):
+    bth_emotions, bth_probs, counter = [], [], 0
+    for n_face in [len(x) for x in bth_alg_face_list]:
+        bth_emotions.append(map_label_func(emotions_cls[counter: counter + n_face]) if n_face > 0 else [])
+        bth_probs.append(probs[counter: counter + n_face])
+        counter += n_face
+    return bth_emotions, bth_probs
+
+
+def recognize_emotion(bth_alg_face_list, device, emt_model, transforms, map_label_func, topk=6):
+    """demo_image.py:79-110: per frame the (n_face, topk) array of mapped tags and the (n_face, topk) array of
+    probabilities; empty lists for every frame when there is no face at all.
+
+    With this module's trans_emotion_inf as `transforms`, an emotion model of this package and equally sized square
+    faces (what the alignment produces) the faces are uploaded once as bytes and transform, network and top-k run
+    back to back on the device (vnf_emotion_recognize).  Any other `transforms` is applied per face on the host, as
+    the reference does (on a PIL image when Pillow is importable), and the stacked result goes through the network."""
+    alg_face_list = []
+    for x in bth_alg_face_list:
+        alg_face_list += x
+    if len(alg_face_list) == 0:
+        return [[] for _ in bth_alg_face_list], [[] for _ in bth_alg_face_list]
+    shapes = {np.asarray(f).shape for f in alg_face_list}
+    resident = (transforms is trans_emotion_inf and hasattr(emt_model, "recognize") and len(shapes) == 1)
+    if resident:
+        s = next(iter(shapes))
+        resident = len(s) == 3 and s[0] == s[1] and s[0] <= 224 and s[2] == 3 and 1 <= int(topk) <= 16
+    if resident:
+        emt_model.eval()
+        faces = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f, np.uint8) for f in alg_face_list]))).to(device)
+        idx, prob = emt_model.recognize(faces, topk)
+        emotions_cls, probs = idx.cpu().numpy().astype(np.int64), prob.cpu().numpy()
+    else:
+        try:
+            from PIL import Image
+            to_obj = Image.fromarray
+        except ImportError:
+            to_obj = lambda a: a   # noqa: E731
+        emt_tf_list = [transforms(to_obj(np.asarray(face))) for face in alg_face_list]
+        aligned_faces_tf = torch.stack(emt_tf_list, dim=0)
+        emotions_cls, probs = find_emotion(aligned_faces_tf.to(device), emt_model, topk)
+    return _split_per_frame(bth_alg_face_list, emotions_cls, probs, map_label_func)
+
+
 class Ticket:
     """One submitted frame batch (FacePipeline.submit).  `done` is set once detection has finished on the host and
     the embedding work is enqueued; the embeddings / classes are produced on the pipeline's embedding stream."""
-    __slots__ = ("counts", "boxes", "probs", "points", "emb", "amax", "prob", "event", "done", "error", "_slice", "_pipe", "upload_slot")
+    __slots__ = ("counts", "boxes", "probs", "points", "emb", "amax", "prob", "event", "done", "error", "_slice", "_pipe", "upload_slot",
+                 "emo_idx", "emo_prob")
 
     def __init__(self):
         self.counts = self.boxes = self.probs = self.points = None
+        self.emo_idx = self.emo_prob = None   # (n,k) int32 / fp32 cuda, with an emotion model in the pipeline
         self.emb = self.amax = self.prob = self.event = self.error = self._slice = self._pipe = None
         self.upload_slot = -1
         self.done = threading.Event()
@@ -179,13 +262,25 @@ class FacePipeline:
     One call per frame batch (demo_video.py:86-129 without the host round trips): frames are
     uploaded once, vnf_mtcnn_detect leaves boxes/landmarks for vnf_align, the warp writes the
     normalised NCHW batch straight in the encoder's input dtype, and only names, boxes and
-    (optionally) embeddings come back."""
+    (optionally) embeddings come back.
 
-    def __init__(self, detector, encoder, classifier, label2name, target_size, threshold=0.0, embed_batch=0, embed_lanes=1):
+    emotion: an emotion model (models.resnet_2branch_50) or None.  With one, `submit` keeps the aligned u8 faces beside
+    the normalised batch and every ticket gains `emo_idx` / `emo_prob` ((n, topk_emotions) int32 / fp32, cuda), produced
+    by vnf_emotion_recognize on the embedding stream before the ticket's event is recorded; `Ticket.result()` keeps its
+    5-tuple.  The faces of a submit are then embedded at once: an emotion model forces embed_batch to 0.  It also forces
+    embed_lanes to 1: the emotion handle keeps one set of activation buffers, so its calls must follow each other on
+    one stream (on rotating lane streams two submits would write the same buffers unordered).  target_size must be
+    <= 224, the largest face the device transform takes.  Without an emotion model nothing changes."""
+
+    def __init__(self, detector, encoder, classifier, label2name, target_size, threshold=0.0, embed_batch=0, embed_lanes=1,
+                 emotion=None, topk_emotions=6):
         self.detectors = list(detector) if isinstance(detector, (list, tuple)) else [detector]
         self.detector, self.encoder, self.classifier = self.detectors[0], encoder, classifier
         self.label2name = label2name
         self.size = int(target_size)
+        if emotion is not None and self.size > 224:
+            raise ValueError("FacePipeline(emotion=...): target_size %d exceeds 224, the largest aligned face the "
+                             "emotion transform takes" % self.size)
         self.template = center_point_dict[str((self.size, self.size))]
         self.threshold = threshold
         self.in_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}.get(
@@ -197,9 +292,12 @@ class FacePipeline:
         # waiting (0: every batch at once).  The encoder's launches have a fixed latency cost, so 256 faces cost
         # 1.4x what 128 do, not 2x.
         self.embed_batch = int(embed_batch)
+        self.emotion, self.topk_emotions = emotion, int(topk_emotions)
+        if emotion is not None:
+            self.embed_batch = 0
         # embedding streams that consecutive embed launches rotate over (with as many encoder activation contexts),
         # so one group's latency-bound tail runs under the next group's stem
-        self.embed_lanes = max(1, int(embed_lanes))
+        self.embed_lanes = max(1, int(embed_lanes)) if emotion is None else 1   # one lane with an emotion model (docstring)
         self._lane = 0
         self._acc = None
         self._acc_n = 0
@@ -239,11 +337,13 @@ class FacePipeline:
                 emb_s.wait_event(found)
                 with torch.cuda.stream(emb_s):
                     if self.embed_batch <= 0:
-                        _, faces = align_faces_device(frames_dev, fidx_d, boxes_d, points_d, self.template, self.size,
-                                                      want_u8=False, norm_dtype=self.in_dtype)
+                        u8, faces = align_faces_device(frames_dev, fidx_d, boxes_d, points_d, self.template, self.size,
+                                                       want_u8=self.emotion is not None, norm_dtype=self.in_dtype)
                         t.emb = self.encoder(faces)
                         if classify:
                             _, t.amax, t.prob = self.classifier.classify(t.emb, want_logp=False)
+                        if self.emotion is not None:
+                            t.emo_idx, t.emo_prob = self.emotion.recognize(u8, self.topk_emotions)
                         t.event = emb_s.record_event()
                         self._lane = (self._lane + 1) % self.embed_lanes
                     else:
@@ -271,6 +371,9 @@ class FacePipeline:
                     x.record_stream(emb_s)
         else:
             t.emb = torch.empty((0, 512), dtype=torch.float32, device=dev)
+            if self.emotion is not None:
+                t.emo_idx = torch.empty((0, self.topk_emotions), dtype=torch.int32, device=dev)
+                t.emo_prob = torch.empty((0, self.topk_emotions), dtype=torch.float32, device=dev)
 
     def _flush_locked(self):
         """embed (+ classify) the waiting faces on the current lane's stream, then move to the next lane; caller holds
@@ -333,6 +436,8 @@ class FacePipeline:
             self._emb_streams = side_streams(dev, self.embed_lanes, 1)
             self._emb_stream = self._emb_streams[0]
             self._acc = [None] * self.embed_lanes
+            if self.emotion is not None and hasattr(self.emotion, "set_streams"):
+                self.emotion.set_streams(1)
             if hasattr(self.encoder, "set_streams"):
                 self.encoder.set_streams(1)   # the detection stream fills the gaps the encoder's own forks would
                 if self.embed_lanes > 1:

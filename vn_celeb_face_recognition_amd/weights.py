@@ -10,6 +10,8 @@ travelling.  Key names follow:
                           36-181 (blocks), 219-258 (top level)
   * MLPModel           -- models/mlp_model.py:6-8 (dense_1, dense_2)
   * IResNet-100        -- models/iresnet_encoder.py:26-61 (IBasicBlock), 83-99, 117-137
+  * ResNet2Branch      -- models/resnet_2_branch.py:14-28 (conv1, bn1, layer1-4, fc, proj),
+                          models/resnet_2_branch_utils/resnet.py:71-82 (Bottleneck)
   * MTCNN P/R/O-Net    -- models/mtcnn.py:19-28, 62-74, 112-128 (real weights ship as
                           weights_mtcnn/*.pt; the synthetic ones are for stress tests only)
   * RetinaFace (mnet)  -- models/retina_face.py:73-108, retina_face_utils/components.py (the reference downloads
@@ -24,7 +26,7 @@ from collections import OrderedDict
 import numpy as np
 
 __all__ = [
-    "irv1_spec", "mlp_spec", "iresnet_spec", "mtcnn_spec", "retina_spec", "generate_state_dict",
+    "irv1_spec", "mlp_spec", "iresnet_spec", "rn50_2b_spec", "mtcnn_spec", "retina_spec", "generate_state_dict",
     "IRV1_MACS_PER_IMAGE", "IR100_MACS_PER_IMAGE",
 ]
 
@@ -135,6 +137,34 @@ def iresnet_spec(layers=(3, 13, 30, 3), num_features=512):
     s.append(("fc.weight", (num_features, 512 * 49), "linear"))
     s.append(("fc.bias", (num_features,), "bias"))
     _bn(s, "features", num_features)
+    return s
+
+
+def rn50_2b_spec(num_classes=1000, num_projections=300):
+    """ResNet2Branch(Bottleneck, [3, 4, 6, 3]).state_dict() layout (resnet_2_branch.py:14-28): the emotion network.
+    bn3 of every block draws the small residual gain, so 16 residual blocks stay O(1); fc draws wide logits so the
+    top softmax values are spread."""
+    s = [("conv1.weight", (64, 3, 7, 7), "conv")]
+    _bn(s, "bn1", 64)
+    inplanes = 64
+    for li, (planes, nblk) in enumerate(zip((64, 128, 256, 512), (3, 4, 6, 3)), start=1):
+        for b in range(nblk):
+            p = "layer%d.%d" % (li, b)
+            cin = inplanes if b == 0 else planes * 4
+            s.append((p + ".conv1.weight", (planes, cin, 1, 1), "conv"))
+            _bn(s, p + ".bn1", planes)
+            s.append((p + ".conv2.weight", (planes, planes, 3, 3), "conv"))
+            _bn(s, p + ".bn2", planes)
+            s.append((p + ".conv3.weight", (planes * 4, planes, 1, 1), "conv_res"))
+            _bn(s, p + ".bn3", planes * 4, res=True)
+            if b == 0:
+                s.append((p + ".downsample.0.weight", (planes * 4, cin, 1, 1), "conv_lin"))
+                _bn(s, p + ".downsample.1", planes * 4)
+        inplanes = planes * 4
+    s.append(("fc.weight", (num_classes, 2048), "linear_wide"))
+    s.append(("fc.bias", (num_classes,), "bias"))
+    s.append(("proj.weight", (num_projections, 2048), "linear"))
+    s.append(("proj.bias", (num_projections,), "bias"))
     return s
 
 
@@ -273,6 +303,7 @@ _SPECS = {
     "irv1": irv1_spec,
     "mlp": mlp_spec,
     "iresnet100": iresnet_spec,
+    "rn50_2b": rn50_2b_spec,
     "pnet": lambda: mtcnn_spec("pnet"),
     "rnet": lambda: mtcnn_spec("rnet"),
     "onet": lambda: mtcnn_spec("onet"),
