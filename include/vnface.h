@@ -23,6 +23,8 @@
  *   vnf_emotion_prep                 data_loader/__init__.py:74-81 (trans_emotion_inf)
  *   vnf_softmax_topk                 demo_image.py:37-47 (find_emotion, after the forward)
  *   vnf_emotion_recognize            demo_image.py:79-110 (recognize_emotion: transform, forward, top-k)
+ *   vnf_augment_faces                data_loader/__init__.py:58-65 (transforms_facenet_aug) as
+ *                                    trainer/online_aug_trainer.py:22-33 consumes it per batch
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -177,6 +179,31 @@ int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t* target, in
 int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
 int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
 int vnf_mlp_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
+
+/* training-time augmentation --------------------------------------------- */
+/* transforms_facenet_aug (data_loader/__init__.py:58-65) for the images VNCelebDataset serves
+ * (data_loader/vn_celeb_dataset.py:12-47) to AugClassificationTrainer (trainer/online_aug_trainer.py:22-33): the random
+ * state of one sample, drawn by the host.  m: the matrix Pillow's Image.rotate builds for the drawn angle (output pixel
+ * centre -> input position); i, j: row and column of the crop origin in the zero-padded image; flip: mirror the crop;
+ * pad: the zero border per side, 2 + max(0, T - (S + 4)) for RandomCrop(T, padding=2, pad_if_needed=True). */
+typedef struct {
+  double m[6];
+  int32_t i, j, flip, pad;
+} vnf_aug_param;
+
+/* One launch: output row r = face index[r] (index NULL: face r, and then n == n_faces) rotated with Pillow's bicubic
+ * resampling (byte-exact: double arithmetic in Pillow's operation order, truncation to u8), zero-padded, cropped at
+ * (i, j), mirrored, then np.float32, (v - 127.5) / 128 and CHW (fix_std, to_tensor; data_loader/__init__.py:27-34).
+ * With m the identity, i = j = pad and flip 0 this is transforms_default (:52-56).
+ *   faces: device (n_faces,S,S,3) u8, the resident data set; index: device (n) int32 or NULL; params: device (n);
+ *   x_out: device (n,3,T,T) of out_dtype VNF_F32 | VNF_BF16 | VNF_F16, may be NULL;
+ *   u8_out: device (n,T,T,3) augmented bytes, may be NULL.
+ * No workspace, nothing allocated, no synchronisation.  n == 0: no-op.  S or T outside 1..1024, a NULL faces / params
+ * with n > 0, n_faces < 1, index NULL with n != n_faces or a bad out_dtype: VNF_E_INVALID.  index and params live in device memory, so the call cannot see their values: a row
+ * whose index is outside 0..n_faces-1 or whose crop origin is outside [0, S + 2 pad - T] is written as the fill
+ * (byte 0) and reads nothing; the host layer checks both before it uploads them. */
+int vnf_augment_faces(const uint8_t* faces, int n_faces, int s, const int32_t* index, const vnf_aug_param* params,
+                      int n, int t, void* x_out, int out_dtype, uint8_t* u8_out, void* stream);
 
 /* detector --------------------------------------------------------------------------------- */
 typedef struct {

@@ -54,6 +54,7 @@ SIGNATURES = {
     "vnf_emotion_forward": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "vnf_emotion_recognize": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "vnf_emotion_prep": (_I, [_P, _I, _I, _P, _I, _P]),
+    "vnf_augment_faces": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _P, _P]),
     "vnf_softmax_topk": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "vnf_maxpool3s2p1": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vnf_mlp_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.POINTER(_P)]),

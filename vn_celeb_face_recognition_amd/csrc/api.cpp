@@ -252,6 +252,27 @@ int vnf_emotion_prep(const uint8_t* faces_u8, int n, int s, void* x_out, int out
   API_GUARD_END
 }
 
+int vnf_augment_faces(const uint8_t* faces, int n_faces, int s, const int32_t* index, const vnf_aug_param* params, int n,
+                      int t, void* x_out, int out_dtype, uint8_t* u8_out, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0) return fail(VNF_E_INVALID, "bad argument");
+  if (s < 1 || s > 1024 || t < 1 || t > 1024) return fail(VNF_E_INVALID, "face size and target size must be 1..1024");
+  if (out_dtype != VNF_F32 && out_dtype != VNF_BF16 && out_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad out_dtype");
+  if (n == 0) return VNF_OK;
+  if (!faces || !params || n_faces < 1) return fail(VNF_E_INVALID, "faces and params must not be NULL");
+  if (!index && n != n_faces) return fail(VNF_E_INVALID, "without an index there is one parameter set per face");
+  for (int n0 = 0; n0 < n; n0 += 32768) {
+    const int nn = n - n0 < 32768 ? n - n0 : 32768;
+    // without an index row r reads face r: the chunk's faces start at n0
+    VNF_HIP(launch_augment_faces(index ? faces : faces + (size_t)n0 * s * s * 3, index ? n_faces : nn, s,
+                                 index ? index + n0 : nullptr, params + n0, nn, t,
+                                 x_out ? (char*)x_out + (size_t)n0 * 3 * t * t * dtype_size(out_dtype) : nullptr, out_dtype,
+                                 u8_out ? u8_out + (size_t)n0 * t * t * 3 : nullptr, (hipStream_t)stream));
+  }
+  return VNF_OK;
+  API_GUARD_END
+}
+
 int vnf_softmax_topk(const float* logits, int n, int c, int k, int32_t* idx, float* prob, void* stream) {
   API_GUARD_BEGIN
   if (n < 0 || c < 1 || (n > 0 && (!logits || !idx || !prob))) return fail(VNF_E_INVALID, "bad argument");

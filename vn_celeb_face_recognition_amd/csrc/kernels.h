@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vnface.h"
+
 namespace vnf {
 
 // F16X2: split-f16 (hi, lo) pairs, split_f16.h -- fp32-class accuracy on the 16-bit MFMA (ids follow include/vnface.h)
@@ -76,6 +78,12 @@ hipError_t launch_maxpool3s2p1(const void* x, int ldx, void* y, int ldy, int dty
 // trans_emotion_inf on the device: u8 faces (n,S,S,3), S <= 224 -> Pillow-exact bilinear 224x224 -> x/255 -> (x-mean)/std,
 // written as NCHW (n,3,224,224) of F32/BF16/F16, or (packed) as the NHWC8 plan input of F32/BF16/F16/F16P
 hipError_t launch_emotion_prep(const uint8_t* faces, int n, int S, void* out, int out_dtype, bool packed, hipStream_t s);
+
+// transforms_facenet_aug on the device (augment.hip): row r of the output is face index[r] (NULL: r) of the u8 data set
+// (n_faces,S,S,3), rotated / padded / cropped / mirrored as params[r] says -> NCHW (n,3,T,T) of F32/BF16/F16 (x_out) and /
+// or the augmented bytes (n,T,T,3) (u8_out); n <= 65535
+hipError_t launch_augment_faces(const uint8_t* faces, int n_faces, int S, const int32_t* index, const vnf_aug_param* params, int n,
+                                int T, void* x_out, int out_dtype, uint8_t* u8_out, hipStream_t s);
 
 // rows of fp32 logits (n,C): indices of the k (1..16, <= C) largest in descending order (exact ties: lower index first)
 // and their softmax values

@@ -6,6 +6,9 @@ the optimisation step itself in libvnface.so (csrc/mlp_train.hip):
   ReduceLROnPlateau       <- torch.optim.lr_scheduler.ReduceLROnPlateau as train.py:64-66 configures it
   MetricTracker           <- /root/reference/utils/utils.py:13-37
   ClassificationTrainer   <- /root/reference/trainer/base_trainer.py:11-190, classification_trainer.py:5-98
+  VNCelebDataset          <- /root/reference/data_loader/vn_celeb_dataset.py:12-47
+  AugClassificationTrainer <- /root/reference/trainer/online_aug_trainer.py:6-97 (images -> augmentation -> frozen
+                             encoder -> MLP step, all on the device: augment.py, csrc/augment.hip)
 
 Same config keys (cfg/train_cfg_emb_classify.json), same checkpoint dict (base_trainer.py:83-105: arch, epoch,
 state_dict, optimizer in torch.optim.Adam's state_dict layout, monitor_best, config), same log_loss.txt.  torch is
@@ -51,6 +54,57 @@ class VNCelebEmbDataset(torch.utils.data.Dataset):
         emb = np.load(str(emb_path))["arr_0"]
         data = self.transforms(emb) if self.transforms else torch.from_numpy(emb)
         return data, self.labels[index], str(emb_path)
+
+
+class VNCelebDataset(torch.utils.data.Dataset):
+    """label json {class: [image names]} + <data_dir>/<image name> -> (index, label, path).
+
+    The reference decodes and transforms one image per __getitem__ on the host (vn_celeb_dataset.py:22-33).  Here every
+    image is decoded once, at construction, and the whole set is one u8 array (N,S,S,3) that faces_device() keeps
+    resident on the GPU; an item is the ROW of that array, so a DataLoader built from the config's own arguments still
+    does the sampling (torch's sampler, torch's generator) while the pixels never leave the device.  Deviation
+    (DESIGN.md 8): the images must be square and all of one size -- aligned face crops, what find_embedding.py and
+    the demos' alignment write -- since one batch is one kernel launch over one array; anything else raises."""
+
+    def __init__(self, data_dir, label_file, transforms=None):
+        from PIL import Image
+        self.data_dir = Path(data_dir)
+        with open(label_file) as fp:
+            self.label_dict = json.load(fp)
+        self.transforms = transforms
+        self.n_samples = sum(len(v) for v in self.label_dict.values())
+        self.n_classes = len(self.label_dict)
+        self.img_names, self.labels = [], []
+        for k, v in self.label_dict.items():
+            names = sorted(v)
+            self.img_names += names
+            self.labels += len(names) * [int(k)]
+        faces = []
+        for name in self.img_names:
+            with Image.open(str(self.data_dir / name)) as im:
+                a = np.asarray(im.convert("RGB"))
+            if a.shape[0] != a.shape[1]:
+                raise ValueError("%s is %dx%d: VNCelebDataset takes square face crops" % (name, a.shape[1], a.shape[0]))
+            if faces and a.shape != faces[0].shape:
+                raise ValueError("%s is %dx%d but %s is %dx%d: all images of a VNCelebDataset must have one size"
+                                 % (name, a.shape[1], a.shape[0], self.img_names[0], faces[0].shape[1], faces[0].shape[0]))
+            faces.append(a)
+        self.faces = np.stack(faces) if faces else np.zeros((0, 0, 0, 3), np.uint8)
+        self.size = int(self.faces.shape[1])
+        self._dev = None
+
+    def __len__(self):
+        return self.n_samples
+
+    def __getitem__(self, index):
+        return index, self.labels[index], str(self.data_dir / self.img_names[index])
+
+    def faces_device(self, device):
+        """The data set as one cuda u8 tensor (N,S,S,3), uploaded at first use."""
+        device = torch.device(device)
+        if self._dev is None or self._dev.device != device:
+            self._dev = torch.from_numpy(self.faces).to(device)
+        return self._dev
 
 
 class TrainableMLP:
@@ -246,6 +300,10 @@ class ClassificationTrainer:
     def setup_loader(self, train_loader, val_loader):
         self.train_loader, self.val_loader = train_loader, val_loader
 
+    def _batch_input(self, data, train):
+        """What the loader yields -> what the MLP step takes: here the embeddings themselves."""
+        return data
+
     def resume_checkpoint(self, checkpoint_path):
         cp = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
         self.logger.info("Loading checkpoint: {} ...".format(checkpoint_path))
@@ -270,6 +328,7 @@ class ClassificationTrainer:
         for t in (self.train_loss, self.train_metrics, self.val_loss, self.val_metrics):
             t.reset()
         for batch_idx, (data, target, _id) in enumerate(self.train_loader):
+            data = self._batch_input(data, train=True)
             loss, hits = self.model.step(data, target, train=True)
             self.train_loss.update(self.loss_name, loss)
             self.train_metrics.update("accuracy", hits / data.size(0), n=data.size(0))
@@ -291,6 +350,7 @@ class ClassificationTrainer:
         self.val_metrics.reset()
         self.logger.info("Validation: ")
         for batch_idx, (data, target, _id) in enumerate(self.val_loader):
+            data = self._batch_input(data, train=False)
             loss, hits = self.model.step(data, target, train=False)
             self.val_loss.update(self.loss_name, loss)
             self.val_metrics.update("accuracy", hits / data.size(0), n=data.size(0))
@@ -327,3 +387,50 @@ class ClassificationTrainer:
                 break
             if epoch % self.save_step == 0:
                 self.save_checkpoint(epoch, save_best=best)
+
+
+class AugClassificationTrainer(ClassificationTrainer):
+    """trainer/online_aug_trainer.py:6-97: the frozen encoder of trainer.encoders[trainer.chosen_idx_enc] embeds every
+    batch inside the loop.  A training batch is: rows of the resident data set (VNCelebDataset) -> the draws of
+    `transforms.name` -> vnf_augment_faces -> encoder -> the fused MLP step; a validation batch takes the default
+    transform (train.py:30-34).  Nothing between the sampler's indices and the loss scalar touches the host.  The
+    encoder is frozen and the default transform draws nothing, so the validation embeddings are computed once and
+    kept.  Log lines, checkpoints, scheduler and early stop are ClassificationTrainer's."""
+
+    def __init__(self, config, model, lr_scheduler, run_id=None):
+        super().__init__(config, model, lr_scheduler, run_id=run_id)
+        from . import augment, models
+        tc = config["trainer"]
+        info = tc["encoders"][tc["chosen_idx_enc"]]
+        self.encoder = getattr(models, info["name"])(**info.get("args", {}))
+        self.encoder.to(self.model.device)
+        self.encoder.eval()
+        tf = config["transforms"]
+        if tf.get("resize"):
+            raise NotImplementedError("transforms.resize is not built: crop the faces at the encoder's input size (DESIGN.md 8)")
+        self.transform = augment.get_transform(tf["name"])
+        self.val_transform = augment.get_transform("default")
+        # the encoder's own input dtype: 16-bit storage paths take 16-bit images, the others fp32
+        self.x_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}.get(self.encoder.compute_dtype, torch.float32)
+        self._val_emb = None
+
+    def embed(self, dataset, index, transform):
+        """Rows `index` of `dataset` through `transform` and the encoder: cuda (n,512) fp32."""
+        from . import augment
+        t = self.encoder.input_size
+        faces = dataset.faces_device(self.model.device)
+        index = torch.as_tensor(index, dtype=torch.int64)
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(dataset)):
+            raise IndexError("sample index outside the data set")
+        params = transform.params(int(index.numel()), dataset.size, t)
+        return self.encoder(augment.augment_faces_device(faces, index, params, t, dtype=self.x_dtype))
+
+    def _batch_input(self, data, train):
+        if train:
+            return self.embed(self.train_loader.dataset, data, self.transform)
+        if self._val_emb is None:
+            ds = self.val_loader.dataset
+            bs = self.encoder.max_batch
+            self._val_emb = torch.cat([self.embed(ds, torch.arange(i, min(i + bs, len(ds))), self.val_transform)
+                                       for i in range(0, len(ds), bs)]) if len(ds) else torch.zeros((0, 512), device=self.model.device)
+        return self._val_emb[torch.as_tensor(data, dtype=torch.int64).to(self._val_emb.device)]
