@@ -3,11 +3,7 @@
 #include <new>
 
 #include "engine.h"
-#include <cstdlib>
 
-namespace vnf {
-const char* last_error_cstr();
-}
 using namespace vnf;
 
 #define API_GUARD_BEGIN try {
@@ -16,6 +12,30 @@ using namespace vnf;
   catch (const std::bad_alloc&) { return fail(VNF_E_INVALID, "host out of memory"); } \
   catch (const std::exception& ex) { return fail(VNF_E_INVALID, std::string("exception: ") + ex.what()); } \
   catch (...) { return fail(VNF_E_INVALID, "unknown exception"); }
+
+// An encoder handle of `arch` on the plan `build` makes: what vnf_encoder_create and vnf_emotion_create share
+template <class Build>
+static int create_encoder(int arch, const vnf_tensor_desc* weights, int n_weights, int compute_dtype, int max_batch, vnf_handle* out,
+                          Build build) {
+  if (!out || !weights || n_weights <= 0 || max_batch <= 0) return fail(VNF_E_INVALID, "bad argument");
+  if (compute_dtype != VNF_F32 && compute_dtype != VNF_BF16 && compute_dtype != VNF_F16 && compute_dtype != VNF_F16X2)
+    return fail(VNF_E_INVALID, "compute_dtype must be VNF_F32, VNF_BF16, VNF_F16 or VNF_F16X2");
+  *out = nullptr;
+  Encoder* e = new Encoder();
+  e->arch = arch;
+  // VNF_F32/BF16/F16 == vnf::F32/BF16/F16; the encoders keep VNF_F16X2 tensors PLANAR (F16P: 8-channel units
+  // [8 hi][8 lo], three MFMAs per product, split_f16.h)
+  e->dtype = compute_dtype == VNF_F16X2 ? F16P : compute_dtype;
+  e->max_batch = max_batch;
+  (void)hipGetDevice(&e->device);
+  WeightMap wm(weights, n_weights);
+  int r = build(*e, wm);
+  if (r == VNF_OK) r = e->finalize();
+  if (r != VNF_OK) { delete e; return r; }
+  VNF_HIP(hipDeviceSynchronize());
+  *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(e));
+  return VNF_OK;
+}
 
 extern "C" {
 
@@ -46,40 +66,15 @@ int vnf_destroy(vnf_handle h) {
 int vnf_encoder_create(int arch, const vnf_tensor_desc* weights, int n_weights, int compute_dtype, int max_batch,
                        vnf_handle* out) {
   API_GUARD_BEGIN
-  if (!out || !weights || n_weights <= 0 || max_batch <= 0) return fail(VNF_E_INVALID, "bad argument");
-  if (compute_dtype != VNF_F32 && compute_dtype != VNF_BF16 && compute_dtype != VNF_F16 && compute_dtype != VNF_F16X2)
-    return fail(VNF_E_INVALID, "compute_dtype must be VNF_F32, VNF_BF16, VNF_F16 or VNF_F16X2");
-  *out = nullptr;
-  Encoder* e = new Encoder();
-  e->kind = 1;
-  e->arch = arch;
-  // VNF_F32/BF16/F16 == vnf::F32/BF16/F16; the encoders keep VNF_F16X2 tensors PLANAR (F16P: 8-channel units
-  // [8 hi][8 lo], three MFMAs per product, split_f16.h)
-  e->dtype = compute_dtype == VNF_F16X2 ? F16P : compute_dtype;
-  e->max_batch = max_batch;
-  (void)hipGetDevice(&e->device);
-  WeightMap wm(weights, n_weights);
-  int r = arch == VNF_ARCH_IRV1 ? build_irv1(*e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(*e, wm)
-                                                                               : fail(VNF_E_INVALID, "unknown arch");
-  if (r == VNF_OK) r = e->finalize();
-  if (r != VNF_OK) {
-    delete e;
-    return r;
-  }
-  VNF_HIP(hipDeviceSynchronize());
-  *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(e));
-  return VNF_OK;
+  return create_encoder(arch, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
+    return arch == VNF_ARCH_IRV1 ? build_irv1(e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(e, wm) : fail(VNF_E_INVALID, "unknown arch");
+  });
   API_GUARD_END
-}
-
-static Encoder* as_encoder(vnf_handle h) {
-  HandleBase* b = reinterpret_cast<HandleBase*>(h);
-  return (b && b->kind == 1) ? static_cast<Encoder*>(b) : nullptr;
 }
 
 int vnf_embed(vnf_handle h, const void* x, int n, int x_dtype, float* emb_out, void* stream) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
   if (e->arch == VNF_ARCH_RN50_2B) return fail(VNF_E_INVALID, "emotion handle: use vnf_emotion_forward");
   if (n < 0 || (n > 0 && (!x || !emb_out))) return fail(VNF_E_INVALID, "bad argument");
@@ -90,7 +85,7 @@ int vnf_embed(vnf_handle h, const void* x, int n, int x_dtype, float* emb_out, v
 
 int vnf_encoder_tap(vnf_handle h, const char* name, int n, float* host_out, int64_t capacity, int64_t shape_out[4]) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e || !name) return fail(VNF_E_INVALID, "not an encoder handle");
   auto it = e->taps.find(name);
   if (it == e->taps.end()) return fail(VNF_E_INVALID, std::string("no such tap: ") + name);
@@ -116,7 +111,7 @@ int vnf_encoder_tap(vnf_handle h, const char* name, int n, float* host_out, int6
 int vnf_encoder_profile(vnf_handle h, const void* x, int n, int x_dtype, float* emb_out, void* stream, char* report,
                         int64_t capacity) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e || !report || capacity <= 0) return fail(VNF_E_INVALID, "bad argument");
   std::string rep;
   int r = e->run(x, n, x_dtype, emb_out, (hipStream_t)stream, &rep);
@@ -129,7 +124,7 @@ int vnf_encoder_profile(vnf_handle h, const void* x, int n, int x_dtype, float* 
 
 int vnf_encoder_flops(vnf_handle h, double* algorithmic, double* executed) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
   if (algorithmic) *algorithmic = 2.0 * e->macs_alg;
   if (executed) *executed = 2.0 * e->macs_exec;
@@ -139,7 +134,7 @@ int vnf_encoder_flops(vnf_handle h, double* algorithmic, double* executed) {
 
 int vnf_encoder_set_streams(vnf_handle h, int max_streams) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
   if (max_streams < 1 || max_streams > 4) return fail(VNF_E_INVALID, "vnf_encoder_set_streams: 1..4");
   if (e->max_streams != max_streams) {
@@ -152,7 +147,7 @@ int vnf_encoder_set_streams(vnf_handle h, int max_streams) {
 
 int vnf_encoder_set_contexts(vnf_handle h, int n) {
   API_GUARD_BEGIN
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
   if (n < 1 || n > 4) return fail(VNF_E_INVALID, "vnf_encoder_set_contexts: 1..4");
   if (e->arch == VNF_ARCH_RN50_2B && n != 1) return fail(VNF_E_INVALID, "vnf_encoder_set_contexts: not for the emotion network");
@@ -170,37 +165,20 @@ int vnf_encoder_set_contexts(vnf_handle h, int n) {
 int vnf_emotion_create(const vnf_tensor_desc* weights, int n_weights, int num_classes, int num_projections, int compute_dtype,
                        int max_batch, vnf_handle* out) {
   API_GUARD_BEGIN
-  if (!out || !weights || n_weights <= 0 || max_batch <= 0 || num_classes < 1 || num_projections < 1 || num_classes > 65536 ||
-      num_projections > 65536)
-    return fail(VNF_E_INVALID, "bad argument");
-  if (compute_dtype != VNF_F32 && compute_dtype != VNF_BF16 && compute_dtype != VNF_F16 && compute_dtype != VNF_F16X2)
-    return fail(VNF_E_INVALID, "compute_dtype must be VNF_F32, VNF_BF16, VNF_F16 or VNF_F16X2");
-  *out = nullptr;
-  Encoder* e = new Encoder();
-  e->kind = 1;
-  e->arch = VNF_ARCH_RN50_2B;
-  e->dtype = compute_dtype == VNF_F16X2 ? F16P : compute_dtype;
-  e->max_batch = max_batch;
-  (void)hipGetDevice(&e->device);
-  WeightMap wm(weights, n_weights);
-  int r = build_rn50_2b(*e, wm, num_classes, num_projections);
-  if (r == VNF_OK) r = e->finalize();
-  if (r == VNF_OK) {
-    e->cls_buf = (float*)e->dalloc((size_t)max_batch * num_classes * 4);
-    if (!e->cls_buf) r = VNF_E_HIP;
-  }
-  if (r != VNF_OK) {
-    delete e;
-    return r;
-  }
-  VNF_HIP(hipDeviceSynchronize());
-  *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(e));
+  if (num_classes < 1 || num_projections < 1 || num_classes > 65536 || num_projections > 65536) return fail(VNF_E_INVALID, "bad argument");
+  const int r = create_encoder(VNF_ARCH_RN50_2B, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
+    return build_rn50_2b(e, wm, num_classes, num_projections);
+  });
+  if (r != VNF_OK) return r;
+  Encoder* e = handle_cast<Encoder>(*out);
+  e->cls_buf = (float*)e->dalloc((size_t)max_batch * num_classes * 4);
+  if (!e->cls_buf) { delete e; *out = nullptr; return VNF_E_HIP; }
   return VNF_OK;
   API_GUARD_END
 }
 
 static Encoder* as_emotion(vnf_handle h) {
-  Encoder* e = as_encoder(h);
+  Encoder* e = handle_cast<Encoder>(h);
   return (e && e->arch == VNF_ARCH_RN50_2B) ? e : nullptr;
 }
 

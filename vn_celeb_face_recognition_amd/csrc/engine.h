@@ -14,6 +14,7 @@ namespace vnf {
 
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+const char* last_error_cstr();   // the calling thread's last message (vnf_last_error)
 
 #define VNF_HIP(expr)                                                                         \
   do {                                                                                        \
@@ -22,14 +23,24 @@ int fail(int code, const std::string& msg);
       return ::vnf::fail(VNF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
+enum class HandleKind { Encoder = 1, Mlp, Mtcnn, MlpTrainer, Retina };
+
 struct HandleBase {
-  int kind = 0;  // 1 encoder, 2 mlp, 3 mtcnn
+  const HandleKind kind;
+  explicit HandleBase(HandleKind k) : kind(k) {}
   int device = 0;
   std::vector<void*> allocs;  // device allocations owned by the handle
   virtual ~HandleBase();
   void* dalloc(size_t bytes);  // hipMalloc + bookkeeping (nullptr on failure, error set)
   void* upload(const void* host, size_t bytes);
 };
+
+// The handle as a T, or nullptr when it is null or of another kind (every handle type names its kind as T::KIND).
+template <class T>
+T* handle_cast(vnf_handle h) {
+  HandleBase* b = reinterpret_cast<HandleBase*>(h);
+  return (b && b->kind == T::KIND) ? static_cast<T*>(b) : nullptr;
+}
 
 // state_dict lookup -----------------------------------------------------------------------
 struct WeightMap {
@@ -70,7 +81,27 @@ struct ConvLayer {
 
 struct Op {
   enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, MAXPOOLC, STEM1, DWCONV, UPADD, RSTEM, DWPW, MAXPOOLP, HEADS } kind;
-  int a = 0, b = 0, c = 0, d = 0, e = 0;  // meaning per kind (see engine.cpp)
+  int src = -1;                   // source buffer
+  int dst = -1, dst_coff = 0;     // destination buffer and the channel offset of the slice written in it
+  int layer = -1;                 // index into Encoder::convs (CONV, STEM1), dws (DWCONV) or dwpws (DWPW)
+  int window = 0;                 // MAXPOOLC: pool window
+  int frame_h = 0, frame_w = 0;   // RSTEM: size of the u8 frames the caller passes as x
+  int n_cls = 0, n_proj = 0, proj_col = 0;   // HEADS: widths of the two heads, first projection column of emb_raw
+
+  static Op pack(int dst) { Op o{PACK}; o.dst = dst; return o; }   // the caller's NCHW tensor (or u8 faces) -> NHWC8 plan input
+  static Op conv(int layer) { Op o{CONV}; o.layer = layer; return o; }
+  static Op stem1(int layer, int dst) { Op o{STEM1}; o.layer = layer; o.dst = dst; return o; }   // PACK + CONV of conv2d_1a, direct
+  static Op maxpool(int src, int dst, int dst_coff) { Op o{MAXPOOL}; o.src = src; o.dst = dst; o.dst_coff = dst_coff; return o; }   // 3x3 s2
+  static Op maxpool_ceil(int src, int dst, int window) { Op o{MAXPOOLC}; o.src = src; o.dst = dst; o.window = window; return o; }
+  static Op maxpool_pad1(int src, int dst) { Op o{MAXPOOLP}; o.src = src; o.dst = dst; return o; }   // 3x3 s2 p1
+  static Op avgpool(int src, int dst) { Op o{AVGPOOL}; o.src = src; o.dst = dst; return o; }
+  static Op l2norm() { return Op{L2NORM}; }     // emb_raw -> out, rows normalised
+  static Op copyout() { return Op{COPYOUT}; }   // emb_raw -> out
+  static Op dwconv(int layer) { Op o{DWCONV}; o.layer = layer; return o; }
+  static Op dwpw(int layer) { Op o{DWPW}; o.layer = layer; return o; }
+  static Op upadd(int src, int dst) { Op o{UPADD}; o.src = src; o.dst = dst; return o; }   // dst += nearest-upsampled src
+  static Op rstem(int frame_h, int frame_w, int dst) { Op o{RSTEM}; o.frame_h = frame_h; o.frame_w = frame_w; o.dst = dst; return o; }
+  static Op heads(int n_cls, int n_proj, int proj_col) { Op o{HEADS}; o.n_cls = n_cls; o.n_proj = n_proj; o.proj_col = proj_col; return o; }
 };
 
 struct DwLayer {   // depthwise 3x3 pad 1 + folded BN + LeakyReLU (fp32 plans: RetinaFace's MobileNetV1)
@@ -92,22 +123,24 @@ struct Group { int first, last, chunk; };
 // of repeat_2 become one launch of block17_trunk_kernel (trunk17.hip), the 25 of repeat_1 five launches of
 // block35_kernel (block35.hip).
 struct FusedStack {
-  int kind = 17;               // 17: persistent Block17 stack (trunk17.hip); 35: one fused launch per Block35 (block35.hip);
-                               // 2: conv2d_2a + conv2d_2b + maxpool_3a in one launch (stem_mid.hip)
+  // Block17: persistent Block17 stack (trunk17.hip); Block35: one fused launch per Block35 (block35.hip);
+  // StemMid: conv2d_2a + conv2d_2b + maxpool_3a in one launch (stem_mid.hip)
+  enum class Kind { StemMid, Block35, Block17 } kind = Kind::Block17;
   int first = 0, last = 0;     // op range
   int in_buf = -1, out_buf = -1;
   int nblocks = 0;
   int conv0 = 0;               // index of the first of the 4*nblocks convolutions (reduce, 1x7, 7x1, up per block)
   void* wstream = nullptr;
   float* bias = nullptr;
-  void* wtail = nullptr;       // kind 35 with ext: block35_tail_repack image of mixed_6a.branch1.0
+  void* wtail = nullptr;       // Block35 with ext: block35_tail_repack image of mixed_6a.branch1.0
   bool active = false;
-  bool stack = false;          // kind 35: the five blocks in ONE launch, x resident in registers (trunk35.hip; bf16 / f16)
+  bool stack = false;          // Block35: the five blocks in ONE launch, x resident in registers (trunk35.hip; bf16 / f16)
   double macs_alg = 0;         // per image
-  // kind 2: conv2d_3b (the op after the pool) folded into the stem kernel; kind 35 (stack): mixed_6a.branch1.0 (the op
+  // StemMid: conv2d_3b (the op after the pool) folded into the stem kernel; Block35 (stack): mixed_6a.branch1.0 (the op
   // after the last block) computed from the register-resident output: ops [first, ext_last) become one launch
   int ext_last = 0, ext_conv = -1, ext_out_buf = -1;
   bool ext = false;
+  int end() const { return ext ? ext_last : last; }   // one past the last op the stack's launch replaces
 };  // ops [first,last) run per `chunk` images (L3 residency)
 
 struct Tap { int buf, coff, C; };
@@ -132,7 +165,12 @@ struct RunExtra {
   int prep_s = 0;
 };
 
+// arch of the internal sub-plans (the public VNF_ARCH_* values are >= 0)
+constexpr int ARCH_MLP = -1, ARCH_RNET = -2, ARCH_ONET = -3, ARCH_RETINA = -5;
+
 struct Encoder : HandleBase {
+  static constexpr HandleKind KIND = HandleKind::Encoder;
+  Encoder() : HandleBase(KIND) {}
   ~Encoder() override;  // side streams, fork/join and context events (device buffers: HandleBase)
   int arch, dtype, max_batch, in_size;
   std::vector<Buf> bufs;
@@ -143,7 +181,9 @@ struct Encoder : HandleBase {
   std::vector<Op> ops;
   std::vector<Group> groups;
   std::vector<FusedStack> fused;
+  std::vector<int> fused_at;   // per op: index of the ACTIVE fused stack that starts there, or -1 (finalize)
   int prepare_fused();  // build the weight streams of the fused stacks (finalize)
+  int launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s);   // images [n0, n0 + nn) through the stack's kernel
   std::unordered_map<std::string, Tap> taps;
   bool buf_materialised(int buf) const;  // false: only ops that an ACTIVE fused stack replaces would write it
   float* emb_raw = nullptr;  // (max_batch,emb_ld) fp32 before the final normalisation
@@ -154,12 +194,18 @@ struct Encoder : HandleBase {
   double macs_alg = 0, macs_exec = 0;
 
   int add_buf(int H, int W, int C);
+  // image n0 of a buffer, at channel `coff` (at_f32: the fp32 / split-f16 pair plans, 4-byte elements)
+  char* at(int buf, int n0, int coff = 0) const {
+    return bufs[buf].ptr + ((size_t)n0 * bufs[buf].elems_per_image() + coff) * dtype_size(dtype);
+  }
+  float* at_f32(int buf, int n0) const { return (float*)at(buf, n0); }
   int finalize();  // allocate buffers, autotune tile configurations
   int autotune();
   ConvArgs conv_args(const ConvLayer& L, int n0, int nn) const;
   int run(const void* x, int n, int x_dtype, float* out, hipStream_t s, std::string* report = nullptr,
           const RunExtra* extra = nullptr);
   int run_range(const void* x, int i0, int i1, int x_dtype, float* out, hipStream_t s, std::string* report, const RunExtra* extra);
+  int write_report(std::vector<hipEvent_t>& prof_ev, const std::vector<int>& prof_op, int n, hipStream_t s, std::string* report) const;
   float* stem_wt = nullptr;  // IRv1: fp32 folded conv2d_1a weights + biases for the direct stem kernel (Op::STEM1)
   // activation-buffer contexts: consecutive vnf_embed calls rotate over n_ctx private buffer sets, so calls issued
   // on DIFFERENT streams may overlap on the GPU (the latency-bound tail of one batch under the throughput-bound
@@ -178,6 +224,11 @@ struct Encoder : HandleBase {
   hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr}, fork_ev = nullptr;
 };
 
+// the two report strings of an active fused stack (vnf_encoder_profile)
+const char* fused_label(const FusedStack& f);
+const char* fused_detail(const FusedStack& f);
+
+// the plan builders (plan_*.cpp)
 int build_irv1(Encoder& e, WeightMap& wm);
 int build_ir100(Encoder& e, WeightMap& wm);
 // ResNet-50 with a class head and a projection head (models/resnet_2_branch.py:12-70), 224 x 224 input

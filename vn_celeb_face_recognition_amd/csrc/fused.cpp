@@ -1,0 +1,232 @@
+// Fused stacks: runs of plan ops that one kernel replaces when the compute dtype allows it (engine.h FusedStack).
+#include "engine.h"
+#include "block35.h"
+#include "stem_mid.h"
+#include "trunk17.h"
+
+#include <cstring>
+
+namespace vnf {
+
+using Kind = FusedStack::Kind;
+
+// Fused stacks: the per-wave weight streams are gathered on the device from the packed per-convolution weights the
+// plan already uploaded (same folding, same k order), biases are concatenated per block.
+int Encoder::prepare_fused() {
+  // bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4: the five
+  // Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
+  // mixed_6a.branch1.0 inside that launch
+  const int enabled = env.fuse;
+  for (FusedStack& f : fused) {
+    f.active = false;
+    if (!enabled || (dtype != BF16 && dtype != F16 && dtype != F16P) || f.nblocks < 1 || f.nblocks > T17_MAX_BLOCKS) continue;
+    if (f.kind == Kind::StemMid) {
+      if (!(enabled & 4)) continue;
+      const ConvLayer& c2a = convs[f.conv0];
+      const ConvLayer& c2b = convs[f.conv0 + 1];
+      if (c2a.cout != 32 || c2a.K != 288 || c2b.cout != 64 || c2b.K != 288 || c2a.ncls != 1 || c2b.ncls != 1)
+        return fail(VNF_E_INVALID, "fused stem: unexpected layer shapes");
+      StemMidPack pk;
+      pk.w[0] = c2a.w; pk.kpad[0] = c2a.Kpad;
+      pk.w[1] = c2b.w; pk.kpad[1] = c2b.Kpad;
+      bool ext_ok = false;
+      if ((enabled & 8) && f.ext_conv >= 0) {
+        const ConvLayer& c3b = convs[f.ext_conv];
+        ext_ok = c3b.cout == 80 && c3b.K == 64 && c3b.KH == 1 && c3b.ncls == 1 && c3b.nseg == 1 && c3b.res_buf < 0 && c3b.act == ACT_RELU &&
+                 bufs[f.ext_out_buf].C == 80;
+      }
+      if (dtype == F16P && !ext_ok) continue;   // the planar split-f16 stem kernel (stem_mids.hip) always carries conv2d_3b
+      f.wstream = dalloc(dtype == F16P ? SMS_WFRAG_BYTES : SM_WFRAG_BYTES);
+      f.bias = (float*)dalloc(SM_BIAS * 4);
+      if (!f.wstream || !f.bias) return VNF_E_HIP;
+      VNF_HIP(hipMemcpy(f.bias, c2a.bias, 32 * 4, hipMemcpyDeviceToDevice));
+      VNF_HIP(hipMemcpy(f.bias + 32, c2b.bias, 64 * 4, hipMemcpyDeviceToDevice));
+      VNF_HIP(dtype == F16P ? stem_mids_repack(pk, f.wstream, 0) : stem_mid_repack(pk, f.wstream, 0));
+      VNF_HIP(hipDeviceSynchronize());
+      f.macs_alg = c2a.macs_alg + c2b.macs_alg;
+      f.active = true;
+      f.ext = ext_ok;
+      if (ext_ok) f.macs_alg += convs[f.ext_conv].macs_alg;
+      continue;
+    }
+    if (f.kind == Kind::Block35) {
+      if (!(enabled & 2)) continue;
+      std::vector<float> bias((size_t)f.nblocks * B35_BIAS, 0.f);
+      static const int rows[5] = {96, 32, 32, 32, 256}, ks[5] = {256, 288, 288, 288, 96}, boff[5] = {0, 96, 128, 160, 192};
+      const size_t wimg_bytes = dtype == F16P ? B35S_WIMG_BYTES : B35_WIMG_BYTES;
+      f.wstream = dalloc((size_t)f.nblocks * wimg_bytes);
+      f.bias = (float*)dalloc(bias.size() * 4);
+      if (!f.wstream || !f.bias) return VNF_E_HIP;
+      for (int b = 0; b < f.nblocks; ++b) {
+        Block35Pack pk;
+        pk.bias = f.bias + (size_t)b * B35_BIAS;
+        for (int c = 0; c < 5; ++c) {
+          const ConvLayer& L = convs[f.conv0 + 5 * b + c];
+          if (L.cout != rows[c] || L.K != ks[c] || L.ncls != 1) return fail(VNF_E_INVALID, "fused Block35: unexpected layer shapes");
+          pk.w[c] = L.w;
+          pk.kpad[c] = L.Kpad;
+          VNF_HIP(hipMemcpy(&bias[(size_t)b * B35_BIAS + boff[c]], L.bias, (size_t)rows[c] * 4, hipMemcpyDeviceToHost));
+          f.macs_alg += L.macs_alg;
+        }
+        VNF_HIP(hipMemcpy(f.bias + (size_t)b * B35_BIAS, &bias[(size_t)b * B35_BIAS], (size_t)B35_BIAS * 4, hipMemcpyHostToDevice));
+        VNF_HIP(dtype == F16P ? block35s_repack(pk, (char*)f.wstream + (size_t)b * wimg_bytes, 0)
+                              : block35_repack(pk, (char*)f.wstream + (size_t)b * wimg_bytes, 0));
+      }
+      VNF_HIP(hipDeviceSynchronize());
+      f.active = true;
+      f.stack = (enabled & 16) && dtype != F16P;
+      f.ext = false;
+      if (f.stack && (enabled & 32) && f.ext_conv >= 0) {
+        const ConvLayer& t = convs[f.ext_conv];
+        const ConvLayer& last_up = convs[f.conv0 + 5 * (f.nblocks - 1) + 4];
+        const bool ok = t.KH == 1 && t.KW == 1 && t.K == 256 && t.cout == 192 && t.ncls == 1 && t.nseg == 1 && t.res_buf < 0 &&
+                        t.act == ACT_RELU && !t.out_f32 && t.x_buf == last_up.seg[0].buf && t.x_coff == 0 &&
+                        t.seg[0].buf == f.ext_out_buf && t.seg[0].coff == 0 && bufs[f.ext_out_buf].C == 192;
+        if (ok) {
+          f.wtail = dalloc(B35_TAIL_BYTES);
+          if (!f.wtail) return VNF_E_HIP;
+          VNF_HIP(block35_tail_repack(t.w, t.Kpad, t.bias, f.wtail, 0));
+          VNF_HIP(hipDeviceSynchronize());
+          f.ext = true;
+          f.macs_alg += t.macs_alg;
+        }
+      }
+      continue;
+    }
+    if (!(enabled & 1)) continue;
+    Trunk17Pack pk;
+    memset(&pk, 0, sizeof pk);
+    pk.nblocks = f.nblocks;
+    std::vector<float> bias((size_t)f.nblocks * T17_BIAS, 0.f);
+    static const int rows[4] = {256, 128, 128, 896}, ks[4] = {896, 896, 896, 256}, boff[4] = {0, 256, 384, 512};
+    bool ok = true;
+    for (int b = 0; b < f.nblocks && ok; ++b)
+      for (int c = 0; c < 4 && ok; ++c) {
+        const ConvLayer& L = convs[f.conv0 + 4 * b + c];
+        if (L.cout != rows[c] || L.K != ks[c] || L.Kpad != ks[c] || L.ncls != 1) { ok = false; break; }
+        pk.w[b][c] = L.w;
+        pk.kpad[c] = L.Kpad;
+        VNF_HIP(hipMemcpy(&bias[(size_t)b * T17_BIAS + boff[c]], L.bias, (size_t)rows[c] * 4, hipMemcpyDeviceToHost));
+        f.macs_alg += L.macs_alg;
+      }
+    if (!ok) return fail(VNF_E_INVALID, "fused Block17 stack: unexpected layer shapes");
+    f.wstream = dalloc(dtype == F16P ? trunk17s_stream_bytes(f.nblocks) : trunk17_stream_bytes(f.nblocks));
+    f.bias = (float*)upload(bias.data(), bias.size() * 4);
+    if (!f.wstream || !f.bias) return VNF_E_HIP;
+    VNF_HIP(dtype == F16P ? trunk17s_repack(pk, f.wstream, 0) : trunk17_repack(pk, f.wstream, 0));
+    VNF_HIP(hipDeviceSynchronize());
+    f.active = true;
+  }
+  return VNF_OK;
+}
+
+// A tap's buffer exists in memory unless every op that writes it sits inside an active fused stack and the stack's own
+// kernel does not produce it (conv2d_2a / conv2d_2b / maxpool_3a with the fused stem: those tensors only ever live in LDS).
+bool Encoder::buf_materialised(int buf) const {
+  for (const FusedStack& f : fused) {
+    if (!f.active) continue;
+    bool written = false;
+    for (int oi = f.first; oi < f.end(); ++oi) {
+      const Op& op = ops[oi];
+      if (op.kind == Op::CONV) {
+        const ConvLayer& L = convs[op.layer];
+        for (int i = 0; i < L.nseg; ++i) written |= L.seg[i].buf == buf;
+      } else if (op.kind == Op::MAXPOOL || op.kind == Op::MAXPOOLC) {
+        written |= op.dst == buf;
+      }
+    }
+    if (!written) continue;
+    bool produced = false;
+    switch (f.kind) {
+      case Kind::StemMid: produced = buf == (f.ext ? f.ext_out_buf : f.out_buf); break;
+      case Kind::Block35:
+        for (int b = 0; b < f.nblocks; ++b) produced |= convs[f.conv0 + 5 * b + 4].seg[0].buf == buf;
+        produced |= f.ext && buf == f.ext_out_buf;
+        break;
+      case Kind::Block17: produced = buf == f.out_buf; break;
+    }
+    if (!produced) return false;
+  }
+  return true;
+}
+
+// One launch of the stack's kernel (one per block for Block35 without `stack`) on images [n0, n0 + nn): what run_range
+// does in place of ops [first, end()).
+int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
+  hipError_t err = hipSuccess;
+  const char* what = "";
+  switch (f.kind) {
+    case Kind::StemMid: {
+      const int out = f.ext ? f.ext_out_buf : f.out_buf;
+      StemMidArgs sa;
+      sa.x = at(f.in_buf, n0); sa.ldx = bufs[f.in_buf].C;
+      sa.y = at(out, n0); sa.ldy = bufs[out].C;
+      sa.n = nn;
+      sa.wfrag = f.wstream; sa.bias = f.bias;
+      sa.w3b = nullptr; sa.b3b = nullptr; sa.k3b_pad = 0;
+      if (f.ext) {
+        const ConvLayer& c3b = convs[f.ext_conv];
+        sa.w3b = c3b.w; sa.b3b = c3b.bias; sa.k3b_pad = c3b.Kpad;
+      }
+      what = "fused stem";
+      err = dtype == F16P ? launch_stem_mids(sa, s) : launch_stem_mid(sa, dtype, s);
+      break;
+    }
+    case Kind::Block35:
+      if (f.stack) {
+        const int in = convs[f.conv0 + 4].res_buf;                                // first block's input
+        const int out = convs[f.conv0 + 5 * (f.nblocks - 1) + 4].seg[0].buf;      // last block's output
+        Block35StackArgs ba;
+        ba.x = at(in, n0); ba.ldx = bufs[in].C;
+        ba.y = at(out, n0); ba.ldy = bufs[out].C;
+        ba.n = nn; ba.nblocks = f.nblocks;
+        ba.wimg = f.wstream;
+        if (f.ext) {
+          ba.wtail = f.wtail;
+          ba.ytail = at(f.ext_out_buf, n0);
+          ba.ldyt = bufs[f.ext_out_buf].C;
+        }
+        what = "fused Block35 stack";
+        err = launch_block35_stack(ba, dtype, s);
+        break;
+      }
+      what = "fused Block35";
+      for (int b = 0; b < f.nblocks && err == hipSuccess; ++b) {
+        const ConvLayer& up = convs[f.conv0 + 5 * b + 4];   // residual source = block input, segment 0 = block output
+        Block35Args ba;
+        ba.x = at(up.res_buf, n0); ba.ldx = bufs[up.res_buf].C;
+        ba.y = at(up.seg[0].buf, n0); ba.ldy = bufs[up.seg[0].buf].C;
+        ba.n = nn;
+        ba.wimg = (const char*)f.wstream + (size_t)b * (dtype == F16P ? B35S_WIMG_BYTES : B35_WIMG_BYTES);
+        ba.zero = conv_zero_page();
+        err = dtype == F16P ? launch_block35s(ba, s) : launch_block35(ba, dtype, s);
+      }
+      break;
+    case Kind::Block17: {
+      Trunk17Args ta;
+      ta.x = at(f.in_buf, n0); ta.ldx = bufs[f.in_buf].C;
+      ta.y = at(f.out_buf, n0); ta.ldy = bufs[f.out_buf].C;
+      ta.n = nn; ta.nblocks = f.nblocks;
+      ta.wstream = f.wstream; ta.bias = f.bias;
+      what = "fused Block17 stack";
+      err = dtype == F16P ? launch_trunk17s(ta, s) : launch_trunk17(ta, dtype, s);
+      break;
+    }
+  }
+  return err == hipSuccess ? VNF_OK : fail(VNF_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
+}
+
+const char* fused_label(const FusedStack& f) {
+  if (f.kind == Kind::StemMid) return f.ext ? "conv2d_2a+2b+maxpool_3a+3b" : "conv2d_2a+2b+maxpool_3a";
+  return f.kind == Kind::Block35 ? "repeat_1 (fused blocks)" : "repeat_2 (persistent trunk)";
+}
+
+const char* fused_detail(const FusedStack& f) {
+  if (f.kind == Kind::StemMid) return "rolling rows, one launch, one workgroup per image";
+  if (f.kind == Kind::Block17) return "10 x Block17 in one launch, one workgroup per image";
+  if (!f.stack) return "5 x Block35, one launch per block, one workgroup per image";
+  return f.ext ? "5 x Block35 + mixed_6a.branch1.0 in one launch, x in registers"
+               : "5 x Block35 in one launch, x in registers, one workgroup per image";
+}
+
+}  // namespace vnf

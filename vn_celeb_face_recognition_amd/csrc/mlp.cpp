@@ -3,11 +3,13 @@
 //   dense_1 (512->2048) + ReLU and dense_2 (2048->C) run on the exact-f32 MFMA GEMM core
 //   (a linear layer is a 1x1 convolution over a 1x1 image), then one wave per face does
 //   log_softmax, argmax and exp.
-#include "engine.h"
+#include "plan.h"
 
 namespace vnf {
 
 struct Mlp : HandleBase {
+  static constexpr HandleKind KIND = HandleKind::Mlp;
+  Mlp() : HandleBase(KIND) {}
   Encoder enc;  // owns the packed layers and the three activation buffers
   int input_dim = 0, num_classes = 0, cpad = 0, max_batch = 0;
   int b_in = -1, b_h = -1, b_logit = -1;
@@ -17,9 +19,6 @@ struct Mlp : HandleBase {
   hipEvent_t done = nullptr;
   ~Mlp() override { if (done) (void)hipEventDestroy(done); }
 };
-
-int add_linear(Encoder& e, const std::string& name, const float* w, const float* b, int cin, int cout, int cout_pad,
-               int x_buf, int o_buf, int act);
 
 }  // namespace vnf
 using namespace vnf;
@@ -37,11 +36,10 @@ extern "C" int vnf_mlp_create(const vnf_tensor_desc* weights, int n_weights, int
     const float* b2 = wm.get("dense_2.bias", num_classes);
     if (!w1 || !b1 || !w2 || !b2) return fail(VNF_E_MISSING, "vnf_mlp_create: missing weight: " + wm.missing);
     Mlp* m = new Mlp();
-    m->kind = 2;
     m->input_dim = input_dim; m->num_classes = num_classes; m->max_batch = max_batch;
     m->cpad = (num_classes + 7) / 8 * 8;
     Encoder& e = m->enc;
-    e.dtype = F32; e.max_batch = max_batch; e.in_size = 1; e.arch = -1;
+    e.dtype = F32; e.max_batch = max_batch; e.in_size = 1; e.arch = ARCH_MLP;
     m->b_in = e.add_buf(1, 1, input_dim);
     m->b_h = e.add_buf(1, 1, 2048);
     m->b_logit = e.add_buf(1, 1, m->cpad);
@@ -60,9 +58,8 @@ extern "C" int vnf_mlp_create(const vnf_tensor_desc* weights, int n_weights, int
 extern "C" int vnf_classify(vnf_handle h, const float* emb, int f, float* logp_out, int32_t* argmax_out, float* prob_out,
                             void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 2) return fail(VNF_E_INVALID, "not an MLP handle");
-    Mlp* m = static_cast<Mlp*>(hb);
+    Mlp* m = handle_cast<Mlp>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MLP handle");
     if (f < 0 || f > m->max_batch) return fail(VNF_E_CAPACITY, "vnf_classify: batch exceeds max_batch");
     if (f == 0) return VNF_OK;
     if (!emb) return fail(VNF_E_INVALID, "vnf_classify: bad argument");

@@ -183,6 +183,8 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 struct MlpTrainer : HandleBase {
+  static constexpr HandleKind KIND = HandleKind::MlpTrainer;
+  MlpTrainer() : HandleBase(KIND) {}
   int D = 0, C = 0, H = 2048, max_batch = 0;
   long long step = 0;
   float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 0.f;
@@ -219,7 +221,6 @@ extern "C" int vnf_mlp_trainer_create(const vnf_tensor_desc* weights, int n_weig
     *out = nullptr;
     WeightMap wm(weights, n_weights);
     MlpTrainer* t = new MlpTrainer();
-    t->kind = 4;
     t->D = input_dim; t->C = num_classes; t->max_batch = max_batch;
     t->b1 = beta1; t->b2 = beta2; t->eps = eps; t->wd = weight_decay;
     (void)hipGetDevice(&t->device);
@@ -255,16 +256,11 @@ extern "C" int vnf_mlp_trainer_create(const vnf_tensor_desc* weights, int n_weig
   }
 }
 
-static MlpTrainer* as_trainer(vnf_handle h) {
-  HandleBase* b = reinterpret_cast<HandleBase*>(h);
-  return (b && b->kind == 4) ? static_cast<MlpTrainer*>(b) : nullptr;
-}
-
 // forward (+ loss / hits); train != 0: backward + Adam step with learning rate lr.
 extern "C" int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t* target, int b, const float* dropout_mask, float lr,
                                   int train, float* loss_out, int32_t* hits_out, void* stream) {
   try {
-    MlpTrainer* t = as_trainer(h);
+    MlpTrainer* t = handle_cast<MlpTrainer>(h);
     if (!t) return fail(VNF_E_INVALID, "not an MLP trainer handle");
     if (b <= 0 || b > t->max_batch) return fail(VNF_E_CAPACITY, "vnf_mlp_train_step: batch exceeds max_batch");
     if (!emb || !target) return fail(VNF_E_INVALID, "vnf_mlp_train_step: bad argument");
@@ -316,7 +312,7 @@ static float* trainer_buf(MlpTrainer* t, const char* name, int kind, size_t* num
 }
 
 extern "C" int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel) {
-  MlpTrainer* t = as_trainer(h);
+  MlpTrainer* t = handle_cast<MlpTrainer>(h);
   if (!t) return fail(VNF_E_INVALID, "not an MLP trainer handle");
   size_t n = 0;
   float* src = trainer_buf(t, name, kind, &n);
@@ -327,7 +323,7 @@ extern "C" int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, flo
 }
 
 extern "C" int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel) {
-  MlpTrainer* t = as_trainer(h);
+  MlpTrainer* t = handle_cast<MlpTrainer>(h);
   if (!t) return fail(VNF_E_INVALID, "not an MLP trainer handle");
   size_t n = 0;
   float* dst = trainer_buf(t, name, kind, &n);
@@ -338,7 +334,7 @@ extern "C" int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, con
 }
 
 extern "C" int vnf_mlp_trainer_step_count(vnf_handle h, int64_t* step_io, int set) {
-  MlpTrainer* t = as_trainer(h);
+  MlpTrainer* t = handle_cast<MlpTrainer>(h);
   if (!t || !step_io) return fail(VNF_E_INVALID, "not an MLP trainer handle");
   if (set) t->step = *step_io; else *step_io = t->step;
   return VNF_OK;

@@ -10,15 +10,17 @@
 // bit-identical to the fp32 numpy / torch-CPU statements of the oracle.
 //
 // Kernel map:
-//   K1 pyramid_kernel        u8 frame -> all pyramid levels (adaptive-average bins, normalised)
+//   K1 pyramid_rows_kernel   u8 frame -> all pyramid levels (adaptive-average bins, normalised); pyramid_kernel is its
+//      fallback for frames whose rows or base address are not 16-byte aligned, or whose rows exceed 64 KiB of LDS as fp32
 //   K2 pnet_conv1_pool_direct / pnet_conv2 / pnet_conv3_heads   (all levels and frames per launch)
 //   K3 threshold + compaction fused into pnet_conv3_heads (wave-aggregated atomic slots;
 //      order restored by the sort keys, which carry the cell index)
 //   K4 nms_scale_kernel (per level x frame, IoU 0.5), nms_image_kernel (per frame, IoU 0.7,
 //      + regress, rerec, pad), stage2_post_kernel (IoU 0.7 + bbreg + rerec + pad)
-//   K5 crop_resize_kernel    box table -> N x 3 x {24,48}^2 (area bins, also up-sampling)
+//   K5 crop_resize_rows_kernel   box table -> N x 3 x {24,48}^2 (area bins, also up-sampling); crop_resize_kernel is
+//      its fallback for unaligned frames
 //   K6 net_front_kernel (conv1 + pool1), net_mid_kernel (conv2 + pool2), then the rest of R-Net / O-Net as MFMA plans
-//      of the conv core (engine.cpp build_rnet / build_onet) over the dense batch of all frames' candidates
+//      of the conv core (plan_mtcnn.cpp build_rnet / build_onet) over the dense batch of all frames' candidates
 //   K7 stage3_post_kernel    landmarks, bbreg, "Min" NMS, area-descending order
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -1171,6 +1173,8 @@ constexpr int LDS_RFRONT = (25 * 24 + 22 * 22 * 8) * 16, LDS_OFRONT = (11 * 48 +
 constexpr int LDS_RMID = 11 * 11 * 128 + 9 * 9 * 12 * 16, LDS_OMID = 23 * 23 * 128 + 21 * 21 * 8 * 16;
 
 struct Mtcnn : HandleBase {
+  static constexpr HandleKind KIND = HandleKind::Mtcnn;
+  Mtcnn() : HandleBase(KIND) {}
   vnf_mtcnn_cfg cfg;
   PNetW pw;
   LevelTable cap_table;  // geometry at (max_height, max_width): sizes the buffers
@@ -1295,7 +1299,6 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
       return fail(VNF_E_INVALID, "vnf_mtcnn_create: bad configuration");
     *out = nullptr;
     Mtcnn* m = new Mtcnn();
-    m->kind = 3;
     m->cfg = *cfg;
     (void)hipGetDevice(&m->device);
     WeightMap wp(pnet, n_pnet), wr(rnet, n_rnet), wo(onet, n_onet);
@@ -1326,7 +1329,7 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
       m->renc = new Encoder();
       m->renc->max_streams = 1;  // the detector shares the GPU with the embedding stream: no forks of its own
       m->renc->tune_batch = std::max(1, m->r_cap / 2);  // typical stage-2 load, not the capacity
-      m->renc->kind = 1; m->renc->arch = -2; m->renc->dtype = plans_f32 ? F32 : F16X2; m->renc->max_batch = m->r_cap;
+      m->renc->arch = ARCH_RNET; m->renc->dtype = plans_f32 ? F32 : F16X2; m->renc->max_batch = m->r_cap;
       auto pack_front = [&](WeightMap& wm, int cout, FrontW& fw) -> bool {
         const float* c1 = wm.get("conv1.weight", (int64_t)cout * 27);
         const float* b1 = wm.get("conv1.bias", cout);
@@ -1379,7 +1382,7 @@ extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const v
       m->oenc = new Encoder();
       m->oenc->max_streams = 1;
       m->oenc->tune_batch = std::max(1, m->o_cap / 4);
-      m->oenc->kind = 1; m->oenc->arch = -3; m->oenc->dtype = m->renc->dtype; m->oenc->max_batch = m->o_cap;
+      m->oenc->arch = ARCH_ONET; m->oenc->dtype = m->renc->dtype; m->oenc->max_batch = m->o_cap;
       if (rr == VNF_OK) rr = build_onet(*m->oenc, wo, m->mid);
       if (rr == VNF_OK) rr = m->oenc->finalize();
       if (rr != VNF_OK) { delete m; return rr; }
@@ -1551,14 +1554,17 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
   mark("nms_stage1", 0);
   const int ncnt = cfg.max_batch * 3 + 16;
   int* const h = m->h_pin;  // pinned: the copy is a true async DMA, the only wait is the stream synchronisation
-  auto read_counts = [&]() -> int {
-    VNF_HIP(hipMemcpyAsync(h, m->row_cnt, (size_t)ncnt * 4, hipMemcpyDeviceToHost, s));
-    VNF_HIP(hipStreamSynchronize(s));
+  auto check_overflow = [&]() -> int {   // after a read-back into h: did a stage-1 list outgrow its table?
     const int st = h[cfg.max_batch * 3];
     if (st & (ST_OVER_SCALE | ST_OVER_IMG | ST_OVER_KEEP))
       return fail(VNF_E_CAPACITY, "mtcnn: candidate table overflow (status " + std::to_string(st) + "): a frame has more than " +
                                   std::to_string(m->keep) + " stage-1 survivors; raise vnf_mtcnn_cfg.max_candidates");
     return VNF_OK;
+  };
+  auto read_counts = [&]() -> int {
+    VNF_HIP(hipMemcpyAsync(h, m->row_cnt, (size_t)ncnt * 4, hipMemcpyDeviceToHost, s));
+    VNF_HIP(hipStreamSynchronize(s));
+    return check_overflow();
   };
   // ---- stages 2 and 3 as launch sequences sized by (largest per-frame candidate count, total candidates): every kernel
   // reads the true counts from device memory and leaves early past them, so any UPPER bound gives the exact result (the
@@ -1631,11 +1637,7 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
     VNF_HIP(hipMemcpyAsync(h, m->stage, ((size_t)ncnt + (size_t)B * FIN_FAST * 15) * 4, hipMemcpyDeviceToHost, s));
     VNF_HIP(hipStreamSynchronize(s));
     mark("readback", 0);
-    const int st = h[cfg.max_batch * 3];
-    if (st & (ST_OVER_SCALE | ST_OVER_IMG | ST_OVER_KEEP))
-      return fail(VNF_E_CAPACITY, "mtcnn: candidate table overflow (status " + std::to_string(st) + "): a frame has more than " +
-                                  std::to_string(m->keep) + " stage-1 survivors; raise vnf_mtcnn_cfg.max_candidates");
-    return VNF_OK;
+    return check_overflow();
   };
   auto counts_of = [&](int base, int& mx, int& tot) {
     mx = tot = 0;
@@ -1707,10 +1709,9 @@ static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipSt
 extern "C" int vnf_mtcnn_detect(vnf_handle h, const uint8_t* frames, int b, int height, int width, int32_t* counts,
                                 float* boxes, float* probs, float* points, int max_out, int32_t* n_out, void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 3) return fail(VNF_E_INVALID, "not an MTCNN handle");
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
     if (!frames || b <= 0 || !counts || !n_out) return fail(VNF_E_INVALID, "vnf_mtcnn_detect: bad argument");
-    Mtcnn* m = static_cast<Mtcnn*>(hb);
     std::vector<int> cnt;
     std::vector<float> fin;
     int r = mtcnn_run(m, frames, b, height, width, (hipStream_t)stream, cnt, fin);
@@ -1738,10 +1739,9 @@ extern "C" int vnf_mtcnn_detect(vnf_handle h, const uint8_t* frames, int b, int 
 extern "C" int vnf_mtcnn_stage_times(vnf_handle h, const uint8_t* frames, int b, int height, int width, char* report,
                                      int64_t capacity, void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 3) return fail(VNF_E_INVALID, "not an MTCNN handle");
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
     if (!frames || b <= 0 || !report || capacity <= 0) return fail(VNF_E_INVALID, "vnf_mtcnn_stage_times: bad argument");
-    Mtcnn* m = static_cast<Mtcnn*>(hb);
     std::vector<int> cnt;
     std::vector<float> fin;
     StageProf prof;
@@ -1766,9 +1766,8 @@ extern "C" int vnf_mtcnn_stage_times(vnf_handle h, const uint8_t* frames, int b,
 
 extern "C" int vnf_mtcnn_results_device(vnf_handle h, int32_t* frame_idx, float* boxes, float* probs, float* points,
                                         int max_out, void* stream) {
-  HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-  if (!hb || hb->kind != 3) return fail(VNF_E_INVALID, "not an MTCNN handle");
-  Mtcnn* m = static_cast<Mtcnn*>(hb);
+  Mtcnn* m = handle_cast<Mtcnn>(h);
+  if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
   if (max_out < 0) return fail(VNF_E_INVALID, "vnf_mtcnn_results_device: bad argument");
   if (m->last_b == 0 || max_out == 0) return VNF_OK;  // the last detection found nothing
   hipLaunchKernelGGL(results_device_kernel, dim3(m->last_b), dim3(64), 0, (hipStream_t)stream, m->fin, m->fin_cnt, max_out, m->keep,
@@ -1784,10 +1783,9 @@ extern "C" int vnf_mtcnn_results_device(vnf_handle h, int32_t* frame_idx, float*
 extern "C" int vnf_mtcnn_debug_stage3(vnf_handle h, const float* boxes, const float* onet_out, int n, float* fin_out,
                                       int max_out, int32_t* n_out, void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 3) return fail(VNF_E_INVALID, "not an MTCNN handle");
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
     if (!boxes || !onet_out || n < 0 || !fin_out || !n_out) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_stage3: bad argument");
-    Mtcnn* m = static_cast<Mtcnn*>(hb);
     if (n > m->keep) return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_stage3: more rows than the handle's tables hold");
     hipStream_t s = (hipStream_t)stream;
     std::vector<Row> rows((size_t)std::max(n, 1));
@@ -1820,9 +1818,8 @@ extern "C" int vnf_mtcnn_debug_stage3(vnf_handle h, const float* boxes, const fl
 extern "C" int vnf_mtcnn_debug_pnet(vnf_handle h, const uint8_t* frames, int height, int width, int level,
                                     float* level_out, float* prob_out, float* reg_out, int32_t dims[4], void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 3) return fail(VNF_E_INVALID, "not an MTCNN handle");
-    Mtcnn* m = static_cast<Mtcnn*>(hb);
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
     LevelTable t = make_levels(height, width, m->cfg.min_face_size, (double)m->cfg.factor);
     if (level < 0 || level >= t.n) return fail(VNF_E_INVALID, "no such level");
     float *pd = nullptr, *rd = nullptr;

@@ -1,6 +1,6 @@
 // RetinaFace detector (mobilenet0.25 backbone) on the device: /root/reference/models/retina_face.py:56-232 --
 // the network (MobileNetV1-0.25 body, FPN, 3 x SSH, class / bbox / landmark heads: retina_face_utils/components.py) runs as a
-// plan on the exact-f32 MFMA core (engine.cpp build_retina_mnet); this file holds what surrounds it:
+// plan on the exact-f32 MFMA core (plan_retina.cpp build_retina_mnet); this file holds what surrounds it:
 //
 //   retina_prep_kernel     u8 RGB frames -> NHWC4 fp32, channel means (104, 117, 123) subtracted (retina_face.py:158-164)
 //   retina_score_kernel    softmax over the 2 classes of every anchor, threshold conf_thres, compaction (191-195)
@@ -162,6 +162,8 @@ __global__ void __launch_bounds__(256) retina_select_kernel(RetinaGeom g, const 
 }
 
 struct Retina : HandleBase {
+  static constexpr HandleKind KIND = HandleKind::Retina;
+  Retina() : HandleBase(KIND) {}
   vnf_retina_cfg cfg;
   Encoder* enc = nullptr;
   bool layers = false;   // VNF_RETINA_LAYERS (diagnostic): per-layer table of the plan on stderr
@@ -204,7 +206,6 @@ extern "C" int vnf_retina_create(const vnf_tensor_desc* weights, int n_weights, 
       return fail(VNF_E_INVALID, "vnf_retina_create: bad configuration (keep_top_k <= 768, frames >= 32 px)");
     *out = nullptr;
     Retina* r = new Retina();
-    r->kind = 5;
     r->cfg = *cfg;
     r->layers = getenv("VNF_RETINA_LAYERS") != nullptr;
     (void)hipGetDevice(&r->device);
@@ -215,7 +216,7 @@ extern "C" int vnf_retina_create(const vnf_tensor_desc* weights, int n_weights, 
       delete r;
       return fail(VNF_E_INVALID, "vnf_retina_create: compute_dtype must be VNF_F32 or VNF_F16X2");
     }
-    e.kind = 1; e.arch = -5; e.dtype = cfg->compute_dtype == VNF_F16X2 ? F16X2 : F32; e.max_batch = cfg->max_batch; e.max_streams = 1;
+    e.arch = ARCH_RETINA; e.dtype = cfg->compute_dtype == VNF_F16X2 ? F16X2 : F32; e.max_batch = cfg->max_batch; e.max_streams = 1;
     int rc = build_retina_mnet(e, wm, cfg->height, cfg->width, r->head_bufs);
     if (rc == VNF_OK) rc = e.finalize();
     if (rc != VNF_OK) { delete r; return rc; }
@@ -252,9 +253,8 @@ extern "C" int vnf_retina_create(const vnf_tensor_desc* weights, int n_weights, 
 extern "C" int vnf_retina_detect(vnf_handle h, const uint8_t* frames, int b, int height, int width, int32_t* counts, float* boxes,
                                  float* probs, float* points, int max_out, int32_t* n_out, void* stream) {
   try {
-    HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-    if (!hb || hb->kind != 5) return fail(VNF_E_INVALID, "not a RetinaFace handle");
-    Retina* r = static_cast<Retina*>(hb);
+    Retina* r = handle_cast<Retina>(h);
+    if (!r) return fail(VNF_E_INVALID, "not a RetinaFace handle");
     if (!frames || b <= 0 || !counts || !n_out) return fail(VNF_E_INVALID, "vnf_retina_detect: bad argument");
     if (b > r->cfg.max_batch || height != r->cfg.height || width != r->cfg.width)
       return fail(VNF_E_CAPACITY, "vnf_retina_detect: the handle was created for another frame size / batch");
@@ -313,9 +313,8 @@ extern "C" int vnf_retina_detect(vnf_handle h, const uint8_t* frames, int b, int
 
 extern "C" int vnf_retina_results_device(vnf_handle h, int32_t* frame_idx, float* boxes, float* probs, float* points, int max_out,
                                          void* stream) {
-  HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-  if (!hb || hb->kind != 5) return fail(VNF_E_INVALID, "not a RetinaFace handle");
-  Retina* r = static_cast<Retina*>(hb);
+  Retina* r = handle_cast<Retina>(h);
+  if (!r) return fail(VNF_E_INVALID, "not a RetinaFace handle");
   if (max_out < 0) return fail(VNF_E_INVALID, "vnf_retina_results_device: bad argument");
   if (r->last_b == 0 || max_out == 0) return VNF_OK;
   hipLaunchKernelGGL(retina_results_kernel, dim3(r->last_b), dim3(64), 0, (hipStream_t)stream, r->fin, r->fin_cnt, max_out, frame_idx,
@@ -326,9 +325,8 @@ extern "C" int vnf_retina_results_device(vnf_handle h, int32_t* frame_idx, float
 
 // staged parity: raw head outputs of pyramid level `level` of the last detection as a host (b, fh, fw, 32) fp32 array
 extern "C" int vnf_retina_debug_heads(vnf_handle h, int level, int b, float* host_out, int64_t capacity, int32_t dims[2]) {
-  HandleBase* hb = reinterpret_cast<HandleBase*>(h);
-  if (!hb || hb->kind != 5 || level < 0 || level > 2) return fail(VNF_E_INVALID, "vnf_retina_debug_heads: bad argument");
-  Retina* r = static_cast<Retina*>(hb);
+  Retina* r = handle_cast<Retina>(h);
+  if (!r || level < 0 || level > 2) return fail(VNF_E_INVALID, "vnf_retina_debug_heads: bad argument");
   const Buf& bf = r->enc->bufs[r->head_bufs[level]];
   if (dims) { dims[0] = bf.H; dims[1] = bf.W; }
   const int64_t total = (int64_t)b * bf.H * bf.W * 32;
