@@ -236,11 +236,12 @@ int build_rn50_2b(Encoder& e, WeightMap& wm, int num_classes, int num_projection
 // RetinaFace (mobilenet0.25) on the exact-f32 core for an H x W input: buffer 0 = NHWC4 mean-subtracted input (written by
 // the caller), head_bufs[l] = (Hl, Wl, 32) fp32 [cls 4 | bbox 8 | landmark 20] of pyramid level l
 int build_retina_mnet(Encoder& e, WeightMap& wm, int H, int W, int head_bufs[3]);
-// MTCNN R-Net / O-Net as MFMA plans (exact-f32 or split-f16) over NHWC4 candidate crops (input buffer 0 is written by
-// the crop kernel, conv1 + pool1 by the detector's net_front_kernel into buffer 1, with mid conv2 + pool2 by its
-// net_mid_kernel into buffer 3; the last buffer holds the head outputs: 8 floats [a0,a1,reg0..3,-,-] / 16 floats
-// [a0,a1,reg0..3,lm0..9])
-int build_rnet(Encoder& e, WeightMap& wm, bool mid);
-int build_onet(Encoder& e, WeightMap& wm, bool mid);
+// MTCNN R-Net / O-Net as MFMA plans (exact-f32 or split-f16) over NHWC4 candidate crops.  The detector touches four of a
+// plan's buffers, named in `nb`: `crops` is written by its crop kernel, `pooled1` (conv1 + pool1) by its net_front_kernel,
+// with mid `pooled2` (conv2 + pool2) by its net_mid_kernel, and `heads` holds the outputs: 8 floats [a0,a1,reg0..3,-,-] /
+// 16 floats [a0,a1,reg0..3,lm0..9]
+struct NetBufs { int crops, pooled1, pooled2, heads; };
+int build_rnet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb);
+int build_onet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb);
 
 }  // namespace vnf

@@ -22,52 +22,21 @@
 //   K6 net_front_kernel (conv1 + pool1), net_mid_kernel (conv2 + pool2), then the rest of R-Net / O-Net as MFMA plans
 //      of the conv core (plan_mtcnn.cpp build_rnet / build_onet) over the dense batch of all frames' candidates
 //   K7 stage3_post_kernel    landmarks, bbreg, "Min" NMS, area-descending order
+//
+// The host layer (handle, create, the cascade's control, the C ABI) is mtcnn_host.cpp; it reaches these kernels through the
+// launchers at the end of this file, declared in mtcnn.h with the types both sides share.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include <algorithm>
-#include <cstring>
-#include <cmath>
-#include <vector>
-
-#include "engine.h"
+#include "conv_device.h"
+#include "mtcnn.h"
 #include "nms_device.h"
 #include "split_f16.h"
 
 namespace vnf {
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
-
-constexpr int MAX_LEVELS = 24;
-// Candidate tables.  Stage 1 is sized by the pyramid itself: every (level, frame) list has room for all cells of the
-// level, so it cannot overflow.  The stage-2 / stage-3 tables hold `keep` rows per frame, a RUN-TIME capacity
-// (vnf_mtcnn_cfg.max_candidates, default KEEP).  The NMS kernels keep their sort keys and kept boxes in LDS while a
-// list fits the constants below and switch to global-memory scratch beyond them -- the reference has no cap at all
-// (detect_face.py:79-93,203-218) and neither has the arithmetic here; only the row tables of stages 2 / 3 are bounded,
-// by a capacity the caller can raise (the host layer grows it and retries on VNF_E_CAPACITY).
-constexpr int CAP_LDS_KEYS = 8192;   // sort keys held in LDS by the stage-1 NMS kernels
-constexpr int KEEP = 2048;           // kept boxes / post-kernel keys held in LDS; default rows per frame of the stage tables
-
-
-struct LevelDesc {
-  int Hs, Ws, Hp, Wp, H2, W2, oh, ow;
-  float scale;
-  int off_px, off_p1, off_c2, off_out;  // prefix offsets (in pixels of that stage) over levels
-};
-
-struct LevelTable {
-  int n;
-  int tot_px, tot_p1, tot_c2, tot_out;
-  LevelDesc l[MAX_LEVELS];
-};
-
-struct PNetW {  // transposed to [cin][3][3][cout] so one tap's output-channel weights are contiguous
-  const float *w1, *b1, *a1, *w2, *b2, *a2, *w3, *b3, *a3, *w41, *b41, *w42, *b42;
-};
-
-struct Cand { float score, r0, r1, r2, r3; int cell; };
-struct Row { float x1, y1, x2, y2, score; int y, ey, x, ex; };  // stage-2 / stage-3 table row
 
 __device__ __forceinline__ int find_level(const LevelTable& t, int idx, int which) {
   int l = 0;
@@ -395,14 +364,6 @@ __device__ __forceinline__ float4 cell_box(int cell, int ow, float scale) {
 // --------------------------------------------------------------------------------------------- K4a
 // detect_face.py:79: batched_nms(..., 0.5) within each (scale, image).  Visiting order = stable
 // score-descending over nonzero() order (y, x): key = (inverted score | cell | slot).
-// global-memory fallback of the NMS kernels (per frame `stride` entries; a level's region starts at its off_out)
-struct NmsScratch {
-  unsigned long long* keys;
-  float4* kbox;
-  int* keep;
-  float4* reg;
-  int stride;
-};
 
 template <bool KEYS_G, bool KEPT_G>
 __device__ __forceinline__ void nms_scale_body(const Cand* __restrict__ cd, const int* __restrict__ cl, int n, int ow, float scale,
@@ -760,7 +721,6 @@ __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __
 // (weights stay in registers), the PReLU outputs are parked in LDS as [pixel][32] with the 16-byte chunk index
 // XOR-swizzled by the pixel, and the pooled rows are reduced from there and written as whole NHWC rows.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-struct FrontW { const float* w; const float* b; const float* a; };   // [32][9 taps][4 channels (3 + zero)], [32], [32]
 
 __device__ __forceinline__ float split_pack(float v) {
   const sf16 h(v);
@@ -899,7 +859,6 @@ __global__ void __launch_bounds__(NT) net_front_kernel(const float* __restrict__
 // values: the same up to the split format's 2^-22 rounding; detections agree to 1e-3 px / 1e-6, tested).  The unfused plan wrote and re-read that map (O-Net: 99 MB
 // per 880 candidates) and paid two launches: 0.089 + 0.029 ms (O-Net), 0.057 + 0.017 ms (R-Net) per 16 frames.
 typedef _Float16 f16x8m_t __attribute__((ext_vector_type(8)));
-struct MidW { const uint4* w; const float* b; const float* a; };   // [CO/16][18][64 lanes] fragments, [CO], [CO]
 
 template <int PI, int CO, int NWAVE, int NPASS>
 __global__ void __launch_bounds__(NWAVE * 64) net_mid_kernel(const float* __restrict__ p1, MidW mw, float* __restrict__ p2) {
@@ -1163,56 +1122,6 @@ __global__ void __launch_bounds__(256) stage3_post_kernel(const Row* __restrict_
   else stage3_post_body<true>(r, oo, n0, thr_score, thr_nms, select_largest, g.keys + gb, g.kbox + gb, g.keep + gb, g.reg + gb, s_cbox, s_alive, fo, fin_cnt + img, status);
 }
 
-// =============================================================================================
-// host side
-constexpr int FIN_FAST = 32;  // faces per frame covered by the one-copy read-back (VNF_FIN_FAST lowers it: test hook)
-// dynamic LDS (bytes) of the launches that take some: the NMS kernels of stage 1, the post kernels of stages 2 / 3, the
-// fronts ((crop rows of a band * S + conv rows of a band * C * 8) float4) and the mids (input map + conv map)
-constexpr int LDS_NMS = CAP_LDS_KEYS * 8 + KEEP * 20 + 256 * 20, LDS_POST = KEEP * 44 + 256 * 20;
-constexpr int LDS_RFRONT = (25 * 24 + 22 * 22 * 8) * 16, LDS_OFRONT = (11 * 48 + 9 * 46 * 8) * 16;
-constexpr int LDS_RMID = 11 * 11 * 128 + 9 * 9 * 12 * 16, LDS_OMID = 23 * 23 * 128 + 21 * 21 * 8 * 16;
-
-struct Mtcnn : HandleBase {
-  static constexpr HandleKind KIND = HandleKind::Mtcnn;
-  Mtcnn() : HandleBase(KIND) {}
-  vnf_mtcnn_cfg cfg;
-  PNetW pw;
-  LevelTable cap_table;  // geometry at (max_height, max_width): sizes the buffers
-  float *lvl = nullptr, *p1 = nullptr, *c2 = nullptr;
-  Cand* cand = nullptr;                       // stage-1 records, dense by cell: [frame][cap_out]
-  int *cells = nullptr, *keep1c = nullptr;    // per (level, frame) compact cell lists: P-Net hits / per-scale NMS survivors
-  int keep = KEEP;                            // rows per frame of the stage-2 / stage-3 tables (vnf_mtcnn_cfg.max_candidates)
-  NmsScratch scratch{};                       // global-memory fallback of the NMS kernels
-  int *cand_cnt = nullptr, *keep1_cnt = nullptr, *row_cnt = nullptr, *row3_cnt = nullptr, *fin_cnt = nullptr, *status = nullptr;
-  Row *rows = nullptr, *rows3 = nullptr;
-  float *rout = nullptr, *oout = nullptr, *fin = nullptr;
-  float *prob_dbg = nullptr, *reg_dbg = nullptr;
-  Encoder *renc = nullptr, *oenc = nullptr;  // R-Net / O-Net plans on the MFMA core (candidates = batch)
-  int* row_order = nullptr;                   // pyramid dispatch order (device), rebuilt when the frame size changes
-  int row_order_h = 0, row_order_w = 0, row_order_cap = 0;
-  FrontW rfw{}, ofw{};                        // conv1 + PReLU + pool1 of both nets by net_front_kernel (plans start at conv2)
-  bool mid = false;                           // conv2 + PReLU + pool2 by net_mid_kernel (split-f16 plans start at conv3)
-  MidW rmw{}, omw{};
-  int r_cap = 0, o_cap = 0;
-  int* offs = nullptr;                        // device: (max_batch + 1) compact-batch offsets
-  // final read-back: counts block + the first FIN_FAST rows of every frame packed by one kernel into `stage`,
-  // one D2H copy into pinned memory, one host synchronisation (a frame with more faces takes the 2-D copy)
-  float* stage = nullptr;
-  int* h_pin = nullptr;
-  // switches of the environment, read once at create time so that every handle keeps the ones it was made with
-  int fin_fast = FIN_FAST;                    // VNF_FIN_FAST
-  bool spec_on = true;                        // VNF_MTCNN_SPEC: size stages 2 / 3 from the previous call's counts
-  bool layers = false;                        // VNF_MTCNN_LAYERS (diagnostic): per-layer table of the plans on stderr
-  int last_b = 0;  // frames of the last vnf_mtcnn_detect (vnf_mtcnn_results_device)
-  struct Spec { bool valid = false; int b = 0, H = 0, W = 0, max2 = 0, total2 = 0, max3 = 0, total3 = 0; } spec;   // launch sizes of stages 2 / 3 from the previous call
-  long long spec_misses = 0;
-  ~Mtcnn() override { delete renc; delete oenc; if (h_pin) (void)hipHostFree(h_pin); }
-  size_t cap_px = 0, cap_p1 = 0, cap_c2 = 0, cap_out = 0;
-  std::vector<float> h_fin;
-  std::vector<int> h_cnt;
-  LevelTable last_table;
-};
-
 
 // counts block (row_cnt .. status) followed by [B][FIN_FAST][15] result rows
 __global__ void pack_results_kernel(const int* __restrict__ cnt_block, int ncnt, const float* __restrict__ fin,
@@ -1227,626 +1136,121 @@ __global__ void pack_results_kernel(const int* __restrict__ cnt_block, int ncnt,
   }
 }
 
-// device-resident copy of the last detection, frames concatenated in order (the host arrays' layout)
-__global__ void results_device_kernel(const float* __restrict__ fin, const int* __restrict__ fin_cnt, int max_out, int KR,
-                                      int32_t* __restrict__ fidx, float* __restrict__ boxes, float* __restrict__ probs,
-                                      float* __restrict__ points) {
-  const int img = blockIdx.x;
-  int off = 0;
-  for (int i = 0; i < img; ++i) off += fin_cnt[i];
-  const int c = fin_cnt[img];
-  for (int k = threadIdx.x; k < c; k += blockDim.x) {
-    const int o = off + k;
-    if (o >= max_out) break;
-    const float* f = fin + ((size_t)img * KR + k) * 15;
-    if (fidx) fidx[o] = img;
-    if (boxes) { boxes[o * 4] = f[0]; boxes[o * 4 + 1] = f[1]; boxes[o * 4 + 2] = f[2]; boxes[o * 4 + 3] = f[3]; }
-    if (probs) probs[o] = f[4];
-    if (points)
-      for (int j = 0; j < 10; ++j) points[o * 10 + j] = f[5 + j];
+// =============================================================================================
+// launchers (mtcnn.h)
+hipError_t launch_pyramid(const uint8_t* frames, int B, int H, int W, const LevelTable& t, float* lvl, const int* row_order,
+                          hipStream_t s) {
+  // bin sums must stay exact in fp32 (< 2^24): always true below 256x256-pixel bins
+  if (row_order) {
+    int rows = 0;
+    for (int l = 0; l < t.n; ++l) rows += t.l[l].Hs;
+    hipLaunchKernelGGL(pyramid_rows_kernel, dim3(B, rows), dim3(256), (size_t)W * 12, s, frames, H, W, t, lvl, row_order);
+  } else {
+    hipLaunchKernelGGL(pyramid_kernel, dim3((t.tot_px + 255) / 256, B), dim3(256), 0, s, frames, H, W, t, lvl);
   }
+  return hipGetLastError();
 }
 
-static LevelTable make_levels(int h, int w, int minsize, double factor) {
-  // detect_face.py:50-60,71 in python-double arithmetic
-  LevelTable t;
-  memset(&t, 0, sizeof(t));
-  const double m = 12.0 / minsize;
-  double minl = std::min(h, w) * m, scale = m;
-  int opx = 0, op1 = 0, oc2 = 0, oout = 0;
-  while (minl >= 12 && t.n < MAX_LEVELS) {
-    LevelDesc& L = t.l[t.n];
-    L.Hs = (int)(h * scale + 1);
-    L.Ws = (int)(w * scale + 1);
-    L.Hp = (L.Hs - 2 + 1) / 2;  // ceil((Hs-2)/2)
-    L.Wp = (L.Ws - 2 + 1) / 2;
-    L.H2 = L.Hp - 2; L.W2 = L.Wp - 2;
-    L.oh = L.H2 - 2; L.ow = L.W2 - 2;
-    L.scale = (float)scale;
-    L.off_px = opx; L.off_p1 = op1; L.off_c2 = oc2; L.off_out = oout;
-    opx += L.Hs * L.Ws; op1 += L.Hp * L.Wp; oc2 += L.H2 * L.W2; oout += L.oh * L.ow;
-    ++t.n;
-    scale = scale * factor;
-    minl = minl * factor;
+hipError_t launch_pnet_conv1_pool(const float* lvl, int B, const LevelTable& t, const PNetW& w, float* p1, hipStream_t s) {
+  int rows = 0;
+  for (int l = 0; l < t.n; ++l) rows += t.l[l].Hp;
+  hipLaunchKernelGGL(pnet_conv1_pool_direct_kernel, dim3(B, rows), dim3(256), 0, s, lvl, t, w, p1);
+  return hipGetLastError();
+}
+
+hipError_t launch_pnet_conv2(const float* p1, int B, const LevelTable& t, const PNetW& w, float* c2, hipStream_t s) {
+  hipLaunchKernelGGL(pnet_conv2_kernel, dim3(B, (t.tot_c2 + 255) / 256), dim3(256), 0, s, p1, t, w, c2);
+  return hipGetLastError();
+}
+
+hipError_t launch_pnet_conv3_heads(const float* c2, int B, const LevelTable& t, const PNetW& w, float thr, int cap_out, Cand* cand,
+                                   int* cells, int* cand_cnt, float* prob_dbg, float* reg_dbg, hipStream_t s) {
+  hipLaunchKernelGGL(pnet_conv3_heads_kernel, dim3((t.tot_out + 255) / 256, B), dim3(256), 0, s, c2, t, w, thr, B, cap_out, cand,
+                     cells, cand_cnt, prob_dbg, reg_dbg);
+  return hipGetLastError();
+}
+
+hipError_t launch_nms_stage1(const Cand* cand, const int* cells, const int* cand_cnt, const LevelTable& t, int B, int cap_out, int H,
+                             int W, int KR, int* keep1c, int* keep1_cnt, Row* rows, int* row_cnt, int* status, const NmsScratch& g,
+                             hipStream_t s) {
+  allow_dynamic_lds<nms_scale_kernel>(LDS_NMS);
+  allow_dynamic_lds<nms_image_kernel>(LDS_NMS);
+  hipLaunchKernelGGL(nms_scale_kernel, dim3(t.n, B), dim3(256), LDS_NMS, s, cand, cells, cand_cnt, t, B, cap_out, 0.5f, keep1c,
+                     keep1_cnt, status, g);
+  hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(256), LDS_NMS, s, cand, keep1c, keep1_cnt, t, B, cap_out, 0.7f, W, H, KR, rows,
+                     row_cnt, status, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_crop_resize(const uint8_t* frames, int B, int H, int W, const Row* rows, const int* row_cnt, int maxc, int S,
+                              float* out, int* status, const int* offs, int c0, int cap, int KR, hipStream_t s) {
+  if (frames_aligned(frames, W))
+    // S / 8 row groups per candidate: 8 output rows per workgroup = 4 waves x 2 rows (measured best of 2..8 groups)
+    hipLaunchKernelGGL(crop_resize_rows_kernel, dim3(maxc, B, S / 8), dim3(256), 0, s, frames, H, W, rows, row_cnt, S, out, status, offs, c0, cap, KR);
+  else
+    hipLaunchKernelGGL(crop_resize_kernel, dim3(maxc, B), dim3(256), 0, s, frames, H, W, rows, row_cnt, S, out, status, offs, c0, cap, KR);
+  return hipGetLastError();
+}
+
+template <int S, int BANDP, bool SPLIT>
+static hipError_t launch_front(int bands, int lds, const float* crops, const FrontW& fw, float* p1, int n, hipStream_t s) {
+  allow_dynamic_lds<net_front_kernel<S, BANDP, 512, SPLIT>>(lds);
+  hipLaunchKernelGGL((net_front_kernel<S, BANDP, 512, SPLIT>), dim3(bands, n), dim3(512), lds, s, crops, fw, p1);
+  return hipGetLastError();
+}
+
+hipError_t launch_net_front(int S, bool split, const float* crops, const FrontW& fw, float* p1, int n, hipStream_t s) {
+  // R-Net: the whole candidate in one workgroup of 8 waves (no band overlap to recompute; measured 0.065 ms against
+  // 0.074 for two bands x 4 waves); O-Net: bands of 4 pooled rows x 8 waves (larger bands / 16 waves were slower)
+  if (S == 24) return split ? launch_front<24, 11, true>(1, LDS_RFRONT, crops, fw, p1, n, s) : launch_front<24, 11, false>(1, LDS_RFRONT, crops, fw, p1, n, s);
+  return split ? launch_front<48, 4, true>(6, LDS_OFRONT, crops, fw, p1, n, s) : launch_front<48, 4, false>(6, LDS_OFRONT, crops, fw, p1, n, s);
+}
+
+hipError_t launch_net_mid(int S, const float* p1, const MidW& mw, float* p2, int n, hipStream_t s) {
+  if (S == 24) {
+    allow_dynamic_lds<net_mid_kernel<11, 48, 6, 1>>(LDS_RMID);
+    hipLaunchKernelGGL((net_mid_kernel<11, 48, 6, 1>), dim3(n), dim3(384), LDS_RMID, s, p1, mw, p2);
+  } else {
+    allow_dynamic_lds<net_mid_kernel<23, 64, 8, 2>>(LDS_OMID);
+    hipLaunchKernelGGL((net_mid_kernel<23, 64, 8, 2>), dim3(n), dim3(512), LDS_OMID, s, p1, mw, p2);
   }
-  t.tot_px = opx; t.tot_p1 = op1; t.tot_c2 = oc2; t.tot_out = oout;
-  return t;
+  return hipGetLastError();
 }
 
-static const float* up_transposed(Mtcnn& m, const float* w, int cout, int cin, int k) {
-  // [cout][cin][k][k] -> [cin][k][k][cout]
-  std::vector<float> t((size_t)cout * cin * k * k);
-  for (int co = 0; co < cout; ++co)
-    for (int c = 0; c < cin; ++c)
-      for (int i = 0; i < k * k; ++i) t[((size_t)c * k * k + i) * cout + co] = w[((size_t)co * cin + c) * k * k + i];
-  return (const float*)m.upload(t.data(), t.size() * 4);
+hipError_t launch_prefix_offsets(const int* cnt, int B, int* offs, hipStream_t s) {
+  hipLaunchKernelGGL(prefix_offsets_kernel, dim3(1), dim3(64), 0, s, cnt, B, offs);
+  return hipGetLastError();
 }
 
-#define GETW(dst, wmref, name, numel)                                                        \
-  const float* dst = (wmref).get(name, numel);                                               \
-  if (!dst) { delete m; return fail(VNF_E_MISSING, std::string("mtcnn: missing weight ") + (wmref).missing); }
-#define UP(ptr, numel) (const float*)m->upload(ptr, (size_t)(numel) * 4)
+hipError_t launch_heads_scatter(const float* heads, int hw, const int* offs, const int* cnt, int maxc, int B, int c0, int cap,
+                                float* dst, int nf, bool split, int KR, hipStream_t s) {
+  hipLaunchKernelGGL(heads_scatter_kernel, dim3((maxc + 63) / 64, B), dim3(64), 0, s, heads, hw, offs, cnt, c0, cap, dst, nf,
+                     split ? 1 : 0, KR);
+  return hipGetLastError();
+}
+
+hipError_t launch_stage2_post(const Row* rows, const int* row_cnt, const float* rout, float thr_score, int B, int H, int W, int KR,
+                              Row* rows3, int* row3_cnt, int* status, const NmsScratch& g, hipStream_t s) {
+  allow_dynamic_lds<stage2_post_kernel>(LDS_POST);
+  hipLaunchKernelGGL(stage2_post_kernel, dim3(B), dim3(256), LDS_POST, s, rows, row_cnt, rout, thr_score, 0.7f, W, H, KR, rows3,
+                     row3_cnt, status, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_stage3_post(const Row* rows3, const int* row3_cnt, const float* oout, float thr_score, int select_largest, int B,
+                              int KR, float* fin, int* fin_cnt, int* status, const NmsScratch& g, hipStream_t s) {
+  allow_dynamic_lds<stage3_post_kernel>(LDS_POST);
+  hipLaunchKernelGGL(stage3_post_kernel, dim3(B), dim3(256), LDS_POST, s, rows3, row3_cnt, oout, thr_score, 0.7f, select_largest,
+                     KR, fin, fin_cnt, status, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_pack_results(const int* cnt_block, int ncnt, const float* fin, const int* fin_cnt, int B, int KR, float* stage,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(pack_results_kernel, dim3(B), dim3(256), 0, s, cnt_block, ncnt, fin, fin_cnt, B, KR, stage);
+  return hipGetLastError();
+}
+
+bool stage_tables_overflowed(int status) { return (status & (ST_OVER_SCALE | ST_OVER_IMG | ST_OVER_KEEP)) != 0; }
 
 }  // namespace vnf
-using namespace vnf;
-
-extern "C" int vnf_mtcnn_create(const vnf_tensor_desc* pnet, int n_pnet, const vnf_tensor_desc* rnet, int n_rnet,
-                                const vnf_tensor_desc* onet, int n_onet, const vnf_mtcnn_cfg* cfg, vnf_handle* out) {
-  try {
-    if (!pnet || !rnet || !onet || !cfg || !out) return fail(VNF_E_INVALID, "vnf_mtcnn_create: bad argument");
-    if (cfg->min_face_size < 1 || cfg->max_batch < 1 || cfg->max_height < 12 || cfg->max_width < 12 ||
-        !(cfg->factor > 0.f && cfg->factor < 1.f))
-      return fail(VNF_E_INVALID, "vnf_mtcnn_create: bad configuration");
-    *out = nullptr;
-    Mtcnn* m = new Mtcnn();
-    m->cfg = *cfg;
-    (void)hipGetDevice(&m->device);
-    WeightMap wp(pnet, n_pnet), wr(rnet, n_rnet), wo(onet, n_onet);
-    {
-      GETW(c1, wp, "conv1.weight", 270) GETW(b1, wp, "conv1.bias", 10) GETW(a1, wp, "prelu1.weight", 10)
-      GETW(c2, wp, "conv2.weight", 1440) GETW(b2, wp, "conv2.bias", 16) GETW(a2, wp, "prelu2.weight", 16)
-      GETW(c3, wp, "conv3.weight", 4608) GETW(b3, wp, "conv3.bias", 32) GETW(a3, wp, "prelu3.weight", 32)
-      GETW(c41, wp, "conv4_1.weight", 64) GETW(b41, wp, "conv4_1.bias", 2)
-      GETW(c42, wp, "conv4_2.weight", 128) GETW(b42, wp, "conv4_2.bias", 4)
-      m->pw.w1 = up_transposed(*m, c1, 10, 3, 3); m->pw.b1 = UP(b1, 10); m->pw.a1 = UP(a1, 10);
-      m->pw.w2 = up_transposed(*m, c2, 16, 10, 3); m->pw.b2 = UP(b2, 16); m->pw.a2 = UP(a2, 16);
-      m->pw.w3 = up_transposed(*m, c3, 32, 16, 3); m->pw.b3 = UP(b3, 32); m->pw.a3 = UP(a3, 32);
-      m->pw.w41 = up_transposed(*m, c41, 2, 32, 1); m->pw.b41 = UP(b41, 2);
-      m->pw.w42 = up_transposed(*m, c42, 4, 32, 1); m->pw.b42 = UP(b42, 4);
-    }
-    // switches of the environment: read here, once per handle
-    auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-    // VNF_MTCNN_DTYPE=f32 keeps the R/O-Net plans (and conv1 in net_front_kernel) on the exact-f32 MFMA; the default is
-    // split-f16 (two 16-bit MFMAs per product, ~22 significant bits) for every layer of both nets
-    const bool plans_f32 = getenv("VNF_MTCNN_DTYPE") && !strcmp(getenv("VNF_MTCNN_DTYPE"), "f32");
-    const bool mid_env = env_int("VNF_MTCNN_MID", 1) != 0;
-    m->spec_on = env_int("VNF_MTCNN_SPEC", 1) != 0;
-    m->layers = getenv("VNF_MTCNN_LAYERS") != nullptr;
-    m->fin_fast = std::max(0, std::min(FIN_FAST, env_int("VNF_FIN_FAST", FIN_FAST)));
-    {
-      m->r_cap = std::min(cfg->max_batch * KEEP, 8192);
-      m->o_cap = std::min(cfg->max_batch * KEEP, 2048);
-      m->renc = new Encoder();
-      m->renc->max_streams = 1;  // the detector shares the GPU with the embedding stream: no forks of its own
-      m->renc->tune_batch = std::max(1, m->r_cap / 2);  // typical stage-2 load, not the capacity
-      m->renc->arch = ARCH_RNET; m->renc->dtype = plans_f32 ? F32 : F16X2; m->renc->max_batch = m->r_cap;
-      auto pack_front = [&](WeightMap& wm, int cout, FrontW& fw) -> bool {
-        const float* c1 = wm.get("conv1.weight", (int64_t)cout * 27);
-        const float* b1 = wm.get("conv1.bias", cout);
-        const float* a1 = wm.get("prelu1.weight", cout);
-        if (!c1 || !b1 || !a1) return false;
-        std::vector<float> w(32 * 36, 0.f), b(32, 0.f), a(32, 0.f);
-        for (int co = 0; co < cout; ++co) {
-          for (int c = 0; c < 3; ++c)
-            for (int kh = 0; kh < 3; ++kh)
-              for (int kw = 0; kw < 3; ++kw) w[(co * 9 + kh * 3 + kw) * 4 + c] = c1[((co * 3 + c) * 3 + kh) * 3 + kw];
-          b[co] = b1[co]; a[co] = a1[co];
-        }
-        fw.w = (const float*)m->upload(w.data(), w.size() * 4);
-        fw.b = (const float*)m->upload(b.data(), b.size() * 4);
-        fw.a = (const float*)m->upload(a.data(), a.size() * 4);
-        return fw.w && fw.b && fw.a;
-      };
-      if (!pack_front(wr, 28, m->rfw) || !pack_front(wo, 32, m->ofw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv1 weights"); }
-      m->mid = mid_env && m->renc->dtype == F16X2;
-      if (m->mid) {
-        // conv2 weights [cout][cin][3][3] -> MFMA A-fragments of interleaved split-f16: fragment (ct, kb = 2 tap + half),
-        // lane (row r, group g) = the 4 k values (channels 16 half + 4 g .. + 3 of the tap) of output channel 16 ct + r
-        // as (hi, lo) pairs; input channels beyond cin (R-Net: 28 of 32) are zero
-        auto pack_mid = [&](WeightMap& wm, int cout, int cin, MidW& mw) -> bool {
-          const float* c2 = wm.get("conv2.weight", (int64_t)cout * cin * 9);
-          const float* b2 = wm.get("conv2.bias", cout);
-          const float* a2 = wm.get("prelu2.weight", cout);
-          if (!c2 || !b2 || !a2) return false;
-          std::vector<uint32_t> w((size_t)(cout / 16) * 18 * 64 * 4, 0u);
-          for (int ct = 0; ct < cout / 16; ++ct)
-            for (int kb = 0; kb < 18; ++kb)
-              for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 4; ++e) {
-                  const int co = 16 * ct + (l & 15), c = 16 * (kb & 1) + 4 * (l >> 4) + e, tap = kb >> 1;
-                  const float v = c < cin ? c2[((size_t)(co * cin + c) * 3 + tap / 3) * 3 + tap % 3] : 0.f;
-                  const sf16 sv(v);
-                  uint32_t bits;
-                  memcpy(&bits, &sv, 4);
-                  w[(((size_t)ct * 18 + kb) * 64 + l) * 4 + e] = bits;
-                }
-          mw.w = (const uint4*)m->upload(w.data(), w.size() * 4);
-          mw.b = (const float*)m->upload(b2, (size_t)cout * 4);
-          mw.a = (const float*)m->upload(a2, (size_t)cout * 4);
-          return mw.w && mw.b && mw.a;
-        };
-        if (!pack_mid(wr, 48, 28, m->rmw) || !pack_mid(wo, 64, 32, m->omw)) { delete m; return fail(VNF_E_MISSING, "mtcnn: conv2 weights"); }
-      }
-      int rr = build_rnet(*m->renc, wr, m->mid);
-      if (rr == VNF_OK) rr = m->renc->finalize();
-      m->oenc = new Encoder();
-      m->oenc->max_streams = 1;
-      m->oenc->tune_batch = std::max(1, m->o_cap / 4);
-      m->oenc->arch = ARCH_ONET; m->oenc->dtype = m->renc->dtype; m->oenc->max_batch = m->o_cap;
-      if (rr == VNF_OK) rr = build_onet(*m->oenc, wo, m->mid);
-      if (rr == VNF_OK) rr = m->oenc->finalize();
-      if (rr != VNF_OK) { delete m; return rr; }
-    }
-    const int B = cfg->max_batch;
-    m->cap_table = make_levels(cfg->max_height, cfg->max_width, cfg->min_face_size, (double)cfg->factor);
-    // other aspect ratios up to the same bounds can need slightly more: 10 % head-room
-    m->cap_px = (size_t)(m->cap_table.tot_px * 1.1) + 4096; m->cap_p1 = (size_t)(m->cap_table.tot_p1 * 1.1) + 4096;
-    m->cap_c2 = (size_t)(m->cap_table.tot_c2 * 1.1) + 4096; m->cap_out = (size_t)(m->cap_table.tot_out * 1.1) + 4096;
-    {
-      int rows_cap = 0;
-      for (int l = 0; l < m->cap_table.n; ++l) rows_cap += m->cap_table.l[l].Hs;
-      m->row_order_cap = (int)(rows_cap * 1.1) + 64;
-      m->row_order = (int*)m->dalloc((size_t)m->row_order_cap * 4);
-      if (!m->row_order) { delete m; return VNF_E_HIP; }
-    }
-    m->lvl = (float*)m->dalloc(m->cap_px * 3 * B * 4);
-    m->p1 = (float*)m->dalloc(m->cap_p1 * 10 * B * 4);
-    m->c2 = (float*)m->dalloc(m->cap_c2 * 16 * B * 4);
-    const size_t nseg = (size_t)MAX_LEVELS * B;
-    // rows per frame of the stage-2 / stage-3 tables: run-time (max_candidates), at least the LDS fast-path size
-    m->keep = std::max(KEEP, cfg->max_candidates);
-    const size_t KR = (size_t)m->keep;
-    m->cand = (Cand*)m->dalloc((size_t)B * m->cap_out * sizeof(Cand));
-    m->cells = (int*)m->dalloc((size_t)B * m->cap_out * 4);
-    m->keep1c = (int*)m->dalloc((size_t)B * m->cap_out * 4);
-    m->cand_cnt = (int*)m->dalloc((nseg * 2 + (size_t)B * 3 + 16) * 4);
-    m->keep1_cnt = m->cand_cnt + nseg;
-    m->row_cnt = m->keep1_cnt + nseg;
-    m->row3_cnt = m->row_cnt + B;
-    m->fin_cnt = m->row3_cnt + B;
-    m->status = m->fin_cnt + B;
-    m->rows = (Row*)m->dalloc((size_t)B * KR * sizeof(Row));
-    m->rows3 = (Row*)m->dalloc((size_t)B * KR * sizeof(Row));
-    m->rout = (float*)m->dalloc((size_t)B * KR * 5 * 4);
-    m->oout = (float*)m->dalloc((size_t)B * KR * 15 * 4);
-    m->fin = (float*)m->dalloc((size_t)B * KR * 15 * 4);
-    {
-      // NMS scratch in global memory (lists longer than the LDS tables): per frame max(cells of the pyramid, rows)
-      const size_t st = std::max(m->cap_out, KR);
-      m->scratch.stride = (int)st;
-      m->scratch.keys = (unsigned long long*)m->dalloc((size_t)B * st * 8);
-      m->scratch.kbox = (float4*)m->dalloc((size_t)B * st * 16);
-      m->scratch.keep = (int*)m->dalloc((size_t)B * st * 4);
-      m->scratch.reg = (float4*)m->dalloc((size_t)B * st * 16);
-      if (!m->scratch.keys || !m->scratch.kbox || !m->scratch.keep || !m->scratch.reg || !m->cells || !m->keep1c) { delete m; return VNF_E_HIP; }
-    }
-    {
-      const size_t sb = ((size_t)B * 3 + 16) * 4 + (size_t)B * FIN_FAST * 15 * 4;
-      m->stage = (float*)m->dalloc(sb);
-      if (hipHostMalloc((void**)&m->h_pin, sb, hipHostMallocDefault) != hipSuccess) m->h_pin = nullptr;
-      if (!m->stage || !m->h_pin) { delete m; return fail(VNF_E_HIP, "mtcnn: read-back buffers"); }
-    }
-    m->offs = (int*)m->dalloc((size_t)(B + 1) * 4);
-    if (!m->lvl || !m->p1 || !m->c2 || !m->cand || !m->cand_cnt || !m->rows || !m->rows3 ||
-        !m->rout || !m->oout || !m->fin || !m->pw.w1) {
-      delete m;
-      return VNF_E_HIP;
-    }
-    // Dynamic LDS of every launch that requests some: opt in with the exact sizes (above 64 KiB this is needed; gfx950
-    // has 160 KiB per workgroup).  pyramid_rows_kernel takes the fast path only up to 64 KiB.
-    // The attribute call is advisory on some ROCm builds; launch errors are checked at run time.
-    {
-      int lds_max = 0;
-      VNF_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device));
-      const std::pair<const void*, int> need[] = {
-          {(const void*)nms_scale_kernel, LDS_NMS}, {(const void*)nms_image_kernel, LDS_NMS},
-          {(const void*)stage2_post_kernel, LDS_POST}, {(const void*)stage3_post_kernel, LDS_POST},
-          {(const void*)net_front_kernel<24, 11, 512, true>, LDS_RFRONT}, {(const void*)net_front_kernel<24, 11, 512, false>, LDS_RFRONT},
-          {(const void*)net_front_kernel<48, 4, 512, true>, LDS_OFRONT}, {(const void*)net_front_kernel<48, 4, 512, false>, LDS_OFRONT},
-          {(const void*)net_mid_kernel<11, 48, 6, 1>, LDS_RMID}, {(const void*)net_mid_kernel<23, 64, 8, 2>, LDS_OMID}};
-      int need_max = 0;
-      for (const auto& kn : need) {
-        (void)hipFuncSetAttribute(kn.first, hipFuncAttributeMaxDynamicSharedMemorySize, kn.second);
-        need_max = std::max(need_max, kn.second);
-      }
-      (void)hipGetLastError();
-      if (lds_max < need_max) {
-        delete m;
-        return fail(VNF_E_INVALID, "mtcnn: device reports " + std::to_string(lds_max) + " B of LDS per workgroup, need " + std::to_string(need_max));
-      }
-    }
-    VNF_HIP(hipDeviceSynchronize());
-    *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(m));
-    return VNF_OK;
-  } catch (const std::exception& ex) {
-    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
-  }
-}
-
-// per-stage device time + algorithmic bytes of one call (vnf_mtcnn_stage_times): events between the stages' launches
-struct StageProf {
-  std::vector<std::string> name;
-  std::vector<double> bytes;
-  std::vector<hipEvent_t> ev;
-  void mark(const char* n, double b, hipStream_t s) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
-    (void)hipEventRecord(e, s);
-    name.push_back(n); bytes.push_back(b); ev.push_back(e);
-  }
-  ~StageProf() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-};
-
-static int mtcnn_run(Mtcnn* m, const uint8_t* frames, int b, int H, int W, hipStream_t s, std::vector<int>& cnt,
-                     std::vector<float>& fin, StageProf* prof = nullptr) {
-  const vnf_mtcnn_cfg& cfg = m->cfg;
-  // a mark closes the stage named in it: its time is the span since the previous mark
-  auto mark = [&](const char* n, double bytes) { if (prof) prof->mark(n, bytes, s); };
-  if (b > cfg.max_batch || H > cfg.max_height || W > cfg.max_width) return fail(VNF_E_CAPACITY, "mtcnn: frame batch exceeds handle capacity");
-  LevelTable t = make_levels(H, W, cfg.min_face_size, (double)cfg.factor);
-  m->last_table = t;
-  m->last_b = 0;
-  cnt.assign(b, 0);
-  fin.clear();
-  if (t.n == 0) return VNF_OK;  // image smaller than one cell: no detections
-  if ((size_t)t.tot_px > m->cap_px || (size_t)t.tot_p1 > m->cap_p1 || (size_t)t.tot_c2 > m->cap_c2 || (size_t)t.tot_out > m->cap_out)
-    return fail(VNF_E_CAPACITY, "mtcnn: pyramid exceeds handle capacity");
-  const int B = b;
-  const size_t nseg = (size_t)MAX_LEVELS * cfg.max_batch;
-  VNF_HIP(hipMemsetAsync(m->cand_cnt, 0, (nseg * 2 + (size_t)cfg.max_batch * 3 + 16) * 4, s));
-  mark("begin", 0);
-  {
-    // bin sums must stay exact in fp32 (< 2^24): always true below 256x256-pixel bins
-    const bool fast = (W * 3) % 16 == 0 && (size_t)W * 12 <= 64 * 1024 && ((reinterpret_cast<uintptr_t>(frames)) & 15) == 0;
-    if (fast) {
-      int rows = 0;
-      for (int l = 0; l < t.n; ++l) rows += t.l[l].Hs;
-      if (rows > m->row_order_cap) return fail(VNF_E_CAPACITY, "mtcnn: pyramid exceeds handle capacity");
-      if (m->row_order_h != H || m->row_order_w != W) {
-        std::vector<std::pair<long long, int>> ord;     // (first input row, tall bins first) -> (level << 16 | row)
-        for (int l = 0; l < t.n; ++l)
-          for (int i = 0; i < t.l[l].Hs; ++i) {
-            const long long h0 = ((long long)i * H) / t.l[l].Hs;
-            ord.push_back({h0 * 64 + (63 - std::min(l, 63)), (l << 16) | i});
-          }
-        std::sort(ord.begin(), ord.end());
-        std::vector<int> packed(ord.size());
-        for (size_t k = 0; k < ord.size(); ++k) packed[k] = ord[k].second;
-        VNF_HIP(hipMemcpyAsync(m->row_order, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s));
-        VNF_HIP(hipStreamSynchronize(s));              // the host vector goes away; happens once per frame size
-        m->row_order_h = H; m->row_order_w = W;
-      }
-      hipLaunchKernelGGL(pyramid_rows_kernel, dim3(B, rows), dim3(256), (size_t)W * 12, s, frames, H, W, t, m->lvl, m->row_order);
-    } else {
-      hipLaunchKernelGGL(pyramid_kernel, dim3((t.tot_px + 255) / 256, B), dim3(256), 0, s, frames, H, W, t, m->lvl);
-    }
-  }
-  // algorithmic bytes per launch: what each kernel must read + write once (SURVEY.md 8d terms, from the level table)
-  const double fB = (double)B;
-  mark("pyramid", fB * ((double)H * W * 3 + (double)t.tot_px * 12));
-  {
-    int rows = 0;
-    for (int l = 0; l < t.n; ++l) rows += t.l[l].Hp;
-    hipLaunchKernelGGL(pnet_conv1_pool_direct_kernel, dim3(B, rows), dim3(256), 0, s, m->lvl, t, m->pw, m->p1);
-  }
-  mark("pnet_conv1_pool", fB * ((double)t.tot_px * 12 + (double)t.tot_p1 * 40));
-  hipLaunchKernelGGL(pnet_conv2_kernel, dim3(B, (t.tot_c2 + 255) / 256), dim3(256), 0, s, m->p1, t, m->pw, m->c2);
-  mark("pnet_conv2", fB * ((double)t.tot_p1 * 40 + (double)t.tot_c2 * 64));
-  const int KR = m->keep, cap_out = (int)m->cap_out;
-  hipLaunchKernelGGL(pnet_conv3_heads_kernel, dim3((t.tot_out + 255) / 256, B), dim3(256), 0, s, m->c2, t, m->pw,
-                     cfg.thresholds[0], B, cap_out, m->cand, m->cells, m->cand_cnt, m->prob_dbg, m->reg_dbg);
-  mark("pnet_conv3_heads", fB * (double)t.tot_c2 * 64);
-  hipLaunchKernelGGL(nms_scale_kernel, dim3(t.n, B), dim3(256), LDS_NMS, s, m->cand, m->cells, m->cand_cnt, t, B, cap_out, 0.5f,
-                     m->keep1c, m->keep1_cnt, m->status, m->scratch);
-  hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(256), LDS_NMS, s, m->cand, m->keep1c, m->keep1_cnt, t, B, cap_out, 0.7f, W, H,
-                     KR, m->rows, m->row_cnt, m->status, m->scratch);
-  VNF_HIP(hipGetLastError());
-  mark("nms_stage1", 0);
-  const int ncnt = cfg.max_batch * 3 + 16;
-  int* const h = m->h_pin;  // pinned: the copy is a true async DMA, the only wait is the stream synchronisation
-  auto check_overflow = [&]() -> int {   // after a read-back into h: did a stage-1 list outgrow its table?
-    const int st = h[cfg.max_batch * 3];
-    if (st & (ST_OVER_SCALE | ST_OVER_IMG | ST_OVER_KEEP))
-      return fail(VNF_E_CAPACITY, "mtcnn: candidate table overflow (status " + std::to_string(st) + "): a frame has more than " +
-                                  std::to_string(m->keep) + " stage-1 survivors; raise vnf_mtcnn_cfg.max_candidates");
-    return VNF_OK;
-  };
-  auto read_counts = [&]() -> int {
-    VNF_HIP(hipMemcpyAsync(h, m->row_cnt, (size_t)ncnt * 4, hipMemcpyDeviceToHost, s));
-    VNF_HIP(hipStreamSynchronize(s));
-    return check_overflow();
-  };
-  // ---- stages 2 and 3 as launch sequences sized by (largest per-frame candidate count, total candidates): every kernel
-  // reads the true counts from device memory and leaves early past them, so any UPPER bound gives the exact result (the
-  // nets then also run on the unused tail rows of the dense batch); an under-estimate leaves candidates out and is
-  // detected after the read-back.
-  const bool crop_fast = (W * 3) % 16 == 0 && ((reinterpret_cast<uintptr_t>(frames)) & 15) == 0;
-  auto crop = [&](const Row* rws, const int* cntp, int maxc, int S, float* dst, const int* offs, int c0, int cap) {
-    if (crop_fast)
-      // S / 8 row groups per candidate: 8 output rows per workgroup = 4 waves x 2 rows (measured best of 2..8 groups)
-      hipLaunchKernelGGL(crop_resize_rows_kernel, dim3(maxc, B, S / 8), dim3(256), 0, s, frames, H, W, rws, cntp, S, dst, m->status, offs, c0, cap, KR);
-    else
-      hipLaunchKernelGGL(crop_resize_kernel, dim3(maxc, B), dim3(256), 0, s, frames, H, W, rws, cntp, S, dst, m->status, offs, c0, cap, KR);
-  };
-  // nets on the MFMA core: candidates of all frames form one dense batch, processed in chunks of `cap`
-  auto run_net = [&](Encoder* enc, int cap, const Row* rws, const int* cntp, int maxc, int total, int S, int hw, float* dst,
-                     int nf) -> int {
-    hipLaunchKernelGGL(prefix_offsets_kernel, dim3(1), dim3(64), 0, s, cntp, B, m->offs);
-    for (int c0 = 0; c0 < total; c0 += cap) {
-      const int n = std::min(cap, total - c0);
-      crop(rws, cntp, maxc, S, (float*)enc->bufs[0].ptr, m->offs, c0, n);
-      mark(S == 24 ? "crop_resize_24" : "crop_resize_48", (double)n * S * S * 16);  // output bytes only (NHWC4 fp32)
-      const bool split = enc->dtype == F16X2;
-      const float* cin = (const float*)enc->bufs[0].ptr;
-      float* pout = (float*)enc->bufs[1].ptr;
-      // R-Net: the whole candidate in one workgroup of 8 waves (no band overlap to recompute; measured 0.065 ms against
-      // 0.074 for two bands x 4 waves); O-Net: bands of 4 pooled rows x 8 waves (larger bands / 16 waves were slower)
-      if (S == 24 && split) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, true>), dim3(1, n), dim3(512), LDS_RFRONT, s, cin, m->rfw, pout);
-      else if (S == 24) hipLaunchKernelGGL((net_front_kernel<24, 11, 512, false>), dim3(1, n), dim3(512), LDS_RFRONT, s, cin, m->rfw, pout);
-      else if (split) hipLaunchKernelGGL((net_front_kernel<48, 4, 512, true>), dim3(6, n), dim3(512), LDS_OFRONT, s, cin, m->ofw, pout);
-      else hipLaunchKernelGGL((net_front_kernel<48, 4, 512, false>), dim3(6, n), dim3(512), LDS_OFRONT, s, cin, m->ofw, pout);
-      VNF_HIP(hipGetLastError());
-      mark(S == 24 ? "rnet_front" : "onet_front", 0);
-      if (m->mid) {   // conv2 + PReLU + pool2: buffer 1 -> buffer 3 (the plan starts at conv3)
-        float* p2o = (float*)enc->bufs[3].ptr;
-        if (S == 24) hipLaunchKernelGGL((net_mid_kernel<11, 48, 6, 1>), dim3(n), dim3(384), LDS_RMID, s, pout, m->rmw, p2o);
-        else hipLaunchKernelGGL((net_mid_kernel<23, 64, 8, 2>), dim3(n), dim3(512), LDS_OMID, s, pout, m->omw, p2o);
-        VNF_HIP(hipGetLastError());
-      }
-      std::string rep;
-      int rc = enc->run(nullptr, n, VNF_F32, nullptr, s, prof && m->layers ? &rep : nullptr);
-      if (rc != VNF_OK) return rc;
-      if (!rep.empty()) fprintf(stderr, "%s n=%d\n%s", S == 24 ? "rnet" : "onet", n, rep.c_str());
-      mark(S == 24 ? "rnet" : "onet", 0);
-      hipLaunchKernelGGL(heads_scatter_kernel, dim3((maxc + 63) / 64, B), dim3(64), 0, s, (const float*)enc->bufs.back().ptr, hw,
-                         m->offs, cntp, c0, n, dst, nf, enc->dtype == F16X2 ? 1 : 0, KR);
-    }
-    return VNF_OK;
-  };
-  auto stage2 = [&](int max2, int total2) -> int {
-    const int rc = run_net(m->renc, m->r_cap, m->rows, m->row_cnt, max2, total2, 24, 8, m->rout, 5);
-    if (rc != VNF_OK) return rc;
-    hipLaunchKernelGGL(stage2_post_kernel, dim3(B), dim3(256), LDS_POST, s, m->rows, m->row_cnt, m->rout, cfg.thresholds[1], 0.7f,
-                       W, H, KR, m->rows3, m->row3_cnt, m->status, m->scratch);
-    VNF_HIP(hipGetLastError());
-    mark("stage2_post", 0);
-    return VNF_OK;
-  };
-  auto stage3 = [&](int max3, int total3) -> int {
-    const int rc = run_net(m->oenc, m->o_cap, m->rows3, m->row3_cnt, max3, total3, 48, 16, m->oout, 15);
-    if (rc != VNF_OK) return rc;
-    hipLaunchKernelGGL(stage3_post_kernel, dim3(B), dim3(256), LDS_POST, s, m->rows3, m->row3_cnt, m->oout, cfg.thresholds[2], 0.7f,
-                       cfg.select_largest, KR, m->fin, m->fin_cnt, m->status, m->scratch);
-    m->last_b = B;
-    hipLaunchKernelGGL(pack_results_kernel, dim3(B), dim3(256), 0, s, m->row_cnt, ncnt, m->fin, m->fin_cnt, B, KR, m->stage);
-    VNF_HIP(hipGetLastError());
-    mark("stage3_post", 0);
-    return VNF_OK;
-  };
-  auto readback = [&]() -> int {
-    VNF_HIP(hipMemcpyAsync(h, m->stage, ((size_t)ncnt + (size_t)B * FIN_FAST * 15) * 4, hipMemcpyDeviceToHost, s));
-    VNF_HIP(hipStreamSynchronize(s));
-    mark("readback", 0);
-    return check_overflow();
-  };
-  auto counts_of = [&](int base, int& mx, int& tot) {
-    mx = tot = 0;
-    for (int i = 0; i < B; ++i) { mx = std::max(mx, h[base + i]); tot += h[base + i]; }
-  };
-  // an estimate with head room, in whole tiles of the nets' batch dimension
-  auto padded = [&](int v, int limit) { return std::min(limit, ((v + v / 8 + 8 + 15) / 16) * 16); };
-  // Sizes of stages 2 / 3 WITHOUT asking the device (the reference synchronises at both stage boundaries to shape its
-  // tensors, detect_face.py:96-146): a video stream's candidate counts move slowly, so the previous call's counts plus
-  // head room size this call's launches, and the one read-back at the end tells whether they covered it.  If not (or on
-  // the first call of a frame size) stage-1's counts are read and stages 2 / 3 run with exact bounds: stage 2 by its
-  // own counts, stage 3 by stage 2's (it only filters stage-2 rows) -- never a second mid-cascade synchronisation.
-  Mtcnn::Spec& sp = m->spec;
-  int r = VNF_OK;
-  bool exact_needed = true;
-  if (m->spec_on && sp.valid && sp.b == B && sp.H == H && sp.W == W) {
-    r = stage2(sp.max2, sp.total2);
-    if (r == VNF_OK) r = stage3(sp.max3, sp.total3);
-    if (r == VNF_OK) r = readback();
-    if (r != VNF_OK) return r;
-    int mx2, tot2, mx3, tot3;
-    counts_of(0, mx2, tot2);
-    counts_of(cfg.max_batch, mx3, tot3);
-    exact_needed = mx2 > sp.max2 || tot2 > sp.total2 || mx3 > sp.max3 || tot3 > sp.total3;
-    if (exact_needed) m->spec_misses++;
-  } else {
-    r = read_counts();
-    if (r != VNF_OK) return r;
-    mark("host_sync_1", 0);
-  }
-  if (exact_needed) {
-    // h[0..B) = stage-1 counts (from read_counts, or from the read-back of the speculative pass: stage 1 is not re-run)
-    int mx2, tot2;
-    counts_of(0, mx2, tot2);
-    if (mx2 > 0) {
-      r = stage2(mx2, tot2);
-      if (r == VNF_OK) r = stage3(mx2, tot2);      // stage-3 rows are a subset of stage-2 rows: exact upper bounds
-    } else {
-      m->last_b = B;
-      hipLaunchKernelGGL(pack_results_kernel, dim3(B), dim3(256), 0, s, m->row_cnt, ncnt, m->fin, m->fin_cnt, B, KR, m->stage);
-    }
-    if (r == VNF_OK) r = readback();
-    if (r != VNF_OK) return r;
-  }
-  {
-    int mx2, tot2, mx3, tot3;
-    counts_of(0, mx2, tot2);
-    counts_of(cfg.max_batch, mx3, tot3);
-    sp.valid = true; sp.b = B; sp.H = H; sp.W = W;
-    sp.max2 = padded(mx2, KR); sp.total2 = padded(tot2, B * KR);
-    sp.max3 = padded(mx3, KR); sp.total3 = padded(tot3, B * KR);
-  }
-  int maxf = 0;
-  for (int i = 0; i < B; ++i) { cnt[i] = h[2 * cfg.max_batch + i]; maxf = std::max(maxf, cnt[i]); }
-  if (maxf == 0) return VNF_OK;
-  fin.resize((size_t)B * maxf * 15);
-  if (maxf <= m->fin_fast) {
-    const float* rows = reinterpret_cast<const float*>(h + ncnt);
-    for (int i = 0; i < B; ++i)
-      memcpy(&fin[(size_t)i * maxf * 15], rows + (size_t)i * FIN_FAST * 15, (size_t)maxf * 15 * 4);
-    return VNF_OK;
-  }
-  VNF_HIP(hipMemcpy2DAsync(fin.data(), (size_t)maxf * 15 * 4, m->fin, (size_t)KR * 15 * 4, (size_t)maxf * 15 * 4, B,
-                           hipMemcpyDeviceToHost, s));
-  VNF_HIP(hipStreamSynchronize(s));
-  return VNF_OK;
-}
-
-extern "C" int vnf_mtcnn_detect(vnf_handle h, const uint8_t* frames, int b, int height, int width, int32_t* counts,
-                                float* boxes, float* probs, float* points, int max_out, int32_t* n_out, void* stream) {
-  try {
-    Mtcnn* m = handle_cast<Mtcnn>(h);
-    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
-    if (!frames || b <= 0 || !counts || !n_out) return fail(VNF_E_INVALID, "vnf_mtcnn_detect: bad argument");
-    std::vector<int> cnt;
-    std::vector<float> fin;
-    int r = mtcnn_run(m, frames, b, height, width, (hipStream_t)stream, cnt, fin);
-    if (r != VNF_OK) return r;
-    int total = 0, maxf = 0;
-    for (int i = 0; i < b; ++i) { counts[i] = cnt[i]; total += cnt[i]; maxf = std::max(maxf, cnt[i]); }
-    *n_out = total;
-    if (total > max_out) return fail(VNF_E_CAPACITY, "vnf_mtcnn_detect: more faces than max_out");
-    int o = 0;
-    for (int i = 0; i < b; ++i)
-      for (int k = 0; k < cnt[i]; ++k, ++o) {
-        const float* f = &fin[((size_t)i * maxf + k) * 15];
-        if (boxes) memcpy(boxes + (size_t)o * 4, f, 16);
-        if (probs) probs[o] = f[4];
-        if (points) memcpy(points + (size_t)o * 10, f + 5, 40);
-      }
-    return VNF_OK;
-  } catch (const std::exception& ex) {
-    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
-  }
-}
-
-// One detection with HIP events between the cascade's stages (on the caller's stream): a text table, one line per
-// stage "name ms algorithmic_bytes" (bytes 0 where the stage is not bandwidth-priced).  Synchronises.
-extern "C" int vnf_mtcnn_stage_times(vnf_handle h, const uint8_t* frames, int b, int height, int width, char* report,
-                                     int64_t capacity, void* stream) {
-  try {
-    Mtcnn* m = handle_cast<Mtcnn>(h);
-    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
-    if (!frames || b <= 0 || !report || capacity <= 0) return fail(VNF_E_INVALID, "vnf_mtcnn_stage_times: bad argument");
-    std::vector<int> cnt;
-    std::vector<float> fin;
-    StageProf prof;
-    int r = mtcnn_run(m, frames, b, height, width, (hipStream_t)stream, cnt, fin, &prof);
-    if (r != VNF_OK) return r;
-    VNF_HIP(hipStreamSynchronize((hipStream_t)stream));
-    std::string rep;
-    char line[160];
-    for (size_t i = 1; i < prof.ev.size(); ++i) {
-      float ms = 0;
-      VNF_HIP(hipEventElapsedTime(&ms, prof.ev[i - 1], prof.ev[i]));
-      snprintf(line, sizeof line, "%s %.6f %.0f\n", prof.name[i].c_str(), ms, prof.bytes[i]);
-      rep += line;
-    }
-    strncpy(report, rep.c_str(), (size_t)capacity - 1);
-    report[capacity - 1] = 0;
-    return VNF_OK;
-  } catch (const std::exception& ex) {
-    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
-  }
-}
-
-extern "C" int vnf_mtcnn_results_device(vnf_handle h, int32_t* frame_idx, float* boxes, float* probs, float* points,
-                                        int max_out, void* stream) {
-  Mtcnn* m = handle_cast<Mtcnn>(h);
-  if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
-  if (max_out < 0) return fail(VNF_E_INVALID, "vnf_mtcnn_results_device: bad argument");
-  if (m->last_b == 0 || max_out == 0) return VNF_OK;  // the last detection found nothing
-  hipLaunchKernelGGL(results_device_kernel, dim3(m->last_b), dim3(64), 0, (hipStream_t)stream, m->fin, m->fin_cnt, max_out, m->keep,
-                     frame_idx, boxes, probs, points);
-  VNF_HIP(hipGetLastError());
-  return VNF_OK;
-}
-
-// Staged-parity hook for the O-stage decode alone (detect_face.py:148-169 + mtcnn.py:334-340): runs stage3_post_kernel
-// on a caller-made candidate table of ONE frame -- boxes (n,4) before bbreg and the O-Net outputs (n,15: face
-// probability, 4 regression values, 5 x-landmarks, 5 y-landmarks) -- so a test can inject exactly tied scores.
-// fin_out receives up to max_out rows [x1,y1,x2,y2,score, 10 landmark coordinates].  Synchronises.
-extern "C" int vnf_mtcnn_debug_stage3(vnf_handle h, const float* boxes, const float* onet_out, int n, float* fin_out,
-                                      int max_out, int32_t* n_out, void* stream) {
-  try {
-    Mtcnn* m = handle_cast<Mtcnn>(h);
-    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
-    if (!boxes || !onet_out || n < 0 || !fin_out || !n_out) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_stage3: bad argument");
-    if (n > m->keep) return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_stage3: more rows than the handle's tables hold");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<Row> rows((size_t)std::max(n, 1));
-    for (int i = 0; i < n; ++i) {
-      Row r{};
-      r.x1 = boxes[i * 4]; r.y1 = boxes[i * 4 + 1]; r.x2 = boxes[i * 4 + 2]; r.y2 = boxes[i * 4 + 3];
-      rows[i] = r;
-    }
-    VNF_HIP(hipMemcpyAsync(m->rows3, rows.data(), (size_t)n * sizeof(Row), hipMemcpyHostToDevice, s));
-    VNF_HIP(hipMemcpyAsync(m->oout, onet_out, (size_t)n * 15 * 4, hipMemcpyHostToDevice, s));
-    VNF_HIP(hipMemcpyAsync(m->row3_cnt, &n, 4, hipMemcpyHostToDevice, s));
-    VNF_HIP(hipMemsetAsync(m->status, 0, 4, s));
-    hipLaunchKernelGGL(stage3_post_kernel, dim3(1), dim3(256), LDS_POST, s, m->rows3, m->row3_cnt, m->oout, m->cfg.thresholds[2],
-                       0.7f, m->cfg.select_largest, m->keep, m->fin, m->fin_cnt, m->status, m->scratch);
-    VNF_HIP(hipGetLastError());
-    int nk = 0;
-    VNF_HIP(hipMemcpyAsync(&nk, m->fin_cnt, 4, hipMemcpyDeviceToHost, s));
-    VNF_HIP(hipStreamSynchronize(s));
-    *n_out = nk;
-    if (nk > max_out) return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_stage3: more rows than max_out");
-    VNF_HIP(hipMemcpy(fin_out, m->fin, (size_t)nk * 15 * 4, hipMemcpyDeviceToHost));
-    m->last_b = 0;
-    return VNF_OK;
-  } catch (const std::exception& ex) {
-    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
-  }
-}
-
-// Staged-parity hook: dense P-Net maps of one pyramid level for frame 0 of a batch (test use).
-extern "C" int vnf_mtcnn_debug_pnet(vnf_handle h, const uint8_t* frames, int height, int width, int level,
-                                    float* level_out, float* prob_out, float* reg_out, int32_t dims[4], void* stream) {
-  try {
-    Mtcnn* m = handle_cast<Mtcnn>(h);
-    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
-    LevelTable t = make_levels(height, width, m->cfg.min_face_size, (double)m->cfg.factor);
-    if (level < 0 || level >= t.n) return fail(VNF_E_INVALID, "no such level");
-    float *pd = nullptr, *rd = nullptr;
-    VNF_HIP(hipMalloc(&pd, (size_t)t.tot_out * 4 * m->cfg.max_batch));
-    VNF_HIP(hipMalloc(&rd, (size_t)t.tot_out * 16 * m->cfg.max_batch));
-    m->prob_dbg = pd; m->reg_dbg = rd;
-    std::vector<int> cnt;
-    std::vector<float> fin;
-    int r = mtcnn_run(m, frames, 1, height, width, (hipStream_t)stream, cnt, fin);
-    m->prob_dbg = nullptr; m->reg_dbg = nullptr;
-    if (r == VNF_OK) {
-      const LevelDesc& L = t.l[level];
-      dims[0] = L.Hs; dims[1] = L.Ws; dims[2] = L.oh; dims[3] = L.ow;
-      hipError_t e = hipSuccess;
-      if (level_out)
-        for (int c = 0; c < 3 && e == hipSuccess; ++c)
-          e = hipMemcpy(level_out + (size_t)c * L.Hs * L.Ws, m->lvl + (size_t)c * t.tot_px + L.off_px, (size_t)L.Hs * L.Ws * 4, hipMemcpyDeviceToHost);
-      if (prob_out && e == hipSuccess) e = hipMemcpy(prob_out, pd + L.off_out, (size_t)L.oh * L.ow * 4, hipMemcpyDeviceToHost);
-      if (reg_out)
-        for (int c = 0; c < 4 && e == hipSuccess; ++c)
-          e = hipMemcpy(reg_out + (size_t)c * L.oh * L.ow, rd + (size_t)c * t.tot_out + L.off_out, (size_t)L.oh * L.ow * 4, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) r = fail(VNF_E_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(pd);
-    (void)hipFree(rd);
-    return r;
-  } catch (const std::exception& ex) {
-    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
-  }
-}

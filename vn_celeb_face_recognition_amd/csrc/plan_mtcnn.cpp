@@ -3,7 +3,7 @@
 namespace vnf {
 
 // MTCNN R-Net (mtcnn.py:52-99) and O-Net (102-157) as plans on the exact-f32 MFMA convolution core.
-// Candidates are the batch dimension; the crop kernel writes NHWC4 fp32 crops into buffer 0.
+// Candidates are the batch dimension; the crop kernel writes NHWC4 fp32 crops into the first buffer.
 // dense4 / dense5 consume x.permute(0,3,2,1) flattened (feature (w*H + h)*C + c), i.e. they are a
 // 3x3 "convolution" over the 3x3xC map with weight[o][c][kh=h][kw=w] = dense[o][(w*3 + h)*C + c].
 static int mtcnn_conv(Encoder& e, WeightMap& wm, const std::string& name, const std::string& prelu, int xb, int cin,
@@ -51,14 +51,14 @@ static int mtcnn_heads(Encoder& e, WeightMap& wm, const std::vector<std::pair<st
 }
 
 // conv1 + PReLU + pool1 are computed by the detector's own fused kernel (mtcnn.hip net_front_kernel), which reads
-// buffer 0 (the crops) and writes buffer 1 (the pooled map); the plan starts at conv2.  mid: conv2 + pool2 as well, from
-// net_mid_kernel (mtcnn.hip: the plan starts at conv3 and reads buffer 3)
-int build_rnet(Encoder& e, WeightMap& wm, bool mid) {
+// nb.crops and writes nb.pooled1; the plan starts at conv2.  mid: conv2 + pool2 as well, from net_mid_kernel (mtcnn.hip:
+// the plan starts at conv3 and reads nb.pooled2)
+int build_rnet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb) {
   e.in_size = 24;
-  e.add_buf(24, 24, 4);
-  const int p1 = e.add_buf(11, 11, 32);
+  const int x = e.add_buf(24, 24, 4), p1 = e.add_buf(11, 11, 32);
   const int c2 = e.add_buf(9, 9, 48), p2 = e.add_buf(4, 4, 48), c3 = e.add_buf(3, 3, 64), d4 = e.add_buf(1, 1, 128);
-  const int hd = e.add_buf(1, 1, 8);   // the heads stay the LAST buffer (mtcnn.hip reads bufs.back())
+  const int hd = e.add_buf(1, 1, 8);
+  nb = {x, p1, p2, hd};
   static thread_local std::vector<float> keep;
   if (!mid) {
     TRY(mtcnn_conv(e, wm, "conv2", "prelu2", p1, 28, 32, 48, 48, 3, c2));
@@ -70,13 +70,13 @@ int build_rnet(Encoder& e, WeightMap& wm, bool mid) {
   return VNF_OK;
 }
 
-int build_onet(Encoder& e, WeightMap& wm, bool mid) {
+int build_onet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb) {
   e.in_size = 48;
-  e.add_buf(48, 48, 4);
-  const int p1 = e.add_buf(23, 23, 32);
+  const int x = e.add_buf(48, 48, 4), p1 = e.add_buf(23, 23, 32);
   const int c2 = e.add_buf(21, 21, 64), p2 = e.add_buf(10, 10, 64), c3 = e.add_buf(8, 8, 64), p3 = e.add_buf(4, 4, 64);
   const int c4 = e.add_buf(3, 3, 128), d5 = e.add_buf(1, 1, 256);
   const int hd = e.add_buf(1, 1, 16);
+  nb = {x, p1, p2, hd};
   static thread_local std::vector<float> keep;
   if (!mid) {
     TRY(mtcnn_conv(e, wm, "conv2", "prelu2", p1, 32, 32, 64, 64, 3, c2));

@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "conv_device.h"
+#include "det_results.h"
 #include "engine.h"
 #include "nms_device.h"
 #include "split_f16.h"
@@ -26,6 +28,7 @@ namespace vnf {
 
 constexpr int RCAP = 16384;   // anchors above conf_thres per frame (sort keys live in LDS: 128 KiB)
 constexpr int RKEEP = 768;    // >= keep_top_k (750)
+constexpr int LDS_RSELECT = RCAP * 8 + RKEEP * 20 + 256 * 20;   // dynamic LDS of retina_select_kernel
 
 struct RetinaGeom {
   int H, W, n_anchor;
@@ -176,26 +179,6 @@ struct Retina : HandleBase {
   ~Retina() override { delete enc; }
 };
 
-// device-resident copy of the last detection, frames concatenated in order
-__global__ void retina_results_kernel(const float* __restrict__ fin, const int* __restrict__ fin_cnt, int max_out,
-                                      int32_t* __restrict__ fidx, float* __restrict__ boxes, float* __restrict__ probs,
-                                      float* __restrict__ points) {
-  const int img = blockIdx.x;
-  int off = 0;
-  for (int i = 0; i < img; ++i) off += fin_cnt[i];
-  const int c = fin_cnt[img];
-  for (int k = threadIdx.x; k < c; k += blockDim.x) {
-    const int o = off + k;
-    if (o >= max_out) break;
-    const float* f = fin + ((size_t)img * RKEEP + k) * 15;
-    if (fidx) fidx[o] = img;
-    if (boxes) { boxes[o * 4] = f[0]; boxes[o * 4 + 1] = f[1]; boxes[o * 4 + 2] = f[2]; boxes[o * 4 + 3] = f[3]; }
-    if (probs) probs[o] = f[4];
-    if (points)
-      for (int j = 0; j < 10; ++j) points[o * 10 + j] = f[5 + j];
-  }
-}
-
 }  // namespace vnf
 using namespace vnf;
 
@@ -239,9 +222,6 @@ extern "C" int vnf_retina_create(const vnf_tensor_desc* weights, int n_weights, 
     r->fin_cnt = r->cnt + B;
     r->status = r->fin_cnt + B;
     r->scratch = r->status + 1;
-    const int lds = RCAP * 8 + RKEEP * 20 + 256 * 20;
-    (void)hipFuncSetAttribute((const void*)retina_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipGetLastError();
     VNF_HIP(hipDeviceSynchronize());
     *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(r));
     return VNF_OK;
@@ -277,8 +257,8 @@ extern "C" int vnf_retina_detect(vnf_handle h, const uint8_t* frames, int b, int
     VNF_HIP(hipMemsetAsync(r->cnt, 0, (2 * (size_t)r->cfg.max_batch + 8) * 4, s));
     hipLaunchKernelGGL(retina_score_kernel, dim3((g.n_anchor + 255) / 256, b), dim3(256), 0, s, g, b, r->cfg.conf_thres, r->cand, r->cnt,
                        r->status);
-    const int lds = RCAP * 8 + RKEEP * 20 + 256 * 20;
-    hipLaunchKernelGGL(retina_select_kernel, dim3(b), dim3(256), lds, s, g, r->cand, r->cnt, r->cfg.topk_bf_nms, r->cfg.nms_thres,
+    allow_dynamic_lds<retina_select_kernel>(LDS_RSELECT);
+    hipLaunchKernelGGL(retina_select_kernel, dim3(b), dim3(256), LDS_RSELECT, s, g, r->cand, r->cnt, r->cfg.topk_bf_nms, r->cfg.nms_thres,
                        r->cfg.keep_top_k, r->cfg.vis_thres, r->fin, r->fin_cnt, r->scratch);
     VNF_HIP(hipGetLastError());
     r->last_b = b;
@@ -288,23 +268,14 @@ extern "C" int vnf_retina_detect(vnf_handle h, const uint8_t* frames, int b, int
     VNF_HIP(hipMemcpyAsync(&hc[b], r->status, 4, hipMemcpyDeviceToHost, s));
     VNF_HIP(hipStreamSynchronize(s));
     if (hc[b] & ST_OVER_IMG) return fail(VNF_E_CAPACITY, "vnf_retina_detect: more than 16384 anchors above conf_thres in a frame");
-    int total = 0, maxf = 0;
-    for (int i = 0; i < b; ++i) { counts[i] = hc[i]; total += hc[i]; maxf = std::max(maxf, hc[i]); }
-    *n_out = total;
-    if (total > max_out) return fail(VNF_E_CAPACITY, "vnf_retina_detect: more faces than max_out");
-    if (total == 0) return VNF_OK;
+    int maxf = 0;
+    rc = count_results("vnf_retina_detect", hc.data(), b, counts, max_out, n_out, &maxf);
+    if (rc != VNF_OK || maxf == 0) return rc;
     std::vector<float> rows((size_t)b * maxf * 15);
     VNF_HIP(hipMemcpy2DAsync(rows.data(), (size_t)maxf * 15 * 4, r->fin, (size_t)RKEEP * 15 * 4, (size_t)maxf * 15 * 4, b,
                              hipMemcpyDeviceToHost, s));
     VNF_HIP(hipStreamSynchronize(s));
-    int o = 0;
-    for (int i = 0; i < b; ++i)
-      for (int k = 0; k < hc[i]; ++k, ++o) {
-        const float* f = &rows[((size_t)i * maxf + k) * 15];
-        if (boxes) memcpy(boxes + (size_t)o * 4, f, 16);
-        if (probs) probs[o] = f[4];
-        if (points) memcpy(points + (size_t)o * 10, f + 5, 40);
-      }
+    scatter_rows(rows.data(), maxf, hc.data(), b, boxes, probs, points);
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
@@ -315,12 +286,7 @@ extern "C" int vnf_retina_results_device(vnf_handle h, int32_t* frame_idx, float
                                          void* stream) {
   Retina* r = handle_cast<Retina>(h);
   if (!r) return fail(VNF_E_INVALID, "not a RetinaFace handle");
-  if (max_out < 0) return fail(VNF_E_INVALID, "vnf_retina_results_device: bad argument");
-  if (r->last_b == 0 || max_out == 0) return VNF_OK;
-  hipLaunchKernelGGL(retina_results_kernel, dim3(r->last_b), dim3(64), 0, (hipStream_t)stream, r->fin, r->fin_cnt, max_out, frame_idx,
-                     boxes, probs, points);
-  VNF_HIP(hipGetLastError());
-  return VNF_OK;
+  return results_device("vnf_retina_results_device", r->fin, r->fin_cnt, r->last_b, RKEEP, frame_idx, boxes, probs, points, max_out, stream);
 }
 
 // staged parity: raw head outputs of pyramid level `level` of the last detection as a host (b, fh, fw, 32) fp32 array

@@ -14,14 +14,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .detector import MTCNN
+from .detector import _Detector
 
 
 def remove_prefix(state_dict, prefix):
     return {(k.split(prefix, 1)[-1] if k.startswith(prefix) else k): v for k, v in state_dict.items()}
 
 
-class RetinaFace:
+class RetinaFace(_Detector):
     """RetinaFace (mobilenet0.25) detector plugin (/root/reference/models/retina_face.py:56-232).
 
     Limits of the device tables (reference-legal inputs beyond them fail loudly, never truncate): at most 16 384 anchors
@@ -30,6 +30,7 @@ class RetinaFace:
     checkpoint exists offline; the reference's cfg points at /content/...): boxes are then meaningless -- a
     RuntimeWarning says so; pass `synthetic=True` (benchmarks, tests) to acknowledge it."""
     channels_subtract = (104, 117, 123)
+    _detect_fn, _results_fn = "vnf_retina_detect", "vnf_retina_results_device"
 
     def __init__(self, backbone_cfg="cfg_mnet", phase="test", backbone_path=None, device="cuda:0", conf_thres=0.02,
                  topk_bf_nms=5000, keep_top_k=750, nms_thres=0.4, vis_thres=0.6, checkpoint_path=None, state_dict=None,
@@ -50,9 +51,6 @@ class RetinaFace:
         if compute_dtype not in ("f32", "f16x2"):
             raise ValueError("RetinaFace compute_dtype: 'f32' (exact, default) or 'f16x2' (split-f16, ~15 %% faster), got %r" % (compute_dtype,))
         self.compute_dtype = compute_dtype
-        self._handle = None
-        self._handle_key = None
-        self._frames = None
         if state_dict is not None:
             self._sd = remove_prefix(dict(state_dict), "module.")
         elif checkpoint_path is not None:
@@ -74,24 +72,6 @@ class RetinaFace:
             d = d["state_dict"]
         self._sd = remove_prefix(d, "module.")
         self._drop()
-
-    def eval(self):
-        return self
-
-    def to(self, device):
-        self.device = torch.device(device)
-        return self
-
-    def __del__(self):
-        try:
-            self._drop()
-        except Exception:
-            pass
-
-    def _drop(self):
-        if self._handle is not None:
-            _lib.load().vnf_destroy(self._handle)
-            self._handle = None
 
     def _ensure(self, b, h, w):
         if self.device.type != "cuda":
@@ -117,49 +97,10 @@ class RetinaFace:
         self._handle, self._handle_key = h_, key
         return h_
 
-    _to_device_frames = MTCNN._to_device_frames   # same input forms (list of HWC arrays, (B,H,W,3) array / tensor)
-
-    def last_frames_device(self):
-        return self._frames
-
     def detect_device(self, frames):
         """frames: (B,H,W,3) u8 cuda.  Returns (counts list, boxes (n,4), scores (n,), points (n,5,2)) on host."""
-        b, h, w, _ = frames.shape
-        hd = self._ensure(b, h, w)
-        lib = _lib.load()
-        cap = b * self.keep_top_k       # a frame never returns more rows than keep_top_k: one call, no capacity retry
-        while True:
-            counts = np.zeros(b, dtype=np.int32)
-            boxes = np.empty((cap, 4), dtype=np.float32)
-            probs = np.empty((cap,), dtype=np.float32)
-            points = np.empty((cap, 10), dtype=np.float32)
-            n_out = ctypes.c_int32(0)
-            with torch.cuda.device(frames.device):
-                rc = lib.vnf_retina_detect(hd, ctypes.c_void_p(frames.data_ptr()), b, h, w, counts.ctypes.data,
-                                           boxes.ctypes.data, probs.ctypes.data, points.ctypes.data, cap,
-                                           ctypes.byref(n_out), _lib.current_stream_ptr())
-            if rc == -4 and n_out.value > cap:
-                cap = int(n_out.value)
-                continue
-            _lib.check(rc)
-            n = n_out.value
-            return counts.tolist(), boxes[:n], probs[:n], points[:n].reshape(n, 5, 2)
-
-    def results_device(self, n, device=None):
-        """Device-resident copy of the last detect_device(): (frame_idx, boxes, scores, points (n,10)) cuda tensors."""
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        fidx = torch.empty((n,), dtype=torch.int32, device=dev)
-        boxes = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        probs = torch.empty((n,), dtype=torch.float32, device=dev)
-        points = torch.empty((n, 10), dtype=torch.float32, device=dev)
-        if n:
-            if self._handle is None:
-                raise RuntimeError("results_device(): no detection has run on this detector yet")
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().vnf_retina_results_device(
-                    self._handle, ctypes.c_void_p(fidx.data_ptr()), ctypes.c_void_p(boxes.data_ptr()),
-                    ctypes.c_void_p(probs.data_ptr()), ctypes.c_void_p(points.data_ptr()), n, _lib.current_stream_ptr()))
-        return fidx, boxes, probs, points
+        # a frame never returns more rows than keep_top_k: one call, no capacity retry
+        return self._detect_device(frames, frames.shape[0] * self.keep_top_k)
 
     def inference(self, rgb_images, landmark=True):
         """retina_face.py:156-232: rgb_images = an iterable of equal-size HWC RGB images (a single image is NOT
