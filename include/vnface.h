@@ -25,6 +25,8 @@
  *   vnf_emotion_recognize            demo_image.py:79-110 (recognize_emotion: transform, forward, top-k)
  *   vnf_augment_faces                data_loader/__init__.py:58-65 (transforms_facenet_aug) as
  *                                    trainer/online_aug_trainer.py:22-33 consumes it per batch
+ *   vnf_extract_faces                models/mtcnn.py:458-509 (MTCNN.extract) +
+ *                                    models/mtcnn_utils/detect_face.py:309-377 (crop_resize, extract_face)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -309,6 +311,27 @@ int vnf_retina_debug_heads(vnf_handle h, int level, int b, float* host_out, int6
 int vnf_align(const uint8_t* frames, int b, int height, int width, const int32_t* frame_idx,
               const float* boxes, const float* points, int n, const float* template5x2, int s,
               uint8_t* faces_u8, void* faces_norm, int norm_dtype, void* stream);
+
+/* face extraction -------------------------------------------------------------------------- */
+/* MTCNN.extract / extract_face (models/mtcnn.py:458-509, models/mtcnn_utils/detect_face.py:309-377, tensor path):
+ * row r is the rectangle rects[r] = {frame, x1, y1, x2, y2} (pixels [y1,y2) x [x1,x2) of that frame; the margin
+ * arithmetic of detect_face.py:358-368 is the caller's, detector.crop_rects) resampled to s x s as
+ * interpolate(mode="area") does (detect_face.py:304-306,317-322: bin of output (oy,ox) = rows [oy*ch/s, ceil((oy+1)*ch/s)),
+ * columns alike, also when up-sampling), truncated to a byte (.byte()): integer sums and one IEEE fp32 division.
+ *   frames: device (B,H,W,3) u8; rects: device (n,5) int32;
+ *   x_out: device (n,3,s,s) of out_dtype VNF_F32 | VNF_BF16 | VNF_F16 (the fp32 value rounded to nearest-even), may be
+ *          NULL: float(byte) (detect_face.py:376), or (byte - 127.5) / 128 with standardize != 0 (mtcnn.py:516-518);
+ *   u8_out: device (n,s,s,3) bytes, may be NULL.
+ * One launch, no workspace, nothing allocated, no synchronisation.  n == 0: no-op.  s outside 1..1024, NULL frames or
+ * rects with n > 0, a bad out_dtype or both outputs NULL: VNF_E_INVALID.  rects live in device memory, so the call
+ * cannot see their values: a row whose frame index is outside 0..B-1, whose rectangle is empty or leaves the frame, or
+ * whose bins reach 2^15 pixels ((ceil(ch/s)+1) * (ceil(cw/s)+1), the bound under which every correctly rounded
+ * quotient truncates to the same byte) is written as zeros and reads nothing; the host layer checks all of it before it
+ * uploads the table. */
+int vnf_extract_faces(const uint8_t* frames, int b, int height, int width,
+                      const int32_t* rects /* device (n,5): frame, x1, y1, x2, y2 */, int n, int s,
+                      int standardize, void* x_out /* (n,3,s,s) */, int out_dtype /* VNF_F32|VNF_BF16|VNF_F16 */,
+                      uint8_t* u8_out /* (n,s,s,3) */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,7 @@ SIGNATURES = {
     "vnf_retina_results_device": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "vnf_retina_debug_heads": (_I, [_P, _I, _I, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
     "vnf_align": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "vnf_extract_faces": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
 }
 
 
