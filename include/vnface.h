@@ -27,6 +27,11 @@
  *                                    trainer/online_aug_trainer.py:22-33 consumes it per batch
  *   vnf_extract_faces                models/mtcnn.py:458-509 (MTCNN.extract) +
  *                                    models/mtcnn_utils/detect_face.py:309-377 (crop_resize, extract_face)
+ *   vnf_encoder_create_classifier / vnf_encoder_logprobs
+ *                                    models/inception_resnet_v1.py:202-216,260-265,298-300 (classify=True) and
+ *                                    models/iresnet_encoder.py:100-103,155-157,174-179 (n_classes)
+ *   vnf_logits_eval                  trainer/classification_trainer.py:42-80 (_validate_epoch: nll_loss, accuracy,
+ *                                    argmax / exp for the result rows) + trainer/base_trainer.py:177-200 (eval)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -118,6 +123,35 @@ int vnf_encoder_set_streams(vnf_handle h, int max_streams);
  * Each call stays ordered on the stream it was given.  Extra sets are allocated at first use (~2 GB for IRv1 at
  * max_batch 256).  Default 1. */
 int vnf_encoder_set_contexts(vnf_handle h, int n);
+
+/* encoders with their own classification head ----------------------------------------------- */
+/* InceptionResnetV1(classify=True, num_classes=C) (inception_resnet_v1.py:202-216,260-265,298-300) and
+ * iresnet100(n_classes=C) (iresnet_encoder.py:100-103,155-157): vnf_encoder_create plus the `logits` layer, so weights
+ * must also hold logits.weight (num_classes,512) and logits.bias (num_classes); VNF_E_MISSING names the absent one.
+ * (vnf_encoder_create ignores logits.* and builds no head.)  The head reads the fp32 features the plan leaves before its
+ * last op -- last_bn's output before the L2 normalisation for IRv1, `features` for IR-100 -- and is one exact-f32
+ * linear layer in every compute_dtype.  Everything else about the handle is as vnf_encoder_create makes it: vnf_embed
+ * returns the same embeddings. */
+int vnf_encoder_create_classifier(int arch, const vnf_tensor_desc* weights, int n_weights, int compute_dtype,
+                                  int max_batch, int num_classes, vnf_handle* out);
+/* forward() of a classify model (inception_resnet_v1.py:298-300 F.log_softmax, iresnet_encoder.py:155-157): the plan,
+ * the head, then vnf_logits_eval's row kernel, enqueued on `stream` with no host synchronisation.  x as for vnf_embed.
+ * logp_out: device (N,num_classes) fp32; amax_out: device (N) int32; prob_out: device (N) fp32; each may be NULL.
+ * N > max_batch: VNF_E_CAPACITY; a handle without a head: VNF_E_INVALID; N == 0: no-op. */
+int vnf_encoder_logprobs(vnf_handle h, const void* x, int n, int x_dtype, float* logp_out, int32_t* amax_out,
+                         float* prob_out, void* stream);
+/* What a validation step does with a batch of logits (trainer/classification_trainer.py:42-80, losses/metrics.py:3-7):
+ * logits device (n,c) fp32 with row stride ld >= c; target device (n) int64, may be NULL when nll, hit and sums are.
+ * Outputs, all device, each may be NULL:
+ *   logp (n,c)  log_softmax over the row (max-subtracted)      amax (n) int32  first index of the row maximum
+ *   prob (n)    exp(logp[amax])                                nll (n)         -logp[target]
+ *   hit (n) int32  amax == target                              sums (2)        {sum nll, sum hit}
+ * sums are added in index order by a second launch, without float atomics: the same bits on every run, equal to the
+ * fp32 sum of the nll / hit rows taken one after the other.  The call cannot see the targets: one outside [0, c) is
+ * never used as an index, its row gets nll = +inf and hit = 0 (the host layer checks targets before it uploads them).
+ * n == 0: no-op.  No workspace, nothing allocated, no synchronisation. */
+int vnf_logits_eval(const float* logits, int n, int c, int ld, const int64_t* target, float* logp, int32_t* amax,
+                    float* prob, float* nll, int32_t* hit, float* sums, void* stream);
 
 /* emotion network --------------------------------------------------------------------------- */
 /* models/resnet_2_branch.py:12-89: ResNet-50 (Bottleneck 3-4-6-3) on 224x224 inputs with two linear heads, fc

@@ -50,6 +50,9 @@ SIGNATURES = {
     "vnf_encoder_flops": (_I, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "vnf_encoder_set_streams": (_I, [_P, _I]),
     "vnf_encoder_set_contexts": (_I, [_P, _I]),
+    "vnf_encoder_create_classifier": (_I, [_I, ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "vnf_encoder_logprobs": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "vnf_logits_eval": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vnf_emotion_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vnf_emotion_forward": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "vnf_emotion_recognize": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -3,6 +3,8 @@
   MLPModel            <-  /root/reference/models/mlp_model.py:4-15
   load_model_classify <-  /root/reference/demo_image.py:16-21   (checkpoint dict of
                           trainer/base_trainer.py:91-98: needs 'epoch' and 'state_dict')
+  check_targets / logits_eval <- /root/reference/trainer/classification_trainer.py:42-80 (what _validate_epoch does
+                          with a batch of model outputs: nll_loss, accuracy, argmax, exp)
 """
 import ctypes
 from collections import OrderedDict
@@ -115,3 +117,70 @@ def load_model_classify(checkpoint_path, model):
     print("Loading checkpoint: {} ... after training for {} epochs.".format(checkpoint_path, cp['epoch']))
     model.load_state_dict(cp['state_dict'])
     return model
+
+
+def check_targets(target, num_classes):
+    """Class labels of a batch as an int64 CPU tensor, checked on the host before they are uploaded: the device kernels
+    cannot refuse a label, torch's nll_loss raises on one outside [0, C) (trainer/classification_trainer.py:53)."""
+    t = torch.as_tensor(target).detach().cpu()
+    if t.numel() == 0:      # an empty list comes as float32
+        return torch.zeros((0,), dtype=torch.int64)
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("class labels must be integers, got %s" % t.dtype)
+    t = t.to(torch.int64).reshape(-1)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= int(num_classes)):
+        bad = int(t.max()) if int(t.max()) >= int(num_classes) else int(t.min())
+        raise IndexError("Target %d is out of bounds." % bad)
+    return t
+
+
+_EVAL_OUTPUTS = ("logp", "amax", "prob", "nll", "hit", "sums")
+
+
+def logits_eval(logits, target=None, want=("amax", "prob", "nll", "hit", "sums")):
+    """vnf_logits_eval on a cuda (n,C) fp32 matrix of logits (or log-probabilities: log_softmax leaves them as they are,
+    up to rounding) whose rows may be strided.  target: integer labels, checked on the host by check_targets before
+    they reach the device.  Returns {name: cuda tensor} for the names in `want`:
+    logp (n,C), amax (n) int32, prob (n), nll (n), hit (n) int32, sums (2) = {sum nll, sum hit}."""
+    if logits.device.type != "cuda":
+        raise RuntimeError("logits_eval runs on MI355X only: the logits must live on a cuda device (there is no CPU path)")
+    unknown = set(want) - set(_EVAL_OUTPUTS)
+    if unknown:
+        raise ValueError("unknown outputs: %s" % sorted(unknown))
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("expected (n,C) fp32 logits, got %s %s" % (tuple(logits.shape), logits.dtype))
+    n, c = int(logits.shape[0]), int(logits.shape[1])
+    if c < 1:
+        raise ValueError("logits need at least one column")
+    if logits.stride(1) != 1 or (n > 1 and logits.stride(0) < c):
+        logits = logits.contiguous()
+    ld = int(logits.stride(0)) if n > 1 else c
+    needs_t = [k for k in ("nll", "hit", "sums") if k in want]
+    if needs_t and target is None:
+        raise ValueError("%s need a target" % ", ".join(needs_t))
+    t = None
+    if target is not None:
+        t = check_targets(target, c).to(logits.device)
+        if t.numel() != n:
+            raise ValueError("%d targets for %d rows" % (t.numel(), n))
+    dev = logits.device
+    out = {}
+    if "logp" in want:
+        out["logp"] = torch.empty((n, c), dtype=torch.float32, device=dev)
+    if "amax" in want:
+        out["amax"] = torch.empty((n,), dtype=torch.int32, device=dev)
+    for k in ("prob", "nll"):
+        if k in want:
+            out[k] = torch.empty((n,), dtype=torch.float32, device=dev)
+    if "hit" in want:
+        out["hit"] = torch.empty((n,), dtype=torch.int32, device=dev)
+    if "sums" in want:
+        out["sums"] = torch.zeros((2,), dtype=torch.float32, device=dev)
+
+    def ptr(k):
+        return ctypes.c_void_p(out[k].data_ptr()) if k in out else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().vnf_logits_eval(
+            ctypes.c_void_p(logits.data_ptr()), n, c, ld, ctypes.c_void_p(t.data_ptr()) if t is not None else None,
+            ptr("logp"), ptr("amax"), ptr("prob"), ptr("nll"), ptr("hit"), ptr("sums"), _lib.current_stream_ptr()))
+    return out

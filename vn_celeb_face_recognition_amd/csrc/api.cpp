@@ -2,7 +2,7 @@
 #include <cstring>
 #include <new>
 
-#include "engine.h"
+#include "plan.h"
 
 using namespace vnf;
 
@@ -69,6 +69,82 @@ int vnf_encoder_create(int arch, const vnf_tensor_desc* weights, int n_weights, 
   return create_encoder(arch, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
     return arch == VNF_ARCH_IRV1 ? build_irv1(e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(e, wm) : fail(VNF_E_INVALID, "unknown arch");
   });
+  API_GUARD_END
+}
+
+// `logits` (num_classes, 512) + bias on the encoder's fp32 features: an exact-f32 linear plan of its own, whatever the
+// encoder computes in (inception_resnet_v1.py:260-265,298-300; iresnet_encoder.py:100-103,155-157)
+static int attach_head(Encoder& e, WeightMap& wm, int num_classes) {
+  const float* w = wm.get("logits.weight", (int64_t)num_classes * 512);
+  const float* b = wm.get("logits.bias", num_classes);
+  if (!w || !b) return fail(VNF_E_MISSING, "vnf_encoder_create_classifier: missing weight: " + wm.missing);
+  Encoder* hd = new Encoder();
+  e.head = hd;   // owned from here on: ~Encoder deletes it
+  e.head_classes = num_classes;
+  const int cpad = (num_classes + 7) / 8 * 8;
+  hd->dtype = F32; hd->max_batch = e.max_batch; hd->in_size = 1; hd->arch = ARCH_MLP; hd->device = e.device;
+  hd->max_streams = 1;
+  e.head_in = hd->add_buf(1, 1, 512);
+  e.head_logit = hd->add_buf(1, 1, cpad);
+  int r = add_linear(*hd, "logits", w, b, 512, num_classes, cpad, e.head_in, e.head_logit, ACT_NONE);
+  if (r == VNF_OK) r = hd->finalize();
+  if (r != VNF_OK) return r;
+  e.head_emb = (float*)e.dalloc((size_t)e.max_batch * 512 * 4);
+  return e.head_emb ? VNF_OK : VNF_E_HIP;
+}
+
+int vnf_encoder_create_classifier(int arch, const vnf_tensor_desc* weights, int n_weights, int compute_dtype, int max_batch,
+                                  int num_classes, vnf_handle* out) {
+  API_GUARD_BEGIN
+  if (num_classes < 1 || num_classes > (1 << 20)) return fail(VNF_E_INVALID, "vnf_encoder_create_classifier: num_classes must be 1..2^20");
+  return create_encoder(arch, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
+    const int r = arch == VNF_ARCH_IRV1 ? build_irv1(e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(e, wm) : fail(VNF_E_INVALID, "unknown arch");
+    return r != VNF_OK ? r : attach_head(e, wm, num_classes);
+  });
+  API_GUARD_END
+}
+
+int vnf_encoder_logprobs(vnf_handle h, const void* x, int n, int x_dtype, float* logp_out, int32_t* amax_out, float* prob_out,
+                         void* stream) {
+  API_GUARD_BEGIN
+  Encoder* e = handle_cast<Encoder>(h);
+  if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
+  if (!e->head) return fail(VNF_E_INVALID, "vnf_encoder_logprobs: the handle has no classification head (vnf_encoder_create_classifier)");
+  if (n < 0 || (n > 0 && !x)) return fail(VNF_E_INVALID, "bad argument");
+  if (x_dtype != VNF_F32 && x_dtype != VNF_BF16 && x_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad x_dtype");
+  if (n > e->max_batch) return fail(VNF_E_CAPACITY, "batch exceeds max_batch");
+  if (n == 0) return VNF_OK;
+  hipStream_t s = (hipStream_t)stream;
+  Encoder& hd = *e->head;
+  if (e->head_done) VNF_HIP(hipStreamWaitEvent(s, e->head_done, 0));
+  else VNF_HIP(hipEventCreateWithFlags(&e->head_done, hipEventDisableTiming));
+  int r = e->run(x, n, x_dtype, e->head_emb, s);
+  if (r != VNF_OK) return r;
+  // emb_raw is the feature buffer of the activation context this run used: last_bn's output before the normalisation
+  // (IRv1), `features` (IR-100)
+  VNF_HIP(hipMemcpyAsync(hd.bufs[e->head_in].ptr, e->emb_raw, (size_t)n * 512 * 4, hipMemcpyDeviceToDevice, s));
+  if (e->n_ctx > 1) {   // the context is free again only after this copy
+    const int c = (e->next_ctx + e->n_ctx - 1) % e->n_ctx;
+    VNF_HIP(hipEventRecord(e->ctx_ev[c], s));
+  }
+  r = hd.run(nullptr, n, VNF_F32, nullptr, s);
+  if (r != VNF_OK) return r;
+  VNF_HIP(launch_head_eval((const float*)hd.bufs[e->head_logit].ptr, hd.bufs[e->head_logit].C, e->head_classes, n, nullptr, logp_out,
+                           amax_out, prob_out, nullptr, nullptr, nullptr, s));
+  VNF_HIP(hipEventRecord(e->head_done, s));
+  return VNF_OK;
+  API_GUARD_END
+}
+
+int vnf_logits_eval(const float* logits, int n, int c, int ld, const int64_t* target, float* logp, int32_t* amax, float* prob,
+                    float* nll, int32_t* hit, float* sums, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0 || c < 1 || ld < c) return fail(VNF_E_INVALID, "vnf_logits_eval: need n >= 0, c >= 1, ld >= c");
+  if (n == 0) return VNF_OK;
+  if (!logits) return fail(VNF_E_INVALID, "vnf_logits_eval: logits must not be NULL");
+  if (!target && (nll || hit || sums)) return fail(VNF_E_INVALID, "vnf_logits_eval: nll, hit and sums need a target");
+  VNF_HIP(launch_head_eval(logits, ld, c, n, target, logp, amax, prob, nll, hit, sums, (hipStream_t)stream));
+  return VNF_OK;
   API_GUARD_END
 }
 

@@ -163,6 +163,8 @@ Encoder::~Encoder() {
   if (fork_ev) (void)hipEventDestroy(fork_ev);
   for (hipEvent_t ev : ctx_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (head_done) (void)hipEventDestroy(head_done);
+  delete head;
 }
 
 int Encoder::select_ctx(hipStream_t s, int* used) {

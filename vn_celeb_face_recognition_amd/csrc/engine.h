@@ -192,6 +192,12 @@ struct Encoder : HandleBase {
   int n_cls = 0, n_proj = 0;
   float* cls_buf = nullptr;
   double macs_alg = 0, macs_exec = 0;
+  // classification head of an IRv1 / IR-100 handle (vnf_encoder_create_classifier): `logits`, one linear layer on the
+  // fp32 features in emb_raw, as an exact-f32 plan of its own like the MLP's; nullptr: no head
+  Encoder* head = nullptr;
+  int head_classes = 0, head_in = -1, head_logit = -1;
+  float* head_emb = nullptr;         // (max_batch,512): where vnf_encoder_logprobs lets the plan's last op write
+  hipEvent_t head_done = nullptr;    // orders calls on different streams over the head's one buffer set
 
   int add_buf(int H, int W, int C);
   // image n0 of a buffer, at channel `coff` (at_f32: the fp32 / split-f16 pair plans, 4-byte elements)

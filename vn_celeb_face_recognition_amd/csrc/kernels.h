@@ -103,6 +103,12 @@ hipError_t launch_l2norm(const float* x, float* y, int n, int C, hipStream_t s);
 hipError_t launch_logsoftmax_argmax(const float* logits, int ld, int C, int n, float* logp, int32_t* amax, float* prob,
                                     hipStream_t s);
 
+// launch_logsoftmax_argmax plus the targets' side (head_eval.hip): nll[r] = -logp[r][target[r]], hit[r] = argmax == target,
+// sums = {sum nll, sum hit} added in index order.  Every output may be NULL; target may be NULL when nll, hit and sums are.
+// A target outside [0, C) is never an index: nll = +inf, hit = 0.
+hipError_t launch_head_eval(const float* logits, int ld, int C, int n, const int64_t* target, float* logp, int32_t* amax,
+                            float* prob, float* nll, int32_t* hit, float* sums, hipStream_t s);
+
 // depthwise 3x3 convolution, padding 1, stride 1 or 2, fp32 NHWC (C % 4 == 0): y = leaky(sum_t x[tap t] * w[t][c] + bias[c])
 // (retina_face_utils/components.py:30-40 conv_dw, first half; BatchNorm folded into w / bias)
 // (split: the tensors hold split-f16 pairs in their 32-bit elements -- F16X2 plans -- instead of fp32; same for the

@@ -6,6 +6,9 @@
 Same constructor kwargs, `.to()`, `.eval()`, `load_state_dict()`, and `__call__((N,3,S,S)) ->
 (N,512)` on the same device (demo_image.py:30-34, find_embedding.py:58).  All arithmetic runs in
 hand-written HIP kernels; torch only owns the input/output device memory and the stream.
+With their own `logits` head (InceptionResnetV1(classify=True, ...), iresnet100(n_classes=...):
+inception_resnet_v1.py:260-265,298-300, iresnet_encoder.py:100-103,155-157) the models return (N,C)
+log-probabilities, `.logprobs(x)` adds argmax and probability, `.embed(x)` still gives the embeddings.
 There is no CPU path: calling a model that is not on a CUDA(ROCm) device raises.
 """
 import ctypes
@@ -45,6 +48,7 @@ class _Encoder:
 
     def __init__(self, device=None, compute_dtype="f16x2", max_batch=256):
         self._sd = None
+        self._num_classes = None    # width of the model's own `logits` head; None: an embedding model
         self._handle = None
         self._handle_key = None
         self.compute_dtype = compute_dtype
@@ -53,6 +57,11 @@ class _Encoder:
         self.device = torch.device("cpu")
         if device is not None:
             self.to(device)
+
+    @property
+    def head_classes(self):
+        """Width of the model's own `logits` head, or None for an embedding model."""
+        return self._num_classes
 
     # ---- nn.Module surface used by the reference's callers
     def eval(self):
@@ -83,6 +92,10 @@ class _Encoder:
         missing = [k for k in expected if k not in state_dict]
         if strict and missing:
             raise RuntimeError("Missing key(s) in state_dict: %s" % ", ".join(missing[:8]))
+        if self._num_classes is not None and "logits.weight" in state_dict:
+            shp = tuple(state_dict["logits.weight"].shape)
+            if shp != (self._num_classes, 512):
+                raise RuntimeError("size mismatch for logits.weight: %s vs %s" % (shp, (self._num_classes, 512)))
         sd = OrderedDict(self._sd) if (self._sd is not None and not strict) else OrderedDict()
         for k, v in state_dict.items():
             sd[k] = v
@@ -108,7 +121,7 @@ class _Encoder:
         if self.device.type != "cuda":
             raise RuntimeError("%s runs on MI355X only: move it to a cuda device (there is no CPU path)"
                                % type(self).__name__)
-        key = (self.device.index or 0, self.compute_dtype, self.max_batch)
+        key = (self.device.index or 0, self.compute_dtype, self.max_batch, self._num_classes)
         if self._handle is not None and self._handle_key == key:
             return self._handle
         self._drop_handle()
@@ -124,18 +137,51 @@ class _Encoder:
         return h
 
     def _create(self, lib, descs, n, h):
+        if self._num_classes is not None:
+            return lib.vnf_encoder_create_classifier(self._arch, descs, n, _DTYPES[self.compute_dtype], self.max_batch,
+                                                     self._num_classes, ctypes.byref(h))
         return lib.vnf_encoder_create(self._arch, descs, n, _DTYPES[self.compute_dtype], self.max_batch, ctypes.byref(h))
 
     def __call__(self, x):
         return self.forward(x)
 
-    def forward(self, x):
-        h = self._ensure_handle()
+    def _checked_input(self, x):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.input_size or x.shape[3] != self.input_size:
             raise ValueError("expected (N,3,%d,%d) input, got %s" % (self.input_size, self.input_size, tuple(x.shape)))
         if x.device.type != "cuda":
             raise RuntimeError("input tensor must live on the encoder's cuda device")
-        x = x.contiguous()
+        return x.contiguous()
+
+    def forward(self, x):
+        """(N,3,S,S) -> (N,512) embeddings; a model with its own head (classify=True / n_classes): (N,C) log-probabilities."""
+        if self._num_classes is not None:
+            return self.logprobs(x)[0]
+        return self.embed(x)
+
+    def logprobs(self, x):
+        """Model with a `logits` head: (N,3,S,S) cuda -> (logp (N,C) fp32, argmax (N,) int32, prob (N,) fp32 = exp(logp[argmax])),
+        all cuda (vnf_encoder_logprobs)."""
+        if self._num_classes is None:
+            raise RuntimeError("%s was built without a classification head (classify=True / n_classes)" % type(self).__name__)
+        h = self._ensure_handle()
+        x = self._checked_input(x)
+        n = x.shape[0]
+        logp = torch.empty((n, self._num_classes), dtype=torch.float32, device=x.device)
+        amax = torch.empty((n,), dtype=torch.int32, device=x.device)
+        prob = torch.empty((n,), dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        with torch.cuda.device(x.device):
+            for n0 in range(0, n, self.max_batch):
+                nn = min(self.max_batch, n - n0)
+                _lib.check(lib.vnf_encoder_logprobs(h, ctypes.c_void_p(x[n0:n0 + nn].data_ptr()), nn, _lib.torch_dtype_code(x.dtype),
+                                                    ctypes.c_void_p(logp[n0:].data_ptr()), ctypes.c_void_p(amax[n0:].data_ptr()),
+                                                    ctypes.c_void_p(prob[n0:].data_ptr()), _lib.current_stream_ptr()))
+        return logp, amax, prob
+
+    def embed(self, x):
+        """(N,3,S,S) cuda -> (N,512) fp32 embeddings (vnf_embed), head or no head."""
+        h = self._ensure_handle()
+        x = self._checked_input(x)
         n = x.shape[0]
         out = torch.empty((n, 512), dtype=torch.float32, device=x.device)
         lib = _lib.load()
@@ -176,7 +222,7 @@ class _Encoder:
             s_ = streams[i % lanes]
             with torch.cuda.stream(s_):
                 x = x.to(dev, non_blocking=True)
-                emb = self(x)
+                emb = self.embed(x)
                 ev = s_.record_event()
             x.record_stream(s_)
             inflight.append((i, emb, ev))
@@ -231,6 +277,10 @@ class InceptionResnetV1(_Encoder):
     torch's random init); 'vggface2' / 'casia-webface' -> the file the reference caches under
     $TORCH_HOME/checkpoints (never downloaded here); or a path to a local state_dict file
     (build extension).
+
+    classify=True: the model ends in its `logits` layer and returns log-probabilities.  With num_classes the head is a
+    fresh generator-seeded (num_classes, 512) layer (the reference: torch's random init) until load_state_dict brings a
+    trained one; without it the head is the pretrained file's own.  The head runs in exact fp32 in every compute_dtype.
     """
     _arch = _lib.VNF_ARCH_IRV1
     input_size = 160
@@ -238,8 +288,9 @@ class InceptionResnetV1(_Encoder):
 
     def __init__(self, pretrained=None, classify=False, num_classes=None, dropout_prob=0.6, device=None,
                  compute_dtype="f16x2", max_batch=256, seed=0):
-        if classify:
-            raise NotImplementedError("classify=True (logits head) is not on the inference hot path")
+        if pretrained is None and classify and num_classes is None:
+            # inception_resnet_v1.py:214-215
+            raise Exception('If "pretrained" is not specified and "classify" is True, "num_classes" must be specified')
         self.pretrained = pretrained
         self.classify = classify
         self.num_classes = num_classes
@@ -255,12 +306,25 @@ class InceptionResnetV1(_Encoder):
                     "pretrained weights %r not found at %s (no network: place the file there or pass a local path)"
                     % (pretrained, path))
             self.load_state_dict(_load_checkpoint_file(path), strict=False)
+        if classify:
+            if num_classes is not None:
+                # a fresh head (inception_resnet_v1.py:264-265 replaces the file's, whatever its width): the reference
+                # leaves torch's random init, here the generator's draw; load_state_dict replaces it
+                head = generate_state_dict("irv1", seed, num_classes=int(num_classes))
+                self._sd["logits.weight"], self._sd["logits.bias"] = head["logits.weight"], head["logits.bias"]
+                self._num_classes = int(num_classes)
+            else:
+                # the file's own head (:260-262: 8631 classes for vggface2, 10575 for casia-webface)
+                if "logits.weight" not in self._sd or "logits.bias" not in self._sd:
+                    raise RuntimeError("classify=True without num_classes needs the `logits` layer of the pretrained file: %r "
+                                       "has none" % (pretrained,))
+                self._num_classes = int(self._sd["logits.weight"].shape[0])
         if device is not None:
             self.to(device)
 
     def _spec(self):
         from .weights import irv1_spec
-        return irv1_spec()
+        return irv1_spec(num_classes=self._num_classes)
 
 
 class _IResNet100(_Encoder):
@@ -269,21 +333,26 @@ class _IResNet100(_Encoder):
 
     def _spec(self):
         from .weights import iresnet_spec
-        return iresnet_spec()
+        return iresnet_spec(n_classes=self._num_classes)
 
 
 def iresnet100(pretrained=False, progress=True, freeze_weights=False, checkpoint_path="", compute_dtype="f16x2",
-               max_batch=256, seed=0, **kwargs):
+               max_batch=256, seed=0, n_classes=None, **kwargs):
     """Drop-in for models.iresnet100 (iresnet_encoder.py:162-181,194-196); kwargs of
     cfg/embedding/iresnet100_enc.json.  pretrained=True needs checkpoint_path (a file holding
-    {'state_dict': ...}); the URL branch of the reference cannot run offline."""
+    {'state_dict': ...}); the URL branch of the reference cannot run offline.  n_classes (iresnet_encoder.py:100-103):
+    the model gets a `logits` layer (generator weights until a checkpoint brings its own) and returns log-probabilities."""
     if kwargs:
         raise TypeError("unexpected keyword arguments: %s" % sorted(kwargs))
     m = _IResNet100(compute_dtype=compute_dtype, max_batch=max_batch)
-    m._sd = generate_state_dict("iresnet100", seed)
+    if n_classes is not None:
+        m._num_classes = int(n_classes)
+    m._sd = generate_state_dict("iresnet100", seed, n_classes=m._num_classes)
     if pretrained:
         if not checkpoint_path:
             raise FileNotFoundError("iresnet100(pretrained=True) needs checkpoint_path: no network access")
         print("Loaded encoder state dict from checkpoint path {}".format(checkpoint_path))
         m.load_state_dict(_load_checkpoint_file(checkpoint_path), strict=False)
+    if freeze_weights and n_classes is not None:
+        print("Freezing weights !")    # iresnet_encoder.py:174-179: only `logits` would train; nothing trains here
     return m

@@ -10,10 +10,15 @@ the optimisation step itself in libvnface.so (csrc/mlp_train.hip):
   AugClassificationTrainer <- /root/reference/trainer/online_aug_trainer.py:6-97 (images -> augmentation -> frozen
                              encoder -> MLP step, all on the device: augment.py, csrc/augment.hip)
 
+  EvalModel, write_result_csv, ClassificationTrainer.eval
+                          <- /root/reference/trainer/base_trainer.py:177-200, classification_trainer.py:42-80 (evaluation of
+                             a trained model: MLPModel or an encoder with its own head; csrc/head_eval.hip)
+
 Same config keys (cfg/train_cfg_emb_classify.json), same checkpoint dict (base_trainer.py:83-105: arch, epoch,
 state_dict, optimizer in torch.optim.Adam's state_dict layout, monitor_best, config), same log_loss.txt.  torch is
 plumbing: the DataLoader / sampler (batch order), the initial weights (nn.Linear's init) and the dropout draws come from
 torch's CPU generator in the reference's order, so a run seeded like train.py:16-20 follows the reference's loss curve."""
+import csv
 import ctypes
 import json
 import logging
@@ -222,6 +227,73 @@ class TrainableMLP:
             self._step_count(int(float(osd["state"][0]["step"])))
 
 
+class EvalModel:
+    """A trained model under evaluation (eval.py): an inference MLPModel (classifier.py) or an encoder with its own
+    `logits` head (encoders.py), anything that maps a cuda batch to cuda (n,C) log-probabilities.  evaluate() is the
+    device step of _validate_epoch (classification_trainer.py:50-72): log-probabilities + targets -> the batch sums
+    and, when asked, the per-row prediction and probability (vnf_logits_eval); the (n,C) matrix stays on the device."""
+
+    def __init__(self, model, num_classes, device="cuda:0"):
+        self.model, self.num_classes = model, int(num_classes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("evaluation runs on MI355X only (there is no CPU path)")
+        self.model.to(self.device)
+        self.model.eval()
+        self.training = False
+        self.input_size = getattr(model, "input_size", None)   # encoders: side of the images they take
+        cd = getattr(model, "compute_dtype", None)
+        self.x_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}.get(cd, torch.float32)
+
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("EvalModel evaluates; train.py trains (TrainableMLP)")
+        return self
+
+    def to(self, device):
+        return self
+
+    def state_dict(self):
+        return self.model.state_dict()
+
+    def load_state_dict(self, sd):
+        self.model.load_state_dict(sd)
+
+    def load_optimizer_state_dict(self, osd):
+        pass    # a checkpoint's Adam state has no use in evaluation
+
+    def evaluate(self, data, target, rows=False):
+        """One batch -> (sum of the rows' NLL, correct count, predictions (n,) int32 cuda, probabilities (n,) fp32 cuda);
+        the last two are None unless `rows`.  The host reads the two sums (and nothing else)."""
+        from .classifier import check_targets, logits_eval
+        t = check_targets(target, self.num_classes)
+        x = data.to(self.device)
+        if x.shape[0] != t.numel():
+            raise ValueError("%d targets for a batch of %d" % (t.numel(), x.shape[0]))
+        if x.shape[0] == 0:
+            e = torch.zeros((0,), device=self.device)
+            return 0.0, 0, (e.to(torch.int32) if rows else None), (e if rows else None)
+        logp = self.model(x)
+        want = ("nll", "hit", "sums") + (("amax", "prob") if rows else ())
+        r = logits_eval(logp, t, want=want)
+        sums = r["sums"].cpu()
+        return float(sums[0]), int(sums[1]), r.get("amax"), r.get("prob")
+
+
+def write_result_csv(rows, path):
+    """result.csv of BaseTrainer.eval(save_result=True) (base_trainer.py:182-192): rows of (path, target, prediction,
+    probability) under the header Path,Target,Prediction,Probability, no index column, as DataFrame.to_csv writes them
+    (minimal quoting, "\n" line ends, floats by their shortest round-trip repr)."""
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["Path", "Target", "Prediction", "Probability"])
+        for pth, tgt, pred, prob in rows:
+            w.writerow([str(pth), int(tgt), int(pred), repr(float(prob))])
+
+
 class ReduceLROnPlateau:
     """torch.optim.lr_scheduler.ReduceLROnPlateau (cooldown 0, eps 1e-8) acting on TrainableMLP.lr."""
 
@@ -301,7 +373,22 @@ class ClassificationTrainer:
         self.train_loader, self.val_loader = train_loader, val_loader
 
     def _batch_input(self, data, train):
-        """What the loader yields -> what the MLP step takes: here the embeddings themselves."""
+        """What the loader yields -> what the model takes: the embeddings themselves; for a VNCelebDataset under
+        evaluation (rows of the resident image set) the images through the default transform (eval.py:24-40)."""
+        ds = (self.train_loader if train else self.val_loader).dataset
+        if isinstance(ds, VNCelebDataset) and not train:
+            from . import augment
+            index = torch.as_tensor(data, dtype=torch.int64)
+            if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
+                raise IndexError("sample index outside the data set")
+            t = getattr(self.model, "input_size", None)
+            if t is None:
+                raise NotImplementedError("VNCelebDataset under ClassificationTrainer needs a model that takes images")
+            if ds.size != t:
+                raise ValueError("the images are %dx%d but the model takes %dx%d: transforms.resize is not built (DESIGN.md 8)"
+                                 % (ds.size, ds.size, t, t))
+            params = augment.get_transform("default").params(int(index.numel()), ds.size, t)
+            return augment.augment_faces_device(ds.faces_device(self.model.device), index, params, t, dtype=self.model.x_dtype)
         return data
 
     def resume_checkpoint(self, checkpoint_path):
@@ -344,19 +431,65 @@ class ClassificationTrainer:
             self.lr_scheduler.step(self.val_loss.avg(self.loss_name))
         return log
 
-    def _validate_epoch(self, epoch):
+    def _evaluator(self, save_result):
+        """Who scores a validation batch: the model itself when it is an EvalModel; None for the training model inside
+        the training loop (its own forward + loss, TrainableMLP.step); and, when the rows are wanted from a training
+        model, an inference MLPModel of its current weights."""
+        if hasattr(self.model, "evaluate"):
+            return self.model
+        if not save_result:
+            return None
+        from .classifier import MLPModel
+        mlp = MLPModel(self.model.input_dim, self.model.num_classes, max_batch=self.model.max_batch)
+        mlp.load_state_dict(self.model.state_dict())
+        return EvalModel(mlp, self.model.num_classes, device=self.model.device)
+
+    def _validate_epoch(self, epoch, save_result=False):
+        """classification_trainer.py:42-80: the loss is the mean of the batch means, the accuracy is weighted by batch
+        size; with save_result also [paths, targets, predictions, probabilities] per batch."""
         self.model.eval()
         self.val_loss.reset()
         self.val_metrics.reset()
         self.logger.info("Validation: ")
-        for batch_idx, (data, target, _id) in enumerate(self.val_loader):
+        evaluator = self._evaluator(save_result)
+        result = []
+        for batch_idx, (data, target, id_img) in enumerate(self.val_loader):
             data = self._batch_input(data, train=False)
-            loss, hits = self.model.step(data, target, train=False)
+            n = data.size(0)
+            if evaluator is None:
+                loss, hits = self.model.step(data, target, train=False)
+            else:
+                sum_nll, hits, amax, prob = evaluator.evaluate(data, target, rows=save_result)
+                loss = float(np.float32(sum_nll) / np.float32(n))    # F.nll_loss's mean, in fp32
+                if save_result:
+                    result.append([id_img, torch.as_tensor(target), amax.cpu(), prob.cpu().tolist()])
             self.val_loss.update(self.loss_name, loss)
-            self.val_metrics.update("accuracy", hits / data.size(0), n=data.size(0))
+            self.val_metrics.update("accuracy", hits / n, n=n)
         log = self.val_loss.result()
         log.update(self.val_metrics.result())
-        return {"val_{}".format(k): v for k, v in log.items()}
+        val_log = {"val_{}".format(k): v for k, v in log.items()}
+        if save_result:
+            return val_log, result
+        return val_log
+
+    def eval(self, save_result=False):
+        """base_trainer.py:177-200: one pass over val_loader; with save_result also <save_dir>/models/<run_id>/result.csv."""
+        if save_result:
+            log, result = self._validate_epoch(1, save_result)
+            res_path = str(self.save_dir / "result.csv")
+            ids, targets, predictions, probs = [], [], [], []
+            for batch_pred in result:
+                ids += list(batch_pred[0])
+                targets += list(batch_pred[1].cpu().numpy())
+                predictions += list(batch_pred[2].cpu().numpy())
+                probs += list(batch_pred[3])
+            write_result_csv(zip(ids, targets, predictions, probs), res_path)
+            print("Saved prediction to {}.".format(res_path))
+        else:
+            log = self._validate_epoch(1)
+        for key, value in log.items():
+            self.logger.info("    {:15s}: {}".format(str(key), value))
+        return log
 
     def train(self, track4plot=False):
         not_improve_count = 0

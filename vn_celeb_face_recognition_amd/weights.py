@@ -54,8 +54,17 @@ def _bn(spec, prefix, c, res=False):
     spec.append((prefix + ".num_batches_tracked", (), "nbt"))
 
 
-def irv1_spec():
-    """Ordered (name, shape, kind) list == InceptionResnetV1(pretrained=None).state_dict()."""
+def _logits(spec, num_classes):
+    # nn.Linear(512, num_classes) behind the 512 features (inception_resnet_v1.py:260-265, iresnet_encoder.py:100-103).
+    # The features are BatchNorm outputs of a few units each, not unit vectors: the plain 1/fan_in draw already gives
+    # logits whose top probabilities are spread over (0,1) at 7 classes and at 8631
+    spec.append(("logits.weight", (int(num_classes), 512), "linear"))
+    spec.append(("logits.bias", (int(num_classes),), "bias"))
+
+
+def irv1_spec(num_classes=None):
+    """Ordered (name, shape, kind) list == InceptionResnetV1(pretrained=None).state_dict(); with num_classes, that of
+    InceptionResnetV1(classify=True, num_classes=...): the `logits` layer comes last."""
     s = []
     _basic_conv(s, "conv2d_1a", 3, 32, 3)
     _basic_conv(s, "conv2d_2a", 32, 32, 3)
@@ -101,6 +110,8 @@ def irv1_spec():
         s.append((p + ".conv2d.bias", (1792,), "bias"))
     s.append(("last_linear.weight", (512, 1792), "linear"))
     _bn(s, "last_bn", 512)
+    if num_classes is not None:
+        _logits(s, num_classes)
     return s
 
 
@@ -113,8 +124,8 @@ def mlp_spec(input_dim=512, num_classes=1001):
     ]
 
 
-def iresnet_spec(layers=(3, 13, 30, 3), num_features=512):
-    """IResNet (default layers == iresnet100) state_dict layout."""
+def iresnet_spec(layers=(3, 13, 30, 3), num_features=512, n_classes=None):
+    """IResNet (default layers == iresnet100) state_dict layout; with n_classes, `logits` comes last."""
     s = [("conv1.weight", (64, 3, 3, 3), "conv")]
     _bn(s, "bn1", 64)
     s.append(("prelu.weight", (64,), "prelu"))
@@ -137,6 +148,8 @@ def iresnet_spec(layers=(3, 13, 30, 3), num_features=512):
     s.append(("fc.weight", (num_features, 512 * 49), "linear"))
     s.append(("fc.bias", (num_features,), "bias"))
     _bn(s, "features", num_features)
+    if n_classes is not None:
+        _logits(s, n_classes)
     return s
 
 
