@@ -455,3 +455,35 @@ def test_conv2d_1a_on_the_f32_mfma_is_bitwise_the_valu_kernel(monkeypatch, dt):
     assert np.isfinite(ta).all() and np.abs(ta).max() > 0
     assert np.array_equal(ta, tb)
     assert torch.equal(ya, yb)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f16", "f16x2"])
+def test_floor_maxpool_is_exact_in_every_layout(monkeypatch, dt):
+    """nn.MaxPool2d(3, stride=2) (inception_resnet_v1.py:285, :137, :166) moves values and rounds nothing, in the planar
+    split-f16 layout too (the re-split of a recombined pair is that pair): every pooled tap must be, bit for bit, torch's
+    max_pool2d of the handle's own input tap -- 17 -> 8 and 8 -> 3 into a channel slice of the wider mixed_6a / mixed_7a
+    buffers, and 77 -> 38 (maxpool_3a, which only the per-convolution plan writes to memory)."""
+    import torch.nn.functional as F
+    from vn_celeb_face_recognition_amd.models import InceptionResnetV1
+    n = 2
+    x = seeded_normal((n, 3, 160, 160), 23).cuda()
+    monkeypatch.setenv("VNF_AUTOTUNE", "0")
+
+    def pool(t):
+        return F.max_pool2d(torch.from_numpy(t), 3, 2).numpy()
+
+    monkeypatch.delenv("VNF_FUSE", raising=False)
+    m = InceptionResnetV1(pretrained=None, device="cuda:0", compute_dtype=dt, max_batch=n).eval()
+    m(x)
+    got, want = m.tap("mixed_6a", n)[:, 640:896], pool(m.tap("repeat_1", n))
+    assert got.shape == want.shape == (n, 256, 8, 8) and np.abs(want).max() > 0
+    assert np.array_equal(got, want)
+    got, want = m.tap("mixed_7a", n)[:, 896:1792], pool(m.tap("repeat_2", n))
+    assert got.shape == want.shape == (n, 896, 3, 3) and np.abs(want).max() > 0
+    assert np.array_equal(got, want)
+    monkeypatch.setenv("VNF_FUSE", "0")
+    m = InceptionResnetV1(pretrained=None, device="cuda:0", compute_dtype=dt, max_batch=n).eval()
+    m(x)
+    got, want = m.tap("maxpool_3a", n), pool(m.tap("conv2d_2b", n))
+    assert got.shape == want.shape == (n, 64, 38, 38) and np.abs(want).max() > 0
+    assert np.array_equal(got, want)

@@ -38,7 +38,7 @@ def family(label):
     if label.startswith("repeat_2 (persistent"):
         return ("block17_trunk",)
     if label.startswith("maxpool"):
-        return ("maxpool3s2",)
+        return ("maxpool_kernel",)
     if label.startswith("avgpool"):
         return ("avgpool",)
     if label.startswith("l2norm"):

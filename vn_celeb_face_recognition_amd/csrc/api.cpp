@@ -342,8 +342,9 @@ int vnf_maxpool3s2p1(const void* x, int dtype, int planar, int n, int h, int w, 
   if (dtype != VNF_F32 && dtype != VNF_BF16 && dtype != VNF_F16 && dtype != VNF_F16X2) return fail(VNF_E_INVALID, "bad dtype");
   const int dt = dtype == VNF_F16X2 ? (planar ? F16P : F16X2) : dtype;
   if (c % dtype_chan_align(dt)) return fail(VNF_E_INVALID, "channel count is not a multiple of the layout's 16-byte unit");
-  if ((size_t)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * (size_t)c >= ((size_t)1 << 31)) return fail(VNF_E_CAPACITY, "tensor too large");
-  VNF_HIP(launch_maxpool3s2p1(x, c, y, c, dt, n, h, w, c, (hipStream_t)stream));
+  const PoolWindow win = {3, 1, false};
+  if ((size_t)n * pool_out_size(h, win) * pool_out_size(w, win) * (size_t)c >= ((size_t)1 << 31)) return fail(VNF_E_CAPACITY, "tensor too large");
+  VNF_HIP(launch_maxpool(x, c, y, c, dt, n, h, w, c, win, (hipStream_t)stream));
   return VNF_OK;
   API_GUARD_END
 }

@@ -3,7 +3,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include "kernels.h"
-#include "split_f16.h"
+#include "storage_unit.h"
 
 namespace vnf {
 
@@ -12,23 +12,6 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 template <typename T> __device__ __forceinline__ float to_f(T v) { return (float)v; }
-
-// planar split-f16 (split_f16.h pf16): 8 consecutive channels = [8 hi halves][8 lo halves], 32 bytes
-__device__ __forceinline__ void store_unit_pf16(void* dst, const float (&v)[8]) {
-  f16x8_t h, l;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const sf16 s(v[i]);
-    h[i] = s.hi; l[i] = s.lo;
-  }
-  reinterpret_cast<f16x8_t*>(dst)[0] = h;
-  reinterpret_cast<f16x8_t*>(dst)[1] = l;
-}
-__device__ __forceinline__ void load_unit_pf16(const void* src, float (&v)[8]) {
-  const f16x8_t h = reinterpret_cast<const f16x8_t*>(src)[0], l = reinterpret_cast<const f16x8_t*>(src)[1];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = (float)h[i] + (float)l[i];
-}
 
 // ---------------------------------------------------------------- NCHW (n,3,S,S) -> NHWC8
 template <typename TI, typename TO>
@@ -39,7 +22,7 @@ __global__ void pack_input_kernel(const TI* __restrict__ x, TO* __restrict__ y, 
     const TI* src = x + img * 3 * (size_t)hw + p;
     if constexpr (sizeof(TO) == sizeof(pf16) && __is_same(TO, pf16)) {
       const float v[8] = {to_f(src[0]), to_f(src[hw]), to_f(src[2 * (size_t)hw]), 0.f, 0.f, 0.f, 0.f, 0.f};
-      store_unit_pf16(y + i * 8, v);
+      Unit<pf16>::store(y + i * 8, v);
     } else {
       TO o[8];
       o[0] = (TO)to_f(src[0]);
@@ -121,7 +104,7 @@ __global__ void __launch_bounds__(256) stem_conv1a_kernel(const TI* __restrict__
       float v[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) { v[2 * j] = fmaxf(acc[4 * u + j][0], 0.f); v[2 * j + 1] = fmaxf(acc[4 * u + j][1], 0.f); }
-      store_unit_pf16(y + (size_t)i * ldy + u * 8, v);
+      Unit<pf16>::store(y + (size_t)i * ldy + u * 8, v);
     }
   } else {
     TO o[32];
@@ -252,191 +235,145 @@ hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int 
   return hipErrorInvalidValue;
 }
 
-// ---------------------------------------------------------------- max pool 3x3 stride 2
-template <typename T>
-__global__ void maxpool3s2_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int n, int H, int W,
-                                  int C) {
-  constexpr int CH = 16 / (int)sizeof(T);
-  const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1, cc = C / CH;
+// ---------------------------------------------------------------- max pool K x K stride 2
+// One thread per (output pixel, storage unit), NHWC slice -> NHWC slice; padding and the part of a ceil-mode window that
+// hangs over the border compare as -inf.  Every window the plans use has a tap inside the image, so -inf reaches the
+// output only where all of a window's inputs are -inf.  Split-f16: the max of the recombined values is re-split, which
+// reproduces the (hi, lo) pair of the largest value bit for bit.
+// INSIDE: every tap of every window lies in the image (floor mode, no padding): no bounds tests, and with 16-byte units
+// all K*K loads are in flight before the first fmaxf (kept as loaded: their fp32 values would double the registers).
+template <typename T, int K, int PAD, bool INSIDE>
+__global__ void maxpool_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int n, int H, int W, int C,
+                               int Ho, int Wo) {
+  typedef Unit<T> U;
+  constexpr int N = U::N;
+  // the instances that are neither INSIDE nor padded are the ceil-mode windows (a few thousand MTCNN crops): their tap
+  // loops stay rolled, one load at a time, as they always were (20 / 24 VGPRs; unrolled 24 / 27)
+  constexpr bool kCeil = !INSIDE && PAD == 0;
+  constexpr int TAPS = kCeil ? 1 : K;   // unroll factor of the tap loops
+  const int cc = C / N;
   const unsigned total = (unsigned)n * Ho * Wo * cc;  // < 2^31, checked by the launcher: 32-bit index math
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const unsigned p = i / cc;
-    const int c = (int)(i - p * cc) * CH;
+    const int c = (int)(i - p * cc) * N;
     const unsigned q = p / Wo;
     const int wo = (int)(p - q * Wo);
     const unsigned img = q / Ho;
     const int ho = (int)(q - img * Ho);
-    float m[CH];
+    float m[N];
 #pragma unroll
-    for (int e = 0; e < CH; ++e) m[e] = -3.4e38f;
-    const T* xi = x + ((size_t)img * H * W + (size_t)(2 * ho) * W + 2 * wo) * ldx + c;
-    T v[9][CH];
+    for (int e = 0; e < N; ++e) m[e] = -INFINITY;
+    if constexpr (INSIDE && sizeof(typename U::Raw) == 16) {
+      const T* xi = x + ((size_t)img * H * W + (size_t)(2 * ho) * W + 2 * wo) * ldx + c;
+      typename U::Raw r[K * K];
 #pragma unroll
-    for (int dh = 0; dh < 3; ++dh)
+      for (int dh = 0; dh < K; ++dh)
 #pragma unroll
-      for (int dw = 0; dw < 3; ++dw)   // nine independent 16-byte loads in flight
-        *reinterpret_cast<uint4*>(v[dh * 3 + dw]) = *reinterpret_cast<const uint4*>(xi + (size_t)(dh * W + dw) * ldx);
+        for (int dw = 0; dw < K; ++dw) r[dh * K + dw] = U::raw(xi + (size_t)(dh * W + dw) * ldx);
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+      for (int t = 0; t < K * K; ++t)
 #pragma unroll
-      for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], (float)v[t][e]);
-    T o[CH];
+        for (int e = 0; e < N; ++e) m[e] = fmaxf(m[e], U::at(r[t], e));
+    } else {
+      const T* xi = x + (size_t)img * H * W * ldx + c;
+#pragma unroll TAPS
+      for (int dh = 0; dh < K; ++dh)
+#pragma unroll TAPS
+        for (int dw = 0; dw < K; ++dw) {
+          const int yy = 2 * ho - PAD + dh, xx = 2 * wo - PAD + dw;
+          if (INSIDE || ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)) {
+            float v[N];
+            U::load(xi + (size_t)(yy * W + xx) * ldx, v);
 #pragma unroll
-    for (int e = 0; e < CH; ++e) o[e] = (T)m[e];
-    *reinterpret_cast<uint4*>(y + (size_t)p * ldy + c) = *reinterpret_cast<const uint4*>(o);
-  }
-}
-
-// planar split-f16: one thread per (pixel, 8-channel unit); max of the recombined values, re-split (exact: the pair
-// of the largest value is reproduced bit for bit)
-__global__ void maxpool3s2_pf16_kernel(const pf16* __restrict__ x, int ldx, pf16* __restrict__ y, int ldy, int n, int H, int W, int C) {
-  const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1, cc = C / 8;
-  const unsigned total = (unsigned)n * Ho * Wo * cc;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const unsigned p = i / cc;
-    const int c = (int)(i - p * cc) * 8;
-    const unsigned q = p / Wo;
-    const int wo = (int)(p - q * Wo);
-    const unsigned img = q / Ho;
-    const int ho = (int)(q - img * Ho);
-    float m[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) m[e] = -3.4e38f;
-    const pf16* xi = x + ((size_t)img * H * W + (size_t)(2 * ho) * W + 2 * wo) * ldx + c;
-#pragma unroll
-    for (int dh = 0; dh < 3; ++dh)
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        float v[8];
-        load_unit_pf16(xi + (size_t)(dh * W + dw) * ldx, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
-      }
-    store_unit_pf16(y + (size_t)p * ldy + c, m);
-  }
-}
-
-hipError_t launch_maxpool3s2(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C,
-                             hipStream_t s) {
-  const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-  const int ch = dtype_chan_align(dtype);
-  if (C % ch) return hipErrorInvalidValue;
-  const size_t total = (size_t)n * Ho * Wo * (C / ch);
-  if (total == 0) return hipSuccess;
-  if (total >= (1u << 31)) return hipErrorInvalidValue;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  switch (dtype) {
-    case BF16: hipLaunchKernelGGL(maxpool3s2_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, ldx, (__bf16*)y, ldy, n, H, W, C); break;
-    case F16: hipLaunchKernelGGL(maxpool3s2_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)x, ldx, (_Float16*)y, ldy, n, H, W, C); break;
-    case F32: hipLaunchKernelGGL(maxpool3s2_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, n, H, W, C); break;
-    case F16P: hipLaunchKernelGGL(maxpool3s2_pf16_kernel, dim3(blocks), dim3(256), 0, s, (const pf16*)x, ldx, (pf16*)y, ldy, n, H, W, C); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- max pool k x k stride 2, ceil_mode=True
-// (MTCNN R/O-Net pools, mtcnn.py:64,67,114,117,120): windows may hang over the border.
-template <typename T>
-__global__ void maxpool_ceil_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int n, int H, int W,
-                                    int C, int k) {
-  constexpr int CH = 16 / (int)sizeof(T);
-  const int Ho = (H - k + 1) / 2 + 1, Wo = (W - k + 1) / 2 + 1, cc = C / CH;
-  const unsigned total = (unsigned)n * Ho * Wo * cc;  // < 2^31, checked by the launcher: 32-bit index math
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const unsigned p = i / cc;
-    const int c = (int)(i - p * cc) * CH;
-    const unsigned q = p / Wo;
-    const int wo = (int)(p - q * Wo);
-    const unsigned img = q / Ho;
-    const int ho = (int)(q - img * Ho);
-    float m[CH];
-#pragma unroll
-    for (int e = 0; e < CH; ++e) m[e] = -INFINITY;
-    const T* xi = x + (size_t)img * H * W * ldx + c;
-    for (int dh = 0; dh < k; ++dh)
-      for (int dw = 0; dw < k; ++dw) {
-        const int yy = 2 * ho + dh, xx = 2 * wo + dw;
-        if (yy < H && xx < W) {
-          T v[CH];
-          *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xi + (unsigned)(yy * W + xx) * (size_t)ldx);
-#pragma unroll
-          for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], (float)v[e]);
+            for (int e = 0; e < N; ++e) m[e] = fmaxf(m[e], v[e]);
+          }
         }
-      }
-    T o[CH];
-#pragma unroll
-    for (int e = 0; e < CH; ++e) o[e] = (T)m[e];
-    *reinterpret_cast<uint4*>(y + (size_t)p * ldy + c) = *reinterpret_cast<const uint4*>(o);
+    }
+    U::store(y + (size_t)p * ldy + c, m);
   }
 }
 
-hipError_t launch_maxpool_ceil(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, int k,
-                               hipStream_t s) {
-  const int Ho = (H - k + 1) / 2 + 1, Wo = (W - k + 1) / 2 + 1;
-  const int ch = 16 / dtype_size(dtype);
-  if (C % ch) return hipErrorInvalidValue;
+struct PoolArgs { const void* x; int ldx; void* y; int ldy, n, H, W, C, Ho, Wo, blocks; hipStream_t s; };
+
+template <typename T, int K, int PAD, bool INSIDE>
+static void maxpool_go(const PoolArgs& a) {
+  hipLaunchKernelGGL((maxpool_kernel<T, K, PAD, INSIDE>), dim3(a.blocks), dim3(256), 0, a.s, (const T*)a.x, a.ldx, (T*)a.y, a.ldy,
+                     a.n, a.H, a.W, a.C, a.Ho, a.Wo);
+}
+
+// the windows the plans use, each in the layouts that reach it
+static const struct { PoolWindow w; int dtype; void (*go)(const PoolArgs&); } kPools[] = {
+    // 3x3 floor: IRv1 (maxpool_3a, mixed_6a, mixed_7a)
+    {{3, 0, false}, F32, maxpool_go<float, 3, 0, true>},     {{3, 0, false}, BF16, maxpool_go<__bf16, 3, 0, true>},
+    {{3, 0, false}, F16, maxpool_go<_Float16, 3, 0, true>},  {{3, 0, false}, F16P, maxpool_go<pf16, 3, 0, true>},
+    // 3x3 ceil: R-Net, O-Net pool2;  2x2 ceil: O-Net pool3
+    {{3, 0, true}, F32, maxpool_go<float, 3, 0, false>},     {{3, 0, true}, F16X2, maxpool_go<sf16, 3, 0, false>},
+    {{2, 0, true}, F32, maxpool_go<float, 2, 0, false>},     {{2, 0, true}, F16X2, maxpool_go<sf16, 2, 0, false>},
+    // 3x3 pad 1: ResNet-50 stem, vnf_maxpool3s2p1
+    {{3, 1, false}, F32, maxpool_go<float, 3, 1, false>},    {{3, 1, false}, BF16, maxpool_go<__bf16, 3, 1, false>},
+    {{3, 1, false}, F16, maxpool_go<_Float16, 3, 1, false>}, {{3, 1, false}, F16X2, maxpool_go<sf16, 3, 1, false>},
+    {{3, 1, false}, F16P, maxpool_go<pf16, 3, 1, false>},
+};
+
+hipError_t launch_maxpool(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, PoolWindow w,
+                          hipStream_t s) {
+  const int Ho = pool_out_size(H, w), Wo = pool_out_size(W, w);
+  const int ch = dtype_chan_align(dtype);
+  if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || C % ch || ldx % ch || ldy % ch) return hipErrorInvalidValue;
   const size_t total = (size_t)n * Ho * Wo * (C / ch);
   if (total == 0) return hipSuccess;
   if (total >= (1u << 31)) return hipErrorInvalidValue;
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  switch (dtype) {
-    case BF16: hipLaunchKernelGGL(maxpool_ceil_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, ldx, (__bf16*)y, ldy, n, H, W, C, k); break;
-    case F16: hipLaunchKernelGGL(maxpool_ceil_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)x, ldx, (_Float16*)y, ldy, n, H, W, C, k); break;
-    case F32: hipLaunchKernelGGL(maxpool_ceil_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, n, H, W, C, k); break;
-    case F16X2: hipLaunchKernelGGL(maxpool_ceil_kernel<sf16>, dim3(blocks), dim3(256), 0, s, (const sf16*)x, ldx, (sf16*)y, ldy, n, H, W, C, k); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  for (const auto& p : kPools)
+    if (p.w.k == w.k && p.w.pad == w.pad && p.w.ceil == w.ceil && p.dtype == dtype) {
+      p.go(PoolArgs{x, ldx, y, ldy, n, H, W, C, Ho, Wo, blocks, s});
+      return hipGetLastError();
+    }
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- global average pool
+// one thread per (image, storage unit): every channel is summed over p = 0 .. HW-1 in that order and divided once
 template <typename T>
 __global__ void avgpool_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int n, int HW, int C) {
-  const size_t total = (size_t)n * C;
+  constexpr int N = Unit<T>::N;
+  const int cc = C / N;
+  const size_t total = (size_t)n * cc;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t img = i / C;
-    const int c = (int)(i - img * C);
-    float s = 0.f;
-    for (int p = 0; p < HW; ++p) s += (float)x[(img * HW + p) * (size_t)ldx + c];
-    y[i] = (T)(s / (float)HW);
+    const size_t img = i / cc;
+    const int c = (int)(i - img * cc) * N;
+    float s[N], v[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) s[e] = 0.f;
+    for (int p = 0; p < HW; ++p) {
+      Unit<T>::load(x + (img * HW + p) * (size_t)ldx + c, v);
+#pragma unroll
+      for (int e = 0; e < N; ++e) s[e] += v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) s[e] = s[e] / (float)HW;
+    Unit<T>::store(y + img * C + c, s);
   }
 }
 
-__global__ void avgpool_pf16_kernel(const pf16* __restrict__ x, int ldx, pf16* __restrict__ y, int n, int HW, int C) {
-  const size_t total = (size_t)n * (C / 8);
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t img = i / (C / 8);
-    const int c = (int)(i - img * (C / 8)) * 8;
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < HW; ++p) {
-      float v[8];
-      load_unit_pf16(x + (img * HW + p) * (size_t)ldx + c, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s[e] += v[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = s[e] / (float)HW;
-    store_unit_pf16(y + img * C + c, s);
-  }
+template <typename T>
+static hipError_t avgpool_go(const void* x, int ldx, void* y, int n, int HW, int C, hipStream_t s) {
+  const size_t total = (size_t)n * (C / Unit<T>::N);
+  hipLaunchKernelGGL(avgpool_kernel<T>, dim3((int)((total + 255) / 256)), dim3(256), 0, s, (const T*)x, ldx, (T*)y, n, HW, C);
+  return hipGetLastError();
 }
 
 hipError_t launch_avgpool(const void* x, int ldx, void* y, int dtype, int n, int HW, int C, hipStream_t s) {
-  const size_t total = (size_t)n * C;
-  if (total == 0) return hipSuccess;
-  const int blocks = (int)((total + 255) / 256);
-  if (dtype == F16P) {
-    if (C % 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(avgpool_pf16_kernel, dim3((int)((total / 8 + 255) / 256)), dim3(256), 0, s, (const pf16*)x, ldx, (pf16*)y, n, HW, C);
-    return hipGetLastError();
-  }
+  const int ch = dtype_chan_align(dtype);
+  if (C % ch || ldx % ch) return hipErrorInvalidValue;
+  if ((size_t)n * C == 0) return hipSuccess;
   switch (dtype) {
-    case BF16: hipLaunchKernelGGL(avgpool_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, ldx, (__bf16*)y, n, HW, C); break;
-    case F16: hipLaunchKernelGGL(avgpool_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)x, ldx, (_Float16*)y, n, HW, C); break;
-    case F32: hipLaunchKernelGGL(avgpool_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, ldx, (float*)y, n, HW, C); break;
-    default: return hipErrorInvalidValue;
+    case BF16: return avgpool_go<__bf16>(x, ldx, y, n, HW, C, s);
+    case F16: return avgpool_go<_Float16>(x, ldx, y, n, HW, C, s);
+    case F32: return avgpool_go<float>(x, ldx, y, n, HW, C, s);
+    case F16P: return avgpool_go<pf16>(x, ldx, y, n, HW, C, s);
   }
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------- row-wise L2 normalisation
@@ -456,46 +393,6 @@ __global__ void l2norm_kernel(const float* __restrict__ x, float* __restrict__ y
 hipError_t launch_l2norm(const float* x, float* y, int n, int C, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(l2norm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, x, y, n, C);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- log_softmax + argmax + prob
-// one wave per row of logits (mlp_model.py:14 log_softmax; demo_image.py:125-129 argmax, exp)
-__global__ void logsoftmax_argmax_kernel(const float* __restrict__ logits, int ld, int C, int n,
-                                         float* __restrict__ logp, int32_t* __restrict__ amax,
-                                         float* __restrict__ prob) {
-  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float* x = logits + (size_t)row * ld;
-  float m = -INFINITY;
-  int mi = 0x7fffffff;
-  for (int c = lane; c < C; c += 64) {
-    const float v = x[c];
-    if (v > m) { m = v; mi = c; }   // first occurrence within the lane's stride
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o);
-    const int oi = __shfl_xor(mi, o);
-    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-  }
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += expf(x[c] - m);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float ls = logf(s);
-  if (logp)
-    for (int c = lane; c < C; c += 64) logp[(size_t)row * C + c] = (x[c] - m) - ls;
-  if (lane == 0) {
-    if (amax) amax[row] = mi;
-    if (prob) prob[row] = expf(-ls);  // exp(logp[argmax]) with logp[argmax] = 0 - log(sum)
-  }
-}
-
-hipError_t launch_logsoftmax_argmax(const float* logits, int ld, int C, int n, float* logp, int32_t* amax, float* prob,
-                                    hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(logsoftmax_argmax_kernel, dim3((n + 3) / 4), dim3(256), 0, s, logits, ld, C, n, logp, amax, prob);
   return hipGetLastError();
 }
 
@@ -770,47 +667,43 @@ hipError_t launch_upsample_add(const float* x, int Hs, int Ws, float* y, int H, 
 }
 
 // ---------------------------------------------------------------- NHWC slice -> NCHW fp32 (taps)
+// one thread per (image, storage unit, pixel), pixels fastest: N coalesced fp32 rows out
 template <typename T>
 __global__ void nhwc_to_nchw_kernel(const T* __restrict__ x, int ldx, float* __restrict__ y, int n, int HW, int C) {
-  const size_t total = (size_t)n * HW * C;
+  constexpr int N = Unit<T>::N;
+  const int cc = C / N;
+  const size_t total = (size_t)n * cc * HW;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int p = (int)(i % HW);
     const size_t q = i / HW;
-    const int c = (int)(q % C);
-    const size_t img = q / C;
-    y[i] = (float)x[(img * HW + p) * (size_t)ldx + c];
+    const int c = (int)(q % cc) * N;
+    const size_t img = q / cc;
+    float v[N];
+    Unit<T>::load(x + (img * HW + p) * (size_t)ldx + c, v);
+#pragma unroll
+    for (int e = 0; e < N; ++e) y[(img * C + c + e) * HW + p] = v[e];
   }
 }
 
-__global__ void nhwc_to_nchw_pf16_kernel(const pf16* __restrict__ x, int ldx, float* __restrict__ y, int n, int HW, int C) {
-  const size_t total = (size_t)n * HW * C;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int p = (int)(i % HW);
-    const size_t q = i / HW;
-    const int c = (int)(q % C);
-    const size_t img = q / C;
-    // element c of the slice: unit c / 8 (32 bytes), hi half at 2 * (c % 8), lo half 16 bytes further (the slice starts
-    // on a unit boundary)
-    const _Float16* u = reinterpret_cast<const _Float16*>(x + (img * HW + p) * (size_t)ldx + (c & ~7));
-    y[i] = (float)u[c & 7] + (float)u[8 + (c & 7)];
-  }
+template <typename T>
+static hipError_t nhwc_to_nchw_go(const void* x, int ldx, float* y, int n, int HW, int C, hipStream_t s) {
+  const size_t total = (size_t)n * (C / Unit<T>::N) * HW;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)x, ldx, y, n, HW, C);
+  return hipGetLastError();
 }
 
 hipError_t launch_nhwc_to_nchw_f32(const void* x, int ldx, int dtype, float* y, int n, int HW, int C, hipStream_t s) {
-  const size_t total = (size_t)n * HW * C;
-  if (total == 0) return hipSuccess;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  if (dtype == F16P) {
-    hipLaunchKernelGGL(nhwc_to_nchw_pf16_kernel, dim3(blocks), dim3(256), 0, s, (const pf16*)x, ldx, y, n, HW, C);
-    return hipGetLastError();
-  }
+  const int ch = dtype_chan_align(dtype);
+  if (C % ch || ldx % ch) return hipErrorInvalidValue;   // slices start and end on a unit boundary
+  if ((size_t)n * HW * C == 0) return hipSuccess;
   switch (dtype) {
-    case BF16: hipLaunchKernelGGL(nhwc_to_nchw_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, ldx, y, n, HW, C); break;
-    case F16: hipLaunchKernelGGL(nhwc_to_nchw_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)x, ldx, y, n, HW, C); break;
-    case F32: hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, ldx, y, n, HW, C); break;
-    default: return hipErrorInvalidValue;
+    case BF16: return nhwc_to_nchw_go<__bf16>(x, ldx, y, n, HW, C, s);
+    case F16: return nhwc_to_nchw_go<_Float16>(x, ldx, y, n, HW, C, s);
+    case F32: return nhwc_to_nchw_go<float>(x, ldx, y, n, HW, C, s);
+    case F16P: return nhwc_to_nchw_go<pf16>(x, ldx, y, n, HW, C, s);
   }
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf

@@ -30,6 +30,7 @@
 // (exact f32 FMA chain; the <=1e-4 parity path).
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "block35.h"
 #include "conv_device.h"
@@ -310,7 +311,7 @@ static hipError_t launch_dma(const KArgs& k, hipStream_t s) {
 
 // Tile configurations of the LDS-DMA kernel: {BM, BN, waves along M, waves along N, ring stages}.
 struct TileCfg { int bm, bn, wm, wn, s; };
-static const TileCfg kCfgs[] = {
+static constexpr TileCfg kCfgs[] = {
     {128, 128, 2, 2, 3}, {128, 64, 2, 2, 3}, {128, 32, 4, 1, 3}, {64, 64, 2, 2, 4}, {64, 32, 2, 2, 4},
     {256, 32, 4, 1, 3},  {256, 64, 4, 1, 3}, {64, 128, 1, 4, 3}, {32, 64, 2, 2, 4}, {32, 128, 1, 4, 4},
     {128, 64, 2, 2, 4},  {64, 64, 2, 2, 3},  {128, 32, 4, 1, 4},
@@ -346,46 +347,16 @@ bool conv_cfg_ok(const ConvArgs& a, int cfg) {
   return lds <= 160 * 1024;
 }
 
+// cfg -> launch_dma<T, kCfgs[cfg]...>: entry I of the table is the template argument list of launcher I
+template <typename T, size_t... I>
+static hipError_t launch_cfg(int cfg, const KArgs& k, hipStream_t s, std::index_sequence<I...>) {
+  static constexpr hipError_t (*kLaunch[])(const KArgs&, hipStream_t) = {
+      launch_dma<T, kCfgs[I].bm, kCfgs[I].bn, kCfgs[I].wm, kCfgs[I].wn, kCfgs[I].s>...};
+  return (unsigned)cfg < sizeof...(I) ? kLaunch[cfg](k, s) : hipErrorInvalidValue;
+}
 template <typename T>
 static hipError_t launch_cfg(int cfg, const KArgs& k, hipStream_t s) {
-  switch (cfg) {
-    case 0: return launch_dma<T, 128, 128, 2, 2, 3>(k, s);
-    case 1: return launch_dma<T, 128, 64, 2, 2, 3>(k, s);
-    case 2: return launch_dma<T, 128, 32, 4, 1, 3>(k, s);
-    case 3: return launch_dma<T, 64, 64, 2, 2, 4>(k, s);
-    case 4: return launch_dma<T, 64, 32, 2, 2, 4>(k, s);
-    case 5: return launch_dma<T, 256, 32, 4, 1, 3>(k, s);
-    case 6: return launch_dma<T, 256, 64, 4, 1, 3>(k, s);
-    case 7: return launch_dma<T, 64, 128, 1, 4, 3>(k, s);
-    case 8: return launch_dma<T, 32, 64, 2, 2, 4>(k, s);
-    case 9: return launch_dma<T, 32, 128, 1, 4, 4>(k, s);
-    case 10: return launch_dma<T, 128, 64, 2, 2, 4>(k, s);
-    case 11: return launch_dma<T, 64, 64, 2, 2, 3>(k, s);
-    case 12: return launch_dma<T, 128, 32, 4, 1, 4>(k, s);
-    case 13: return launch_dma<T, 128, 128, 2, 4, 3>(k, s);
-    case 14: return launch_dma<T, 256, 128, 4, 2, 3>(k, s);
-    case 15: return launch_dma<T, 256, 64, 4, 2, 3>(k, s);
-    case 16: return launch_dma<T, 128, 64, 4, 2, 3>(k, s);
-    case 17: return launch_dma<T, 128, 256, 2, 4, 3>(k, s);
-    case 18: return launch_dma<T, 128, 128, 2, 4, 4>(k, s);
-    case 19: return launch_dma<T, 128, 64, 4, 2, 6>(k, s);
-    case 20: return launch_dma<T, 64, 64, 2, 2, 8>(k, s);
-    case 21: return launch_dma<T, 64, 32, 2, 2, 8>(k, s);
-    case 22: return launch_dma<T, 32, 64, 2, 2, 8>(k, s);
-    case 23: return launch_dma<T, 128, 32, 4, 1, 6>(k, s);
-    case 24: return launch_dma<T, 64, 128, 2, 4, 5>(k, s);
-    case 25: return launch_dma<T, 128, 64, 2, 2, 6>(k, s);
-    case 26: return launch_dma<T, 64, 256, 1, 8, 3>(k, s);
-    case 27: return launch_dma<T, 64, 256, 1, 8, 4>(k, s);
-    case 28: return launch_dma<T, 128, 256, 2, 4, 3>(k, s);
-    case 29: return launch_dma<T, 128, 96, 4, 1, 3>(k, s);
-    case 30: return launch_dma<T, 64, 96, 2, 2, 4>(k, s);
-    case 31: return launch_dma<T, 128, 192, 2, 4, 3>(k, s);
-    case 32: return launch_dma<T, 64, 192, 2, 4, 3>(k, s);
-    case 33: return launch_dma<T, 256, 96, 4, 1, 3>(k, s);
-    case 34: return launch_dma<T, 64, 192, 2, 4, 4>(k, s);
-  }
-  return hipErrorInvalidValue;
+  return launch_cfg<T>(cfg, k, s, std::make_index_sequence<kNumCfgs>{});
 }
 
 template <typename T>

@@ -22,6 +22,7 @@
 #include <mutex>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 
 #include "conv_device.h"
 #include "stamp.h"
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_patch_kernel(const KArgs a) 
 
 // ===================================================================== host side
 struct PatchCfg { int bm, bn, wm, wn, s; };
-static const PatchCfg kPatch[] = {
+static constexpr PatchCfg kPatch[] = {
     {256, 32, 8, 1, 3},  {256, 32, 4, 1, 3},  {128, 32, 4, 1, 3},  {256, 64, 4, 2, 3},  {128, 64, 4, 2, 3},
     {128, 64, 2, 2, 3},  {64, 64, 2, 2, 4},   {256, 192, 4, 2, 3}, {128, 192, 2, 4, 3}, {64, 192, 2, 4, 3},
     {128, 256, 2, 4, 3}, {256, 256, 4, 2, 3}, {128, 128, 2, 4, 3}, {256, 128, 4, 2, 3}, {64, 128, 2, 4, 3},
@@ -341,51 +342,42 @@ static hipError_t launch_one(const KArgs& k, int lds, hipStream_t s) {
   return hipGetLastError();
 }
 
+// pcfg -> launch_one<T, kPatch[pcfg]...>: entry I of the table is the template argument list of launcher I
+template <typename T, size_t... I>
+static hipError_t launch_patch_typed(int pcfg, const KArgs& k, int lds, hipStream_t s, std::index_sequence<I...>) {
+  static constexpr hipError_t (*kLaunch[])(const KArgs&, int, hipStream_t) = {
+      launch_one<T, kPatch[I].bm, kPatch[I].bn, kPatch[I].wm, kPatch[I].wn, kPatch[I].s>...};
+  return (unsigned)pcfg < sizeof...(I) ? kLaunch[pcfg](k, lds, s) : hipErrorInvalidValue;
+}
 template <typename T>
 static hipError_t launch_patch_typed(int pcfg, const KArgs& k, int lds, hipStream_t s) {
-  switch (pcfg) {
-    case 0: return launch_one<T, 256, 32, 8, 1, 3>(k, lds, s);
-    case 1: return launch_one<T, 256, 32, 4, 1, 3>(k, lds, s);
-    case 2: return launch_one<T, 128, 32, 4, 1, 3>(k, lds, s);
-    case 3: return launch_one<T, 256, 64, 4, 2, 3>(k, lds, s);
-    case 4: return launch_one<T, 128, 64, 4, 2, 3>(k, lds, s);
-    case 5: return launch_one<T, 128, 64, 2, 2, 3>(k, lds, s);
-    case 6: return launch_one<T, 64, 64, 2, 2, 4>(k, lds, s);
-    case 7: return launch_one<T, 256, 192, 4, 2, 3>(k, lds, s);
-    case 8: return launch_one<T, 128, 192, 2, 4, 3>(k, lds, s);
-    case 9: return launch_one<T, 64, 192, 2, 4, 3>(k, lds, s);
-    case 10: return launch_one<T, 128, 256, 2, 4, 3>(k, lds, s);
-    case 11: return launch_one<T, 256, 256, 4, 2, 3>(k, lds, s);
-    case 12: return launch_one<T, 128, 128, 2, 4, 3>(k, lds, s);
-    case 13: return launch_one<T, 256, 128, 4, 2, 3>(k, lds, s);
-    case 14: return launch_one<T, 64, 128, 2, 4, 3>(k, lds, s);
-    case 15: return launch_one<T, 64, 128, 2, 2, 4>(k, lds, s);
-    case 16: return launch_one<T, 256, 64, 4, 2, 6>(k, lds, s);
-    case 17: return launch_one<T, 128, 64, 4, 2, 6>(k, lds, s);
-    case 18: return launch_one<T, 256, 128, 4, 2, 4>(k, lds, s);
-    case 19: return launch_one<T, 256, 32, 8, 1, 6>(k, lds, s);
-    case 20: return launch_one<T, 128, 96, 4, 1, 3>(k, lds, s);
-    case 21: return launch_one<T, 128, 96, 2, 2, 3>(k, lds, s);
-    case 22: return launch_one<T, 64, 192, 1, 4, 3>(k, lds, s);
-    case 23: return launch_one<T, 192, 192, 4, 2, 3>(k, lds, s);
-  }
-  return hipErrorInvalidValue;
+  return launch_patch_typed<T>(pcfg, k, lds, s, std::make_index_sequence<kNumPatch>{});
 }
 
 // Instrumented launch (tools/stamp_patch.py): VNF_PATCH_STAMP=<file> dumps cycle stamps of workgroup 700 of every bf16
-// {256,192,4,2,3} launch with more than 700 workgroups: start, prologue issued, before / after the barrier of every K
+// launch of the tile kStamp with more than 700 workgroups: start, prologue issued, before / after the barrier of every K
 // tile, K loop done, epilogue barrier, end.
 #ifdef VNF_STAMPS
+constexpr PatchCfg kStamp = {256, 192, 4, 2, 3};
+constexpr int patch_cfg_id(const PatchCfg& q) {
+  for (int i = 0; i < kNumPatch; ++i)
+    if (kPatch[i].bm == q.bm && kPatch[i].bn == q.bn && kPatch[i].wm == q.wm && kPatch[i].wn == q.wn && kPatch[i].s == q.s) return i;
+  return -1;
+}
+constexpr int kStampId = patch_cfg_id(kStamp);
+static_assert(kStampId >= 0, "the instrumented tile is one of kPatch");
+
 static hipError_t launch_patch_stamped(const KArgs& k, int lds, hipStream_t s) {
+  constexpr auto kernel = conv_patch_kernel<__bf16, kStamp.bm, kStamp.bn, kStamp.wm, kStamp.wn, kStamp.s, true>;
   KArgs kk = k;
-  kk.tiles_n = (k.Cout + 191) / 192;
-  kk.nblk = ((k.M + 255) / 256) * kk.tiles_n;
+  kk.tiles_n = (k.Cout + kStamp.bn - 1) / kStamp.bn;
+  kk.nblk = ((k.M + kStamp.bm - 1) / kStamp.bm) * kk.tiles_n;
   return stamped_launch(
       "VNF_PATCH_STAMP", 8 * 40, s,
       [&](long long* dbuf) {
         kk.dbg = dbuf;
-        allow_dynamic_lds<conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>>(160 * 1024);
-        hipLaunchKernelGGL((conv_patch_kernel<__bf16, 256, 192, 4, 2, 3, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
+        allow_dynamic_lds<kernel>(160 * 1024);
+        hipLaunchKernelGGL(kernel, dim3(kk.nblk), dim3(kStamp.wm * kStamp.wn * 64), lds, s, kk);
       },
       [&](FILE* f, const long long* host) {
         fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
@@ -406,7 +398,8 @@ hipError_t launch_patch(const ConvArgs& a, const KArgs& k, int pcfg, hipStream_t
   kk.KH = a.KH; kk.KW = a.KW; kk.Cin = a.Cin;
   kk.pp = g.pp; kk.Wp = g.Wp; kk.Hv = g.Hv; kk.patch_bytes = g.patch_bytes; kk.lds_bytes = g.lds;
 #ifdef VNF_STAMPS
-  if (getenv("VNF_PATCH_STAMP") && pcfg == 7 && a.dtype == BF16 && ((k.M + 255) / 256) * ((k.Cout + 191) / 192) > 700)
+  if (getenv("VNF_PATCH_STAMP") && pcfg == kStampId && a.dtype == BF16 &&
+      ((k.M + kStamp.bm - 1) / kStamp.bm) * ((k.Cout + kStamp.bn - 1) / kStamp.bn) > 700)
     return launch_patch_stamped(kk, g.lds, s);
 #endif
   switch (a.dtype) {

@@ -14,6 +14,7 @@
 // refill it while the consumers multiply tile kt.  Same K order, operand roles and epilogue as the
 // ring kernel, so results are bit-identical to it.
 #include <type_traits>
+#include <utility>
 
 #include "conv_device.h"
 #include "stamp.h"
@@ -587,7 +588,7 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
 
 // ===================================================================== host side
 struct WsCfg { int bm, bn, wm, wn, s, lw; };
-static const WsCfg kWs[] = {
+static constexpr WsCfg kWs[] = {
     {256, 128, 2, 2, 3, 4}, {256, 128, 4, 1, 3, 4}, {128, 128, 2, 2, 3, 4}, {128, 128, 2, 2, 4, 4},
     {256, 64, 4, 1, 3, 4},  {128, 192, 2, 2, 3, 4}, {128, 256, 2, 2, 3, 4}, {128, 64, 2, 2, 4, 4},
     {256, 128, 2, 2, 3, 2}, {128, 128, 2, 2, 4, 2}, {128, 192, 2, 2, 3, 2}, {192, 128, 2, 2, 3, 4},
@@ -672,47 +673,43 @@ static hipError_t launch_one(const ConvArgs& a, const KArgs& k, hipStream_t s) {
   return launch_one_tile<T, BM, BN, WM, WN, S, LW>(k, s);
 }
 
+// wcfg -> launch_one<T, kWs[wcfg]...>: entry I of the table is the template argument list of launcher I
+template <typename T, size_t... I>
+static hipError_t launch_ws_typed(int wcfg, const ConvArgs& a, const KArgs& k, hipStream_t s, std::index_sequence<I...>) {
+  static constexpr hipError_t (*kLaunch[])(const ConvArgs&, const KArgs&, hipStream_t) = {
+      launch_one<T, kWs[I].bm, kWs[I].bn, kWs[I].wm, kWs[I].wn, kWs[I].s, kWs[I].lw>...};
+  return (unsigned)wcfg < sizeof...(I) ? kLaunch[wcfg](a, k, s) : hipErrorInvalidValue;
+}
 template <typename T>
 static hipError_t launch_ws_typed(int wcfg, const ConvArgs& a, const KArgs& k, hipStream_t s) {
-  switch (wcfg) {
-    case 0: return launch_one<T, 256, 128, 2, 2, 3, 4>(a, k, s);
-    case 1: return launch_one<T, 256, 128, 4, 1, 3, 4>(a, k, s);
-    case 2: return launch_one<T, 128, 128, 2, 2, 3, 4>(a, k, s);
-    case 3: return launch_one<T, 128, 128, 2, 2, 4, 4>(a, k, s);
-    case 4: return launch_one<T, 256, 64, 4, 1, 3, 4>(a, k, s);
-    case 5: return launch_one<T, 128, 192, 2, 2, 3, 4>(a, k, s);
-    case 6: return launch_one<T, 128, 256, 2, 2, 3, 4>(a, k, s);
-    case 7: return launch_one<T, 128, 64, 2, 2, 4, 4>(a, k, s);
-    case 8: return launch_one<T, 256, 128, 2, 2, 3, 2>(a, k, s);
-    case 9: return launch_one<T, 128, 128, 2, 2, 4, 2>(a, k, s);
-    case 10: return launch_one<T, 128, 192, 2, 2, 3, 2>(a, k, s);
-    case 11: return launch_one<T, 192, 128, 2, 2, 3, 4>(a, k, s);
-    case 12: return launch_one<T, 160, 256, 2, 2, 3, 4>(a, k, s);
-    case 13: return launch_one<T, 160, 192, 2, 2, 3, 4>(a, k, s);
-    case 14: return launch_one<T, 64, 64, 2, 2, 4, 4>(a, k, s);
-    case 15: return launch_one<T, 64, 128, 2, 2, 4, 4>(a, k, s);
-    case 16: return launch_one<T, 32, 64, 2, 2, 6, 4>(a, k, s);
-    case 17: return launch_one<T, 32, 128, 2, 2, 4, 4>(a, k, s);
-    case 18: return launch_one<T, 64, 64, 2, 2, 8, 4>(a, k, s);
-  }
-  return hipErrorInvalidValue;
+  return launch_ws_typed<T>(wcfg, a, k, s, std::make_index_sequence<kNumWs>{});
 }
 
 // Instrumented launch (tools/stamp_ws.py): VNF_WS_STAMP=<file> dumps per-K-tile s_memtime stamps of workgroup 600
-// of every bf16 {128,192,2,2,3,4} launch with more than 600 workgroups.
+// of every bf16 launch of the tile kStamp with more than 600 workgroups.
 #ifdef VNF_STAMPS
+constexpr WsCfg kStamp = {128, 192, 2, 2, 3, 4};
+constexpr int ws_cfg_id(const WsCfg& q) {
+  for (int i = 0; i < kNumWs; ++i)
+    if (kWs[i].bm == q.bm && kWs[i].bn == q.bn && kWs[i].wm == q.wm && kWs[i].wn == q.wn && kWs[i].s == q.s && kWs[i].lw == q.lw) return i;
+  return -1;
+}
+constexpr int kStampId = ws_cfg_id(kStamp);
+static_assert(kStampId >= 0, "the instrumented tile is one of kWs");
+
 static hipError_t launch_stamped(const KArgs& k, hipStream_t s) {
+  constexpr auto kernel = conv_igemm_ws_kernel<__bf16, kStamp.bm, kStamp.bn, kStamp.wm, kStamp.wn, kStamp.s, kStamp.lw, true>;
   KArgs kk = k;
-  const int lds = 3 * (128 + 192) * 128 + k.nkt * 8 * 16;
-  const int tiles_m = (k.M + 127) / 128;
-  kk.tiles_n = (k.Cout + 191) / 192;
+  const int lds = kStamp.s * (kStamp.bm + kStamp.bn) * 128 + k.nkt * 8 * 16;
+  const int tiles_m = (k.M + kStamp.bm - 1) / kStamp.bm;
+  kk.tiles_n = (k.Cout + kStamp.bn - 1) / kStamp.bn;
   kk.nblk = tiles_m * kk.tiles_n;
   return stamped_launch(
       "VNF_WS_STAMP", 8 * 64 * 4, s,
       [&](long long* dbuf) {
         kk.dbg = dbuf;
-        allow_dynamic_lds<conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>>(160 * 1024);
-        hipLaunchKernelGGL((conv_igemm_ws_kernel<__bf16, 128, 192, 2, 2, 3, 4, true>), dim3(kk.nblk), dim3(512), lds, s, kk);
+        allow_dynamic_lds<kernel>(160 * 1024);
+        hipLaunchKernelGGL(kernel, dim3(kk.nblk), dim3((kStamp.wm * kStamp.wn + kStamp.lw) * 64), lds, s, kk);
       },
       [&](FILE* f, const long long* host) {
         fprintf(f, "launch M=%d N=%d nkt=%d nblk=%d\n", k.M, k.Cout, k.nkt, kk.nblk);
@@ -727,7 +724,8 @@ static hipError_t launch_stamped(const KArgs& k, hipStream_t s) {
 hipError_t launch_ws(const ConvArgs& a, const KArgs& k, int wcfg, hipStream_t s) {
   if (!ws_cfg_ok(a, wcfg) || !k.zero) return hipErrorInvalidValue;
 #ifdef VNF_STAMPS
-  if (getenv("VNF_WS_STAMP") && wcfg == 5 && a.dtype == BF16 && (k.M + 127) / 128 * ((k.Cout + 191) / 192) > 600)
+  if (getenv("VNF_WS_STAMP") && wcfg == kStampId && a.dtype == BF16 &&
+      (k.M + kStamp.bm - 1) / kStamp.bm * ((k.Cout + kStamp.bn - 1) / kStamp.bn) > 600)
     return launch_stamped(k, s);
 #endif
   switch (a.dtype) {

@@ -1,6 +1,6 @@
-// Kernels around the ResNet-50 two-head emotion plan (engine.cpp build_rn50_2b): the padded 3x3 stride-2 max pool,
-// the Pillow-exact face transform (u8 faces -> bilinear 224x224 -> ToTensor -> Normalize) and the softmax top-k of the
-// class head.  All three are streaming kernels: vector loads and stores along the contiguous axis, plain C++ stores.
+// Kernels around the ResNet-50 two-head emotion plan (plan_rn50.cpp build_rn50_2b): the Pillow-exact face transform
+// (u8 faces -> bilinear 224x224 -> ToTensor -> Normalize) and the softmax top-k of the class head.  Both are streaming
+// kernels: vector loads and stores along the contiguous axis, plain C++ stores.
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -11,105 +11,6 @@
 namespace vnf {
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-// ---------------------------------------------------------------- max pool 3x3 stride 2 pad 1
-// nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet_2_branch.py:21): Ho = (H - 1) / 2 + 1, padding compares as
-// -inf.  The centre tap of every window lies inside the image, so -inf never reaches the output.
-// One thread per (output pixel, 16-byte channel chunk), NHWC slice -> NHWC slice.
-template <typename T>
-__global__ void maxpool3s2p1_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int n, int H, int W, int C) {
-  constexpr int CH = 16 / (int)sizeof(T);
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, cc = C / CH;
-  const unsigned total = (unsigned)n * Ho * Wo * cc;  // < 2^31, checked by the launcher: 32-bit index math
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const unsigned p = i / cc;
-    const int c = (int)(i - p * cc) * CH;
-    const unsigned q = p / Wo;
-    const int wo = (int)(p - q * Wo);
-    const unsigned img = q / Ho;
-    const int ho = (int)(q - img * Ho);
-    float m[CH];
-#pragma unroll
-    for (int e = 0; e < CH; ++e) m[e] = -INFINITY;
-    const T* xi = x + (size_t)img * H * W * ldx + c;
-#pragma unroll
-    for (int dh = 0; dh < 3; ++dh)
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        const int yy = 2 * ho - 1 + dh, xx = 2 * wo - 1 + dw;
-        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-          T v[CH];
-          *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xi + (size_t)(yy * W + xx) * ldx);
-#pragma unroll
-          for (int e = 0; e < CH; ++e) m[e] = fmaxf(m[e], (float)v[e]);
-        }
-      }
-    T o[CH];
-#pragma unroll
-    for (int e = 0; e < CH; ++e) o[e] = (T)m[e];
-    *reinterpret_cast<uint4*>(y + (size_t)p * ldy + c) = *reinterpret_cast<const uint4*>(o);
-  }
-}
-
-// planar split-f16: one thread per (pixel, 8-channel unit); the max of the recombined values is re-split, which
-// reproduces the (hi, lo) pair of the largest value bit for bit
-__global__ void maxpool3s2p1_pf16_kernel(const pf16* __restrict__ x, int ldx, pf16* __restrict__ y, int ldy, int n, int H, int W,
-                                         int C) {
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, cc = C / 8;
-  const unsigned total = (unsigned)n * Ho * Wo * cc;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const unsigned p = i / cc;
-    const int c = (int)(i - p * cc) * 8;
-    const unsigned q = p / Wo;
-    const int wo = (int)(p - q * Wo);
-    const unsigned img = q / Ho;
-    const int ho = (int)(q - img * Ho);
-    float m[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
-    const pf16* xi = x + (size_t)img * H * W * ldx + c;
-#pragma unroll
-    for (int dh = 0; dh < 3; ++dh)
-#pragma unroll
-      for (int dw = 0; dw < 3; ++dw) {
-        const int yy = 2 * ho - 1 + dh, xx = 2 * wo - 1 + dw;
-        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-          const f16x8_t* src = reinterpret_cast<const f16x8_t*>(xi + (size_t)(yy * W + xx) * ldx);
-          const f16x8_t h = src[0], l = src[1];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], (float)h[e] + (float)l[e]);
-        }
-      }
-    f16x8_t h, l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const sf16 s(m[e]);
-      h[e] = s.hi; l[e] = s.lo;
-    }
-    f16x8_t* dst = reinterpret_cast<f16x8_t*>(y + (size_t)p * ldy + c);
-    dst[0] = h;
-    dst[1] = l;
-  }
-}
-
-hipError_t launch_maxpool3s2p1(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, hipStream_t s) {
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const int ch = dtype_chan_align(dtype);
-  if (H < 1 || W < 1 || C % ch || ldx % ch || ldy % ch) return hipErrorInvalidValue;
-  const size_t total = (size_t)n * Ho * Wo * (C / ch);
-  if (total == 0) return hipSuccess;
-  if (total >= (1u << 31)) return hipErrorInvalidValue;
-  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  switch (dtype) {
-    case BF16: hipLaunchKernelGGL(maxpool3s2p1_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)x, ldx, (__bf16*)y, ldy, n, H, W, C); break;
-    case F16: hipLaunchKernelGGL(maxpool3s2p1_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)x, ldx, (_Float16*)y, ldy, n, H, W, C); break;
-    case F32: hipLaunchKernelGGL(maxpool3s2p1_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)x, ldx, (float*)y, ldy, n, H, W, C); break;
-    case F16X2: hipLaunchKernelGGL(maxpool3s2p1_kernel<sf16>, dim3(blocks), dim3(256), 0, s, (const sf16*)x, ldx, (sf16*)y, ldy, n, H, W, C); break;
-    case F16P: hipLaunchKernelGGL(maxpool3s2p1_pf16_kernel, dim3(blocks), dim3(256), 0, s, (const pf16*)x, ldx, (pf16*)y, ldy, n, H, W, C); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
 
 // ---------------------------------------------------------------- emotion_prep
 // trans_emotion_inf (data_loader/__init__.py:74-81) on aligned (n,S,S,3) u8 faces: Resize(224) on a square PIL image is

@@ -291,16 +291,14 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
                                        env.stem1a_mfma != 0, s));
             break;
           case Op::MAXPOOL:
-            VNF_HIP(launch_maxpool3s2(at(op.src, n0), ib->C, at(op.dst, n0, op.dst_coff), bufs[op.dst].C, dtype, nn, ib->H, ib->W, ib->C, s));
+            VNF_HIP(launch_maxpool(at(op.src, n0), ib->C, at(op.dst, n0, op.dst_coff), bufs[op.dst].C, dtype, nn, ib->H, ib->W, ib->C,
+                                   op.window, s));
             break;
           case Op::AVGPOOL:
             VNF_HIP(launch_avgpool(at(op.src, n0), ib->C, at(op.dst, n0), dtype, nn, ib->H * ib->W, ib->C, s));
             break;
           case Op::L2NORM:
             VNF_HIP(launch_l2norm(emb_raw + (size_t)n0 * 512, out + (size_t)n0 * 512, nn, 512, s));
-            break;
-          case Op::MAXPOOLC:
-            VNF_HIP(launch_maxpool_ceil(at(op.src, n0), ib->C, at(op.dst, n0), bufs[op.dst].C, dtype, nn, ib->H, ib->W, ib->C, op.window, s));
             break;
           case Op::DWCONV: {
             if (!f32_plan) return fail(VNF_E_INVALID, "depthwise conv: fp32 / split-f16 plans only");
@@ -329,9 +327,6 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
             VNF_HIP(launch_upsample_add(at_f32(op.src, n0), ib->H, ib->W, at_f32(op.dst, n0), ob.H, ob.W, ob.C, nn, dtype == F16X2, s));
             break;
           }
-          case Op::MAXPOOLP:
-            VNF_HIP(launch_maxpool3s2p1(at(op.src, n0), ib->C, at(op.dst, n0), bufs[op.dst].C, dtype, nn, ib->H, ib->W, ib->C, s));
-            break;
           case Op::HEADS: {
             const float* raw = emb_raw + (size_t)n0 * emb_ld;
             if (out) VNF_HIP(launch_copy_rows_f32(raw, emb_ld, out + (size_t)n0 * op.n_cls, op.n_cls, nn, op.n_cls, s));
@@ -347,6 +342,25 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
     }
   }
   return report ? write_report(prof_ev, prof_op, n, s, report) : VNF_OK;
+}
+
+// report label of the ops that have no line format of their own
+static const char* op_label(const Op& op) {
+  switch (op.kind) {
+    case Op::PACK: return "pack";
+    case Op::CONV: return "conv";
+    case Op::MAXPOOL: return op.window.ceil ? "maxpool_ceil" : op.window.pad ? "maxpool_pad1" : "maxpool";
+    case Op::AVGPOOL: return "avgpool";
+    case Op::L2NORM: return "l2norm";
+    case Op::COPYOUT: return "copyout";
+    case Op::STEM1: return "stem1";
+    case Op::DWCONV: return "dwconv3x3";
+    case Op::UPADD: return "upsample_add";
+    case Op::RSTEM: return "retina_stem (u8 frames -> conv0)";
+    case Op::DWPW: return "dw3x3+pw1x1 fused";
+    case Op::HEADS: return "heads";
+  }
+  return "?";
 }
 
 // Per-op device time of one run_range (events between consecutive launches on the stream), summed over chunks: one line
@@ -387,9 +401,7 @@ int Encoder::write_report(std::vector<hipEvent_t>& prof_ev, const std::vector<in
       snprintf(line, sizeof line, "%-28s %-60s %8.4f ms  %8.1f GFLOP %8.1f TFLOP/s\n", "conv2d_1a (direct, NCHW in)",
                "3x3 s2 3->32 on the caller's tensor, exact f32 (MFMA / VALU)", t, gf, tflops(gf));
     } else {
-      static const char* kn[] = {"pack", "conv", "maxpool", "avgpool", "l2norm", "copyout", "maxpool_ceil", "stem1", "dwconv3x3",
-                                 "upsample_add", "retina_stem (u8 frames -> conv0)", "dw3x3+pw1x1 fused", "maxpool_pad1", "heads"};
-      snprintf(line, sizeof line, "%-28s %-8s %60s %8.4f ms\n", "", kn[op.kind], "", t);
+      snprintf(line, sizeof line, "%-28s %-8s %60s %8.4f ms\n", "", op_label(op), "", t);
     }
     *report += line;
   }

@@ -80,20 +80,22 @@ struct ConvLayer {
 };
 
 struct Op {
-  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, MAXPOOLC, STEM1, DWCONV, UPADD, RSTEM, DWPW, MAXPOOLP, HEADS } kind;
+  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, STEM1, DWCONV, UPADD, RSTEM, DWPW, HEADS } kind;
   int src = -1;                   // source buffer
   int dst = -1, dst_coff = 0;     // destination buffer and the channel offset of the slice written in it
   int layer = -1;                 // index into Encoder::convs (CONV, STEM1), dws (DWCONV) or dwpws (DWPW)
-  int window = 0;                 // MAXPOOLC: pool window
+  PoolWindow window = {0, 0, false};   // MAXPOOL: stride-2 window (launch_maxpool)
   int frame_h = 0, frame_w = 0;   // RSTEM: size of the u8 frames the caller passes as x
   int n_cls = 0, n_proj = 0, proj_col = 0;   // HEADS: widths of the two heads, first projection column of emb_raw
 
   static Op pack(int dst) { Op o{PACK}; o.dst = dst; return o; }   // the caller's NCHW tensor (or u8 faces) -> NHWC8 plan input
   static Op conv(int layer) { Op o{CONV}; o.layer = layer; return o; }
   static Op stem1(int layer, int dst) { Op o{STEM1}; o.layer = layer; o.dst = dst; return o; }   // PACK + CONV of conv2d_1a, direct
-  static Op maxpool(int src, int dst, int dst_coff) { Op o{MAXPOOL}; o.src = src; o.dst = dst; o.dst_coff = dst_coff; return o; }   // 3x3 s2
-  static Op maxpool_ceil(int src, int dst, int window) { Op o{MAXPOOLC}; o.src = src; o.dst = dst; o.window = window; return o; }
-  static Op maxpool_pad1(int src, int dst) { Op o{MAXPOOLP}; o.src = src; o.dst = dst; return o; }   // 3x3 s2 p1
+  static Op maxpool(int src, int dst, int dst_coff, PoolWindow w = {3, 0, false}) {   // 3x3 s2 into a channel slice of dst
+    Op o{MAXPOOL}; o.src = src; o.dst = dst; o.dst_coff = dst_coff; o.window = w; return o;
+  }
+  static Op maxpool_ceil(int src, int dst, int k) { return maxpool(src, dst, 0, {k, 0, true}); }
+  static Op maxpool_pad1(int src, int dst) { return maxpool(src, dst, 0, {3, 1, false}); }   // 3x3 s2 p1
   static Op avgpool(int src, int dst) { Op o{AVGPOOL}; o.src = src; o.dst = dst; return o; }
   static Op l2norm() { return Op{L2NORM}; }     // emb_raw -> out, rows normalised
   static Op copyout() { return Op{COPYOUT}; }   // emb_raw -> out

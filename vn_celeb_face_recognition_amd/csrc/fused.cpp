@@ -131,7 +131,7 @@ bool Encoder::buf_materialised(int buf) const {
       if (op.kind == Op::CONV) {
         const ConvLayer& L = convs[op.layer];
         for (int i = 0; i < L.nseg; ++i) written |= L.seg[i].buf == buf;
-      } else if (op.kind == Op::MAXPOOL || op.kind == Op::MAXPOOLC) {
+      } else if (op.kind == Op::MAXPOOL) {
         written |= op.dst == buf;
       }
     }

@@ -1,7 +1,8 @@
-// Evaluation of a classification head: logits + targets -> per-row log-probabilities, prediction, probability, loss and
-// hit, and the two batch sums a validation loop reads (trainer/classification_trainer.py:42-80: F.nll_loss on the
-// log_softmax output, losses/metrics.py:3-7 accuracy; trainer/base_trainer.py:177-200 result.csv columns).
-//   head_eval_rows_kernel   one wave per row, as logsoftmax_argmax_kernel (aux_kernels.hip)
+// Evaluation of a classification head: logits (+ targets) -> per-row log-probabilities, prediction, probability, loss and
+// hit, and the two batch sums a validation loop reads (mlp_model.py:14 log_softmax; demo_image.py:125-129 argmax, exp;
+// trainer/classification_trainer.py:42-80: F.nll_loss on the log_softmax output, losses/metrics.py:3-7 accuracy;
+// trainer/base_trainer.py:177-200 result.csv columns).
+//   head_eval_rows_kernel   one wave per row; without targets it is vnf_classify's log_softmax + argmax + prob
 //   head_eval_sums_kernel   one wave adds the rows' nll / hit in index order: no float atomics, the same bits every run
 //   head_eval_sums_rows_kernel   the sums when the caller keeps no per-row nll / hit: one workgroup recomputes the rows
 #include <hip/hip_runtime.h>

@@ -63,17 +63,20 @@ hipError_t launch_pack_input(const void* x, int x_dtype, void* out, int dtype, i
 hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, bool mfma,
                               hipStream_t s);
 
-// 3x3 stride-2 max pool, floor mode, NHWC slice -> NHWC slice
-hipError_t launch_maxpool3s2(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C,
-                             hipStream_t s);
-
-// k x k stride-2 max pool with ceil_mode=True (MTCNN R/O-Net), NHWC slice -> NHWC slice
-hipError_t launch_maxpool_ceil(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, int k,
-                               hipStream_t s);
-
-// 3x3 stride-2 max pool with padding 1 (padding compares as -inf; nn.MaxPool2d(3, 2, 1)), NHWC slice -> NHWC slice;
-// every storage layout the plans use (F32, BF16, F16, F16X2 pairs, F16P planar)
-hipError_t launch_maxpool3s2p1(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, hipStream_t s);
+// K x K stride-2 max pool, NHWC slice -> NHWC slice; padding and the overhang of a ceil-mode window compare as -inf.
+// The windows and storage layouts the plans use (any other combination: hipErrorInvalidValue):
+//   3x3 floor  F32 BF16 F16 F16P         nn.MaxPool2d(3, 2)                  IRv1
+//   3x3 ceil   F32 F16X2                 nn.MaxPool2d(3, 2, ceil_mode=True)  R-Net, O-Net
+//   2x2 ceil   F32 F16X2                 nn.MaxPool2d(2, 2, ceil_mode=True)  O-Net
+//   3x3 pad 1  F32 BF16 F16 F16X2 F16P   nn.MaxPool2d(3, 2, 1)               ResNet-50, vnf_maxpool3s2p1
+// ldx, ldy and C are multiples of the layout's storage unit (dtype_chan_align); a floor-mode window fits the image
+struct PoolWindow { int k, pad; bool ceil; };
+inline int pool_out_size(int in, PoolWindow w) {   // < 1: the image is smaller than a floor-mode window
+  const int span = in + 2 * w.pad - w.k;
+  return span < 0 && !w.ceil ? 0 : (span + (w.ceil ? 1 : 0)) / 2 + 1;
+}
+hipError_t launch_maxpool(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, PoolWindow w,
+                          hipStream_t s);
 
 // trans_emotion_inf on the device: u8 faces (n,S,S,3), S <= 224 -> Pillow-exact bilinear 224x224 -> x/255 -> (x-mean)/std,
 // written as NCHW (n,3,224,224) of F32/BF16/F16, or (packed) as the NHWC8 plan input of F32/BF16/F16/F16P
@@ -92,19 +95,15 @@ hipError_t launch_softmax_topk(const float* logits, int n, int C, int k, int32_t
 // fp32 rows (n,C): pitched copy src (row stride lds) -> dst (row stride ldd)
 hipError_t launch_copy_rows_f32(const float* src, int lds, float* dst, int ldd, int n, int C, hipStream_t s);
 
-// global average pool NHWC (n,HW,C) -> (n,C)
+// global average pool NHWC (n,HW,C) -> (n,C); C and ldx are multiples of the layout's storage unit (dtype_chan_align)
 hipError_t launch_avgpool(const void* x, int ldx, void* y, int dtype, int n, int HW, int C, hipStream_t s);
 
 // rows of fp32 (n,C): y = x / max(||x||_2, 1e-12)
 hipError_t launch_l2norm(const float* x, float* y, int n, int C, hipStream_t s);
 
-// rows of fp32 logits (n, ld >= C): log_softmax over the first C columns, argmax (first
-// occurrence) and exp(logp[argmax])
-hipError_t launch_logsoftmax_argmax(const float* logits, int ld, int C, int n, float* logp, int32_t* amax, float* prob,
-                                    hipStream_t s);
-
-// launch_logsoftmax_argmax plus the targets' side (head_eval.hip): nll[r] = -logp[r][target[r]], hit[r] = argmax == target,
-// sums = {sum nll, sum hit} added in index order.  Every output may be NULL; target may be NULL when nll, hit and sums are.
+// rows of fp32 logits (n, ld >= C) (head_eval.hip): log_softmax over the first C columns, argmax (first occurrence) and
+// exp(logp[argmax]); with targets, nll[r] = -logp[r][target[r]], hit[r] = argmax == target, sums = {sum nll, sum hit}
+// added in index order.  Every output may be NULL; target may be NULL when nll, hit and sums are.
 // A target outside [0, C) is never an index: nll = +inf, hit = 0.
 hipError_t launch_head_eval(const float* logits, int ld, int C, int n, const int64_t* target, float* logp, int32_t* amax,
                             float* prob, float* nll, int32_t* hit, float* sums, hipStream_t s);
@@ -130,7 +129,8 @@ hipError_t launch_dwpw(const float* x, float* y, int n, int H, int W, int cin, i
 // (retina_face_utils/components.py:88-94), fp32 NHWC
 hipError_t launch_upsample_add(const float* x, int Hs, int Ws, float* y, int H, int W, int C, int n, bool split, hipStream_t s);
 
-// NHWC slice (dtype) -> NCHW fp32 (for taps / debugging)
+// NHWC slice (dtype) -> NCHW fp32 (for taps / debugging); the slice starts and ends on a storage-unit boundary: C and ldx
+// are multiples of dtype_chan_align(dtype)
 hipError_t launch_nhwc_to_nchw_f32(const void* x, int ldx, int dtype, float* y, int n, int HW, int C, hipStream_t s);
 
 }  // namespace vnf

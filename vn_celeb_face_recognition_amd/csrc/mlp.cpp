@@ -70,8 +70,8 @@ extern "C" int vnf_classify(vnf_handle h, const float* emb, int f, float* logp_o
     VNF_HIP(hipMemcpyAsync(e.bufs[m->b_in].ptr, emb, (size_t)f * m->input_dim * 4, hipMemcpyDeviceToDevice, s));
     int r = e.run(nullptr, f, VNF_F32, nullptr, s);
     if (r != VNF_OK) return r;
-    VNF_HIP(launch_logsoftmax_argmax((const float*)e.bufs[m->b_logit].ptr, m->cpad, m->num_classes, f, logp_out,
-                                     argmax_out, prob_out, s));
+    VNF_HIP(launch_head_eval((const float*)e.bufs[m->b_logit].ptr, m->cpad, m->num_classes, f, nullptr, logp_out, argmax_out,
+                             prob_out, nullptr, nullptr, nullptr, s));
     VNF_HIP(hipEventRecord(m->done, s));
     return VNF_OK;
   } catch (const std::exception& ex) {
