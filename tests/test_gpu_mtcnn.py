@@ -256,14 +256,9 @@ def test_result_readback_paths_agree(monkeypatch):
         assert np.abs(np.asarray(l1[i]).reshape(-1, 10) - np.asarray(ol[i]).reshape(-1, 10)).max() <= 1e-3
 
 
-@pytest.mark.parametrize("hw,mfs,thr1", [((233, 317), 20, 0.6), ((301, 403), 30, 0.6), ((360, 641), 40, 0.5), ((487, 353), 24, 0.6)])
-def test_random_frame_sizes_match_the_oracle(hw, mfs, thr1):
-    """Odd frame sizes (rows that are not a whole number of 16-byte chunks take the per-pixel pyramid / crop paths; odd
-    level sizes exercise the ceil-mode pooling edges of the MFMA P-Net front and the R/O-Net front bands), a lowered
-    stage-1 threshold (more candidates through the sort / NMS paths), two frames per batch."""
+def _pasted_face_frames(hw):
+    """Two frames of a smooth noisy background with three resized golden faces pasted into each."""
     from PIL import Image
-    from vn_celeb_face_recognition_amd.models import MTCNN
-    from oracle import mtcnn as om
     h, w = hw
     rng = np.random.default_rng(h * 1000 + w)
     faces = [Image.fromarray(load_image(f)) for f in ("041bc30432964f95871d4c223eba8f7c.png", "318c7ec3b94b451c813a5665cfcfbda3.png",
@@ -278,6 +273,18 @@ def test_random_frame_sizes_match_the_oracle(hw, mfs, thr1):
             x0, y0 = int(rng.integers(0, w - s)), int(rng.integers(0, h - s))
             img[y0:y0 + s, x0:x0 + s] = np.asarray(faces[(k + j) % 3].resize((s, s), Image.BICUBIC))
         frames.append(img)
+    return frames
+
+
+@pytest.mark.parametrize("hw,mfs,thr1", [((233, 317), 20, 0.6), ((301, 403), 30, 0.6), ((360, 641), 40, 0.5), ((487, 353), 24, 0.6)])
+def test_random_frame_sizes_match_the_oracle(hw, mfs, thr1):
+    """Odd frame sizes (rows that are not a whole number of 16-byte chunks take the per-pixel pyramid / crop paths; odd
+    level sizes exercise the ceil-mode pooling edges of the MFMA P-Net front and the R/O-Net front bands), a lowered
+    stage-1 threshold (more candidates through the sort / NMS paths), two frames per batch."""
+    from vn_celeb_face_recognition_amd.models import MTCNN
+    from oracle import mtcnn as om
+    h, w = hw
+    frames = _pasted_face_frames(hw)
     thr = [thr1, 0.7, 0.7]
     det = MTCNN(keep_all=True, min_face_size=mfs, thresholds=thr, device="cuda:0", max_batch=2, max_height=h, max_width=w)
     bb, pp, ll = det.inference(frames, landmark=True)
@@ -290,6 +297,63 @@ def test_random_frame_sizes_match_the_oracle(hw, mfs, thr1):
             assert np.abs(np.asarray(bb[i]) - ob[i]).max() <= 1e-3
             assert np.abs(np.asarray(pp[i]) - op_[i]).max() <= 1e-5
             assert np.abs(np.asarray(ll[i]) - ol[i]).max() <= 1e-3
+
+
+def test_aligned_and_unaligned_frames_give_the_same_detections():
+    """The same 240x320 batch (rows of 960 B) at a 16-byte aligned address and one byte into a larger buffer: the first
+    takes the row form of the pyramid and the strips of the crop kernel, the second the per-pixel forms.  Both add the
+    same integers (area_sum.h), so levels and detections are equal to the bit."""
+    from vn_celeb_face_recognition_amd.models import MTCNN
+    h, w = 240, 320
+    host = np.stack(_pasted_face_frames((h, w)))
+    aligned = torch.from_numpy(host).to("cuda:0")
+    buf = torch.zeros(host.size + 1, dtype=torch.uint8, device="cuda:0")
+    buf[1:] = aligned.reshape(-1)
+    shifted = buf[1:].view(host.shape)
+    assert aligned.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 != 0
+    det = MTCNN(keep_all=True, min_face_size=24, thresholds=[0.6, 0.7, 0.7], device="cuda:0", max_batch=2, max_height=h, max_width=w)
+    ba, pa, la = det.inference(aligned, landmark=True)
+    bs, ps, ls = det.inference(shifted, landmark=True)
+    assert sum(len(b) for b in ba) >= 4
+    for i in range(2):
+        assert np.array_equal(np.asarray(ba[i]), np.asarray(bs[i]))
+        assert np.array_equal(np.asarray(pa[i]), np.asarray(ps[i]))
+        assert np.array_equal(np.asarray(la[i]), np.asarray(ls[i]))
+    last = len(om.scale_pyramid(h, w, 24, 0.709)) - 1
+    assert last > 0
+    for li in (0, last):
+        for ma, ms in zip(det.debug_pnet_level(aligned[0], li), det.debug_pnet_level(shifted[0], li)):  # level, prob, reg
+            assert np.array_equal(ma, ms), li
+
+
+def test_crops_wider_than_a_strip_match_the_oracle():
+    """One face filling a 1600x1600 frame (rows of 4800 B, aligned): the oracle's own tables show stage-1 rectangles on
+    both sides of the 1376 px (4128 B) that a strip of column sums holds, so one crop launch mixes strip and per-pixel
+    candidates, and stage-2 rectangles that are all wider, so the O-Net crops are all gathered per pixel.  (Bins deeper
+    than 257 rows take the same branch; that needs crops taller than ~6000 px at S = 24 and is not run here.)"""
+    from PIL import Image
+    from vn_celeb_face_recognition_amd.models import MTCNN
+    n = 1600
+    img = np.full((n, n, 3), 120, np.uint8)
+    face = Image.fromarray(load_image("041bc30432964f95871d4c223eba8f7c.png")).resize((1560, 1560), Image.BICUBIC)
+    img[20:1580, 20:1580] = np.asarray(face)
+    p, r, o = mtcnn_state_dicts()
+    st = {}
+    ob, op_, ol = om.mtcnn_detect(img, p, r, o, min_face_size=600, ties="table", stages=st)
+
+    def widths(boxes):
+        _, _, x, ex = om.pad(boxes, n, n)
+        return ex - x + 1
+
+    w1, w2 = widths(st["stage1"][0]), widths(st["stage2"][0])
+    assert (w1 > 1376).any() and (w1 < 1376).any(), w1
+    assert len(w2) and (w2 > 1376).all(), w2
+    det = MTCNN(keep_all=True, min_face_size=600, device="cuda:0", max_batch=1, max_height=n, max_width=n)
+    bb, pp, ll = det.inference(img, landmark=True)
+    assert len(bb) == len(ob) and len(ob) >= 1
+    assert np.abs(np.asarray(bb) - np.asarray(ob)).max() <= 1e-3
+    assert np.abs(np.asarray(pp) - np.asarray(op_)).max() <= 1e-5
+    assert np.abs(np.asarray(ll) - np.asarray(ol)).max() <= 1e-3
 
 
 def test_candidate_tables_have_no_fixed_cap():

@@ -9,17 +9,18 @@
 //   models/mtcnn.py:516-518                    fixed_image_standardization: (x - 127.5) / 128
 // The rectangle itself (detect_face.py:358-368, float32 margin arithmetic) is host work: detector.crop_rects.
 //
-// Memory-bound byte work, built like the cascade's crop_resize_rows_kernel: a wave owns an output row; its lanes stream
-// 16-byte pieces of the crop's byte span of every input row of the bin row, keep per-byte column sums in registers,
-// park them in a wave-private LDS strip and then add the horizontal bin spans.  Sums are integers; the one division is
-// IEEE fp32 (no reciprocal: s * (1 / (kh kw)) truncates constant bins to v - 1), so for bins under 2^15 pixels the
-// byte is the reference's whatever order it adds in.  Unlike the cascade's kernel the pieces start at the crop's first
-// byte, not at a 16-byte boundary of the frame, so one code path serves every x1 and every row pitch (W*3 % 16 != 0
-// moves the alignment from row to row, which chunk-aligned register sums cannot follow).
+// Memory-bound byte work over the bins and sums of area_sum.h, like the cascade's crop_resize_rows_kernel: a wave owns an
+// output row; its lanes stream 16-byte pieces of the crop's byte span of every input row of the bin row, keep per-byte
+// column sums in registers, park them in a wave-private LDS strip and then add the horizontal bin spans.  The finish is
+// this file's own: one IEEE fp32 division of the exact sum (no reciprocal: s * (1 / (kh kw)) truncates constant bins to
+// v - 1), so for bins under 2^15 pixels the byte is the reference's whatever order it adds in.  Unlike the cascade's
+// kernel the pieces start at the crop's first byte, not at a 16-byte boundary of the frame, so one code path serves every
+// x1 and every row pitch (W*3 % 16 != 0 moves the alignment from row to row, which chunk-aligned register sums cannot
+// follow).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 
+#include "area_sum.h"
 #include "engine.h"
 
 namespace vnf {
@@ -70,19 +71,18 @@ __global__ void __launch_bounds__(256) extract_faces_kernel(const uint8_t* __res
   // a single bin wider than a strip (S tiny against the crop): per-pixel sums for this face
   const bool wide = t.ok && (t.cw + S - 1) / S + 1 > lim_px;
   const bool u8_vec = (S & 3) == 0 && ((uintptr_t)u8_out & 3) == 0;
-  // floor(o * c / S) = o * (c / S) + o * (c % S) / S, and the ceiling alike: 32-bit arithmetic for any crop (o, S <= 1024)
-  const int qw = t.cw / S, rw = t.cw - qw * S, qh = t.ch / S, rh = t.ch - qh * S;
   // the column bins are the same for every row: worked out once per workgroup, not per output value
   if (t.ok)
     for (int ox = threadIdx.x; ox < S; ox += blockDim.x) {
-      wtab0[ox] = ox * qw + (ox * rw) / S;
-      wtab1[ox] = (ox + 1) * qw + ((ox + 1) * rw + S - 1) / S;
+      const AreaBin bw = area_bin(ox, t.cw, S);
+      wtab0[ox] = bw.lo;
+      wtab1[ox] = bw.hi;
     }
   __syncthreads();
 
   for (int oy = oy_lo + wave; oy < oy_hi; oy += 4) {
-    const int h0 = oy * qh + (oy * rh) / S;
-    const int h1 = (oy + 1) * qh + ((oy + 1) * rh + S - 1) / S;
+    const AreaBin bh = area_bin(oy, t.ch, S);
+    const int h0 = bh.lo, h1 = bh.hi;
     int ox_a = 0;
     while (ox_a < S) {
       int ox_b = S, px0 = 0;
@@ -111,30 +111,15 @@ __global__ void __launch_bounds__(256) extract_faces_kernel(const uint8_t* __res
             }
             continue;
           }
-          // bytes 0,2 / 1,3 of each dword add up in the two 16-bit halves of one register for at most 256 rows, then
-          // go to the lane's own 32-bit sums in the strip (written by the first 256 rows, added to by deeper ones);
-          // four independent loads in flight per step (clamped row + mask, no branch)
+          // packed sums of at most 256 rows at a time, one round of four loads per trip, which then go to the lane's own
+          // 32-bit sums in the strip (written by the first 256 rows, added to by deeper ones)
           for (int hb = h0; hb < h1; hb += 256) {
-            const int he = min(h1, hb + 256);
-            unsigned pe[4] = {0u, 0u, 0u, 0u}, po[4] = {0u, 0u, 0u, 0u};
-            for (int yy = hb; yy < he; yy += 4) {
-              uint4 v[4];
-#pragma unroll
-              for (int j = 0; j < 4; ++j) memcpy(&v[j], p0 + (size_t)min(yy + j, he - 1) * pitch, 16);  // unaligned: one dwordx4
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const unsigned msk = (yy + j < he) ? 0x00FF00FFu : 0u;
-                const unsigned wv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                  pe[d] += wv[d] & msk;
-                  po[d] += (wv[d] >> 8) & msk;
-                }
-              }
-            }
+            unsigned pe[4], po[4], u[16];
+            area_colsum16<false, 1>(p0, pitch, hb, min(h1, hb + 256), pe, po);
+            area_unpack(pe, po, u);
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
-              uint4 a = uint4{pe[d] & 0xFFFFu, po[d] & 0xFFFFu, pe[d] >> 16, po[d] >> 16};
+              uint4 a = uint4{u[4 * d], u[4 * d + 1], u[4 * d + 2], u[4 * d + 3]};
               if (hb != h0) {
                 const uint4 o = dst[d];
                 a = uint4{a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w};
@@ -152,15 +137,8 @@ __global__ void __launch_bounds__(256) extract_faces_kernel(const uint8_t* __res
         if (t.ok) {
           const int w0 = wtab0[ox], w1 = wtab1[ox];
           unsigned sum[3] = {0u, 0u, 0u};
-          if (!wide) {
-            const unsigned* row = cs + (w0 - px0) * 3;
-            for (int xx = 0; xx < (w1 - w0) * 3; xx += 3) { sum[0] += row[xx]; sum[1] += row[xx + 1]; sum[2] += row[xx + 2]; }
-          } else {
-            for (int yy = h0; yy < h1; ++yy) {
-              const uint8_t* row = base + (size_t)yy * pitch + (size_t)w0 * 3;
-              for (int xx = 0; xx < (w1 - w0) * 3; xx += 3) { sum[0] += row[xx]; sum[1] += row[xx + 1]; sum[2] += row[xx + 2]; }
-            }
-          }
+          if (!wide) area_span(cs + (w0 - px0) * 3, w1 - w0, sum);
+          else area_gather(base, pitch, h0, h1, w0, w1, sum);
           // one IEEE division of the exact integer sum, truncated (.byte())
           const float area = (float)((h1 - h0) * (w1 - w0));
 #pragma unroll
@@ -204,7 +182,7 @@ extern "C" int vnf_extract_faces(const uint8_t* frames, int b, int height, int w
   if (x_out && out_dtype != VNF_F32 && out_dtype != VNF_BF16 && out_dtype != VNF_F16)
     return fail(VNF_E_INVALID, "vnf_extract_faces: bad out_dtype");
   hipStream_t st = (hipStream_t)stream;
-  // row groups: about 1024 workgroups (four fit a CU: 119 VGPRs, 32 KB of strips), at least one output row per wave
+  // row groups: about 1024 workgroups (four fit a CU: 123 VGPRs, 32 KB of strips), at least one output row per wave
   int z = (1024 + n - 1) / n;
   z = z < 1 ? 1 : z;
   const int zmax = (s + 3) / 4;

@@ -59,7 +59,7 @@ constexpr int LDS_RMID = 11 * 11 * 128 + 9 * 9 * 12 * 16, LDS_OMID = 23 * 23 * 1
 // the most any launcher below asks for: a device with less per workgroup cannot run the detector
 constexpr int MTCNN_LDS_MAX = std::max({LDS_NMS, LDS_POST, LDS_RFRONT, LDS_OFRONT, LDS_RMID, LDS_OMID});
 
-// frames whose rows and base address are 16-byte aligned take the row forms of the pyramid and crop kernels
+// frames whose rows and base address are 16-byte aligned take the row form of the pyramid and the strips of the crop kernel
 inline bool frames_aligned(const uint8_t* frames, int W) { return (W * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0; }
 // ... the pyramid only while a frame row fits 64 KiB of LDS as fp32
 inline bool pyramid_by_rows(const uint8_t* frames, int W) { return frames_aligned(frames, W) && (size_t)W * 12 <= 64 * 1024; }

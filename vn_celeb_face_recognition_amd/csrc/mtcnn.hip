@@ -10,15 +10,15 @@
 // bit-identical to the fp32 numpy / torch-CPU statements of the oracle.
 //
 // Kernel map:
-//   K1 pyramid_rows_kernel   u8 frame -> all pyramid levels (adaptive-average bins, normalised); pyramid_kernel is its
-//      fallback for frames whose rows or base address are not 16-byte aligned, or whose rows exceed 64 KiB of LDS as fp32
+//   K1 pyramid_rows_kernel   u8 frame -> all pyramid levels (area bins of area_sum.h, normalised); pyramid_kernel for
+//      frames whose rows or base address are not 16-byte aligned, or whose rows exceed 64 KiB of LDS as fp32
 //   K2 pnet_conv1_pool_direct / pnet_conv2 / pnet_conv3_heads   (all levels and frames per launch)
 //   K3 threshold + compaction fused into pnet_conv3_heads (wave-aggregated atomic slots;
 //      order restored by the sort keys, which carry the cell index)
 //   K4 nms_scale_kernel (per level x frame, IoU 0.5), nms_image_kernel (per frame, IoU 0.7,
 //      + regress, rerec, pad), stage2_post_kernel (IoU 0.7 + bbreg + rerec + pad)
-//   K5 crop_resize_rows_kernel   box table -> N x 3 x {24,48}^2 (area bins, also up-sampling); crop_resize_kernel is
-//      its fallback for unaligned frames
+//   K5 crop_resize_rows_kernel   box table -> N x {24,48}^2 x 4 (the same area bins, also up-sampling); unaligned
+//      frames and crops wider than a strip of column sums take its per-pixel branch
 //   K6 net_front_kernel (conv1 + pool1), net_mid_kernel (conv2 + pool2), then the rest of R-Net / O-Net as MFMA plans
 //      of the conv core (plan_mtcnn.cpp build_rnet / build_onet) over the dense batch of all frames' candidates
 //   K7 stage3_post_kernel    landmarks, bbreg, "Min" NMS, area-descending order
@@ -29,6 +29,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "area_sum.h"
 #include "conv_device.h"
 #include "mtcnn.h"
 #include "nms_device.h"
@@ -49,9 +50,9 @@ __device__ __forceinline__ int find_level(const LevelTable& t, int idx, int whic
 }
 
 // --------------------------------------------------------------------------------------------- K1
-// detect_face.py:71-72: imresample(imgs, (int(h*s+1), int(w*s+1))) then (x-127.5)*0.0078125.
-// interpolate(mode='area') == adaptive average pooling: bin [floor(i*H/oh), ceil((i+1)*H/oh)),
-// value = sum / kh / kw (two divisions, as ATen rounds).  Pixel sums of 8-bit data are exact in fp32.
+// detect_face.py:71-72: imresample(imgs, (int(h*s+1), int(w*s+1))) then (x-127.5)*0.0078125: the bins, sums and finish
+// of area_sum.h.  This form gathers every output pixel's bin byte by byte: the only one for frames whose rows or base
+// address are not 16-byte aligned, or whose rows exceed 64 KiB of LDS as fp32.
 __global__ void pyramid_kernel(const uint8_t* __restrict__ frames, int H, int W, LevelTable t, float* __restrict__ lvl) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= t.tot_px) return;
@@ -59,31 +60,19 @@ __global__ void pyramid_kernel(const uint8_t* __restrict__ frames, int H, int W,
   const int li = find_level(t, idx, 0);
   const LevelDesc L = t.l[li];
   const int p = idx - L.off_px, y = p / L.Ws, x = p - y * L.Ws;
-  const int h0 = (int)(((long long)y * H) / L.Hs), h1 = (int)((((long long)(y + 1)) * H + L.Hs - 1) / L.Hs);
-  const int w0 = (int)(((long long)x * W) / L.Ws), w1 = (int)((((long long)(x + 1)) * W + L.Ws - 1) / L.Ws);
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  const uint8_t* base = frames + (size_t)img * H * W * 3;
-  for (int yy = h0; yy < h1; ++yy) {
-    const uint8_t* row = base + ((size_t)yy * W + w0) * 3;
-    for (int xx = 0; xx < w1 - w0; ++xx) {
-      s0 += (float)row[3 * xx];
-      s1 += (float)row[3 * xx + 1];
-      s2 += (float)row[3 * xx + 2];
-    }
-  }
-  const float kh = (float)(h1 - h0), kw = (float)(w1 - w0);
+  const AreaBin bh = area_bin(y, H, L.Hs), bw = area_bin(x, W, L.Ws);
+  unsigned s[3];
+  area_gather(frames + (size_t)img * H * W * 3, (size_t)W * 3, bh.lo, bh.hi, bw.lo, bw.hi, s);
   float* o = lvl + ((size_t)img * 3) * t.tot_px + L.off_px + p;
-  o[0] = ((s0 / kh) / kw - 127.5f) * 0.0078125f;
-  o[(size_t)t.tot_px] = ((s1 / kh) / kw - 127.5f) * 0.0078125f;
-  o[2 * (size_t)t.tot_px] = ((s2 / kh) / kw - 127.5f) * 0.0078125f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[c * (size_t)t.tot_px] = area_norm(s[c], bh.hi - bh.lo, bw.hi - bw.lo);
 }
 
-// Fast path of K1 for rows that are a whole number of 16-byte chunks (W*3 % 16 == 0: 1920, 1280, 640 ...).
+// The row form of K1 for rows that are a whole number of 16-byte chunks (W*3 % 16 == 0: 1920, 1280, 640 ...).
 // One workgroup per (output row of any level, frame): every lane streams 16-byte chunks of the input
 // rows of that bin row (fully coalesced; each level re-reads the u8 frame once, from L2 / Infinity
 // Cache after the first), keeps per-byte column sums in registers, parks them in LDS, and the
-// output pixels then add their horizontal spans.  Integer sums, so the result is bit-identical to
-// the per-pixel kernel above and to the oracle.
+// output pixels then add their horizontal spans.
 __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __restrict__ frames, int H, int W,
                                                             LevelTable t, float* __restrict__ lvl, const int* __restrict__ row_order) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -96,7 +85,8 @@ __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __rest
   const int li = packed >> 16, r = packed & 0xFFFF;
   const LevelDesc L = t.l[li];
   const int img = blockIdx.x, i = r;
-  const int h0 = (int)(((long long)i * H) / L.Hs), h1 = (int)((((long long)(i + 1)) * H + L.Hs - 1) / L.Hs);
+  const AreaBin bh = area_bin(i, H, L.Hs);
+  const int h0 = bh.lo, h1 = bh.hi;
   const int rowb = W * 3, nchunk = rowb >> 4;
   const uint8_t* base = frames + (size_t)img * H * rowb;
   for (int c0 = 0; c0 < nchunk; c0 += 512) {   // 2 chunks per thread per sweep
@@ -107,8 +97,8 @@ __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __rest
       for (int j = 0; j < 16; ++j) acc[q][j] = 0u;
     const int ca = c0 + threadIdx.x, cb = ca + 256;
     const int cac = min(ca, nchunk - 1), cbc = min(cb, nchunk - 1);   // clamped: unconditional loads, results dropped below
-    // packed accumulation: bytes 0,2 and 1,3 of every dword add up in two 16-bit lanes of one register (5 VALU ops per
-    // dword instead of 11); 256 rows of 255 fit in 16 bits, then the packed sums are flushed into the 32-bit ones
+    // the packed sums of area_colsum16, on this kernel's own load schedule; 256 rows of 255 fit in 16 bits, then the
+    // packed sums are flushed into the 32-bit ones
     for (int y0 = h0; y0 < h1; y0 += 256) {
       const int y1 = min(h1, y0 + 256);
       unsigned pe[2][4], po[2][4];
@@ -136,14 +126,12 @@ __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __rest
           }
       }
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
+      for (int q = 0; q < 2; ++q) {
+        unsigned u[16];
+        area_unpack(pe[q], po[q], u);
 #pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          acc[q][d * 4 + 0] += pe[q][d] & 0xFFFFu;
-          acc[q][d * 4 + 1] += po[q][d] & 0xFFFFu;
-          acc[q][d * 4 + 2] += pe[q][d] >> 16;
-          acc[q][d * 4 + 3] += po[q][d] >> 16;
-        }
+        for (int j = 0; j < 16; ++j) acc[q][j] += u[j];
+      }
     }
     if (ca < nchunk) {
 #pragma unroll
@@ -155,16 +143,13 @@ __global__ void __launch_bounds__(256) pyramid_rows_kernel(const uint8_t* __rest
     }
   }
   __syncthreads();
-  const float kh = (float)(h1 - h0);
   for (int x = threadIdx.x; x < L.Ws; x += blockDim.x) {
-    const int w0 = (int)(((long long)x * W) / L.Ws), w1 = (int)((((long long)(x + 1)) * W + L.Ws - 1) / L.Ws);
-    unsigned s0 = 0, s1 = 0, s2 = 0;
-    for (int xx = w0; xx < w1; ++xx) { s0 += colsum[3 * xx]; s1 += colsum[3 * xx + 1]; s2 += colsum[3 * xx + 2]; }
-    const float kw = (float)(w1 - w0);
+    const AreaBin bw = area_bin(x, W, L.Ws);
+    unsigned s[3] = {0u, 0u, 0u};
+    area_span(colsum + 3 * bw.lo, bw.hi - bw.lo, s);
     float* o = lvl + ((size_t)img * 3) * t.tot_px + L.off_px + i * L.Ws + x;
-    o[0] = (((float)s0 / kh) / kw - 127.5f) * 0.0078125f;
-    o[(size_t)t.tot_px] = (((float)s1 / kh) / kw - 127.5f) * 0.0078125f;
-    o[2 * (size_t)t.tot_px] = (((float)s2 / kh) / kw - 127.5f) * 0.0078125f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c * (size_t)t.tot_px] = area_norm(s[c], h1 - h0, bw.hi - bw.lo);
   }
 }
 
@@ -507,148 +492,86 @@ __global__ void __launch_bounds__(256) nms_image_kernel(const Cand* __restrict__
 }
 
 // --------------------------------------------------------------------------------------------- K5
-// detect_face.py:109-114 / 138-143: imgs[i, :, y-1:ey, x-1:ex] -> imresample(S,S) -> normalise.
-// One workgroup per candidate.  Degenerate rectangles (the reference silently drops them from im_data,
-// which would desynchronise its tables) are flagged and zeroed.
-// Output addressing of the crop kernels.  Compact NHWC4: candidate offs[img]+k-c0 of a dense batch, 4 floats
-// per pixel (RGB + 0), the input layout of the MFMA R/O-Net plans; candidates outside [c0, c0+cap) are skipped.
-// (offs == nullptr selects a planar (3,S,S) table at [img][KR]; the host no longer asks for it.)
-struct CropDst {
-  float* base;      // nullptr: candidate not in this chunk
-  int cs, ps;       // channel stride, pixel stride (floats)
-};
-__device__ __forceinline__ CropDst crop_dst(float* out, const int* offs, int c0, int cap, int img, int k, int S, int KR) {
-  if (!offs) return CropDst{out + ((size_t)img * KR + k) * 3 * S * S, S * S, 1};
+// detect_face.py:109-114 / 138-143: imgs[i, :, y-1:ey, x-1:ex] -> imresample(S,S) -> normalise (area_sum.h).
+// Degenerate rectangles (the reference silently drops them from im_data, which would desynchronise its tables) are
+// flagged and zeroed.
+// Where candidate k of frame img goes: slot offs[img] + k - c0 of the dense batch, compact NHWC4 (RGB + 0, the input
+// layout of the MFMA R/O-Net plans); nullptr for a candidate outside this chunk [c0, c0 + cap).
+__device__ __forceinline__ float* crop_dst(float* out, const int* offs, int c0, int cap, int img, int k, int S) {
   const int ci = offs[img] + k - c0;
-  if (ci < 0 || ci >= cap) return CropDst{nullptr, 0, 0};
-  return CropDst{out + (size_t)ci * S * S * 4, 1, 4};
+  return ci < 0 || ci >= cap ? nullptr : out + (size_t)ci * S * S * 4;
 }
 
-__global__ void __launch_bounds__(256) crop_resize_kernel(const uint8_t* __restrict__ frames, int H, int W,
-                                                           const Row* __restrict__ rows, const int* __restrict__ row_cnt,
-                                                           int S, float* __restrict__ out, int* __restrict__ status,
-                                                           const int* __restrict__ offs, int c0, int cap, int KR) {
-  const int k = blockIdx.x, img = blockIdx.y;
-  if (k >= row_cnt[img]) return;
-  const CropDst d = crop_dst(out, offs, c0, cap, img, k, S, KR);
-  if (!d.base) return;
-  const Row r = rows[(size_t)img * KR + k];
-  const int y0 = r.y - 1, x0 = r.x - 1, ch = r.ey - y0, cw = r.ex - x0;
-  float* o = d.base;
-  if (d.ps == 4 && blockIdx.z == 0)
-    for (int i = threadIdx.x; i < S * S; i += blockDim.x) o[i * 4 + 3] = 0.f;
-  if ((ch <= 0 || cw <= 0) && blockIdx.z != 0) return;
-  if (ch <= 0 || cw <= 0) {
-    for (int i = threadIdx.x; i < S * S; i += blockDim.x) { o[i * d.ps] = 0.f; o[i * d.ps + d.cs] = 0.f; o[i * d.ps + 2 * d.cs] = 0.f; }
-    if (threadIdx.x == 0) atomicOr(status, ST_DEGENERATE);
-    return;
-  }
-  const uint8_t* base = frames + ((size_t)img * H + y0) * (size_t)W * 3 + (size_t)x0 * 3;
-  for (int i = threadIdx.x; i < S * S; i += blockDim.x) {
-    const int oy = i / S, ox = i - oy * S;
-    const int h0 = (oy * ch) / S, h1 = ((oy + 1) * ch + S - 1) / S;
-    const int w0 = (ox * cw) / S, w1 = ((ox + 1) * cw + S - 1) / S;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int yy = h0; yy < h1; ++yy) {
-      const uint8_t* row = base + ((size_t)yy * W + w0) * 3;
-      for (int xx = 0; xx < w1 - w0; ++xx) {
-        s0 += (float)row[3 * xx]; s1 += (float)row[3 * xx + 1]; s2 += (float)row[3 * xx + 2];
-      }
-    }
-    const float kh = (float)(h1 - h0), kw = (float)(w1 - w0);
-    o[i * d.ps] = ((s0 / kh) / kw - 127.5f) * 0.0078125f;
-    o[i * d.ps + d.cs] = ((s1 / kh) / kw - 127.5f) * 0.0078125f;
-    o[i * d.ps + 2 * d.cs] = ((s2 / kh) / kw - 127.5f) * 0.0078125f;
-  }
-}
-
-// Fast path of K5 (rows of W*3 % 16 == 0, crops up to CROP_MAXB bytes wide): each wave owns output
-// rows wave, wave+4, ...; its lanes stream the 16-byte chunks that cover the crop's byte span of
-// every input row of the bin row (coalesced dwordx4 loads instead of per-pixel byte loads), keep
-// per-byte column sums in registers, park them in a wave-private LDS strip, and then add the
-// horizontal bin spans.  Integer sums: bit-identical to the scalar kernel and to the oracle.
 constexpr int CROP_MAXB = 4096;  // bytes of crop row per strip (1365 px)
 
+// grid (candidate, frame, row group).  Each wave owns output rows wave, wave+4, ... of its group; its lanes stream the
+// 16-byte chunks that cover the crop's byte span of every input row of the bin row (coalesced dwordx4 loads instead of
+// per-pixel byte loads), keep per-byte column sums in registers, park them in a wave-private LDS strip, and then add the
+// horizontal bin spans.  A candidate the strips cannot serve is gathered pixel by pixel by its first row group.
 __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __restrict__ frames, int H, int W,
                                                                 const Row* __restrict__ rows, const int* __restrict__ row_cnt,
                                                                 int S, float* __restrict__ out, int* __restrict__ status,
                                                                 const int* __restrict__ offs, int c0, int cap, int KR) {
-  // per-byte column sums of one bin row are at most (rows of a bin) x 255: 16 bits hold 257 rows, deeper bins (frames
-  // taller than ~6000 px at S = 24) take the per-pixel path.  Half the LDS of 32-bit sums -> twice the resident waves.
+  // per-byte column sums of one bin row are at most (rows of a bin) x 255: 16 bits hold 257 rows.  Half the LDS of
+  // 32-bit sums -> twice the resident waves.
   __shared__ __attribute__((aligned(16))) unsigned short strips[4][CROP_MAXB + 32];
   const int k = blockIdx.x, img = blockIdx.y;
   if (k >= row_cnt[img]) return;
-  const CropDst d = crop_dst(out, offs, c0, cap, img, k, S, KR);
-  if (!d.base) return;
+  float* o = crop_dst(out, offs, c0, cap, img, k, S);
+  if (!o) return;
   const Row r = rows[(size_t)img * KR + k];
   const int y0 = r.y - 1, x0 = r.x - 1, ch = r.ey - y0, cw = r.ex - x0;
-  float* o = d.base;
-  if (d.ps == 4 && blockIdx.z == 0)
+  if (blockIdx.z == 0)
     for (int i = threadIdx.x; i < S * S; i += blockDim.x) o[i * 4 + 3] = 0.f;
   if ((ch <= 0 || cw <= 0) && blockIdx.z != 0) return;
   if (ch <= 0 || cw <= 0) {
-    for (int i = threadIdx.x; i < S * S; i += blockDim.x) { o[i * d.ps] = 0.f; o[i * d.ps + d.cs] = 0.f; o[i * d.ps + 2 * d.cs] = 0.f; }
+    for (int i = threadIdx.x; i < S * S; i += blockDim.x) { o[i * 4] = 0.f; o[i * 4 + 1] = 0.f; o[i * 4 + 2] = 0.f; }
     if (threadIdx.x == 0) atomicOr(status, ST_DEGENERATE);
     return;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int rowb = W * 3, bs = x0 * 3, be = (x0 + cw) * 3;
   const int c_lo = bs >> 4, nch = ((be + 15) >> 4) - c_lo, off = bs - (c_lo << 4);
-  const bool slow = nch * 16 > CROP_MAXB + 32 || (ch + S - 1) / S + 1 > 257;
-  if (slow && blockIdx.z != 0) return;
-  if (slow) {  // wider than a strip (or bins too deep for 16-bit sums): per-pixel path for this candidate
-    const uint8_t* base = frames + ((size_t)img * H + y0) * (size_t)W * 3 + (size_t)x0 * 3;
+  const uint8_t* fbase = frames + (size_t)img * H * rowb;
+  // the strips need 16-byte chunks of the frame (rows and base address aligned: the launcher then sends one row group
+  // only), a crop no wider than a strip and bins of at most 257 rows (frames taller than ~6000 px at S = 24)
+  const bool gather = (rowb & 15) != 0 || (reinterpret_cast<uintptr_t>(frames) & 15) != 0 || nch * 16 > CROP_MAXB + 32 ||
+                      (ch + S - 1) / S + 1 > 257;
+  if (gather && blockIdx.z != 0) return;
+  if (gather) {
+    const uint8_t* base = fbase + (size_t)y0 * rowb + (size_t)x0 * 3;
     for (int i = threadIdx.x; i < S * S; i += blockDim.x) {
       const int oy = i / S, ox = i - oy * S;
-      const int h0 = (oy * ch) / S, h1 = ((oy + 1) * ch + S - 1) / S;
-      const int w0 = (ox * cw) / S, w1 = ((ox + 1) * cw + S - 1) / S;
-      unsigned s0 = 0, s1 = 0, s2 = 0;
-      for (int yy = h0; yy < h1; ++yy) {
-        const uint8_t* row = base + ((size_t)yy * W + w0) * 3;
-        for (int xx = 0; xx < w1 - w0; ++xx) { s0 += row[3 * xx]; s1 += row[3 * xx + 1]; s2 += row[3 * xx + 2]; }
-      }
-      const float kh = (float)(h1 - h0), kw = (float)(w1 - w0);
-      o[i * d.ps] = (((float)s0 / kh) / kw - 127.5f) * 0.0078125f;
-      o[i * d.ps + d.cs] = (((float)s1 / kh) / kw - 127.5f) * 0.0078125f;
-      o[i * d.ps + 2 * d.cs] = (((float)s2 / kh) / kw - 127.5f) * 0.0078125f;
+      const AreaBin bh = area_bin(oy, ch, S), bw = area_bin(ox, cw, S);
+      unsigned s[3];
+      area_gather(base, (size_t)rowb, bh.lo, bh.hi, bw.lo, bw.hi, s);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[i * 4 + c] = area_norm(s[c], bh.hi - bh.lo, bw.hi - bw.lo);
     }
     return;
   }
-  const uint8_t* fbase = frames + (size_t)img * H * rowb;
   unsigned short* cs = strips[wave];
   // blockIdx.z splits the S output rows into gridDim.z groups, so one large box (its bins are tens of input rows
   // deep) is spread over several workgroups instead of setting the duration of the whole launch
   const int zrows = (S + (int)gridDim.z - 1) / (int)gridDim.z;
   const int oy_lo = (int)blockIdx.z * zrows, oy_hi = min(S, oy_lo + zrows);
-  // per-byte column sums of input rows [h0,h1) of one 16-byte chunk column: four independent loads in flight per
-  // step (clamped row + byte mask instead of a branch, so the loads are not serialised behind their predicates)
-  auto colsum = [&](int c, int h0, int h1, unsigned (&acc)[16]) {
-    // bytes 0,2 / 1,3 of each dword accumulate in the two 16-bit halves of one register (a bin has at most 257 rows
-    // here: deeper ones took the per-pixel path above), unpacked once at the end
-    unsigned pe[4] = {0u, 0u, 0u, 0u}, po[4] = {0u, 0u, 0u, 0u};
-    const uint8_t* p0 = fbase + (size_t)y0 * rowb + ((size_t)(c_lo + c) << 4);
-    for (int yy = h0; yy < h1; yy += 4) {
-      uint4 v[4];
+  // per-byte column sums of input rows [h0,h1) of chunk column c, as 16-bit pairs into the strip at dst.  Two rounds
+  // per trip, eight loads in flight: the kernel waits on L2 latency, not on bandwidth.
+  auto colsum = [&](int c, AreaBin bh, unsigned short* dst) {
+    unsigned pe[4], po[4], acc[16];
+    area_colsum16<true, 2>(fbase + (size_t)y0 * rowb + ((size_t)(c_lo + c) << 4), (size_t)rowb, bh.lo, bh.hi, pe, po);
+    area_unpack(pe, po, acc);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const uint4*>(p0 + (size_t)min(yy + j, h1 - 1) * rowb);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned msk = (yy + j < h1) ? 0x00FF00FFu : 0u;
-        const unsigned wv[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          pe[d] += wv[d] & msk;
-          po[d] += (wv[d] >> 8) & msk;
-        }
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      acc[d * 4 + 0] = pe[d] & 0xFFFFu;
-      acc[d * 4 + 1] = po[d] & 0xFFFFu;
-      acc[d * 4 + 2] = pe[d] >> 16;
-      acc[d * 4 + 3] = po[d] >> 16;
-    }
+    for (int j = 0; j < 2; ++j)
+      reinterpret_cast<uint4*>(dst)[j] = uint4{acc[8 * j] | (acc[8 * j + 1] << 16), acc[8 * j + 2] | (acc[8 * j + 3] << 16),
+                                               acc[8 * j + 4] | (acc[8 * j + 5] << 16), acc[8 * j + 6] | (acc[8 * j + 7] << 16)};
+  };
+  // channel cch of output (oy, ox) from the strip row `row` (its byte 0 = the crop's first byte)
+  auto finish = [&](const unsigned short* row, int oy, int ox, int cch, AreaBin bh) {
+    const AreaBin bw = area_bin(ox, cw, S);
+    unsigned sum = 0;
+    for (int xx = bw.lo; xx < bw.hi; ++xx) sum += row[xx * 3 + cch];
+    o[(oy * S + ox) * 4 + cch] = area_norm(sum, bh.hi - bh.lo, bw.hi - bw.lo);
   };
   if (nch <= 32) {
     // narrow crops (the common case: a 100-px box spans ~20 chunks): a wave takes R = 64/nch output rows at
@@ -657,15 +580,7 @@ __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __
     const int R = min(64 / nch, (oy_hi - oy_lo + 3) / 4), sub = lane / nch, c = lane - sub * nch;
     for (int oy0 = oy_lo + wave * R; oy0 < oy_hi; oy0 += 4 * R) {
       const int oy = oy0 + sub;
-      if (sub < R && oy < oy_hi) {
-        unsigned acc[16];
-        colsum(c, (oy * ch) / S, ((oy + 1) * ch + S - 1) / S, acc);
-        uint4* dst = reinterpret_cast<uint4*>(cs + (sub * nch + c) * 16);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          dst[j] = uint4{acc[8 * j] | (acc[8 * j + 1] << 16), acc[8 * j + 2] | (acc[8 * j + 3] << 16),
-                         acc[8 * j + 4] | (acc[8 * j + 5] << 16), acc[8 * j + 6] | (acc[8 * j + 7] << 16)};
-      }
+      if (sub < R && oy < oy_hi) colsum(c, area_bin(oy, ch, S), cs + (sub * nch + c) * 16);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       for (int q = lane; q < R * 3 * S; q += 64) {
@@ -673,12 +588,7 @@ __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __
         const int oy2 = oy0 + s2;
         if (oy2 < oy_hi) {
           const int cch = q2 / S, ox = q2 - cch * S;
-          const int h0 = (oy2 * ch) / S, h1 = ((oy2 + 1) * ch + S - 1) / S;
-          const int w0 = (ox * cw) / S, w1 = ((ox + 1) * cw + S - 1) / S;
-          const unsigned short* row = cs + s2 * nch * 16 + off;
-          unsigned sum = 0;
-          for (int xx = w0; xx < w1; ++xx) sum += row[xx * 3 + cch];
-          o[(oy2 * S + ox) * d.ps + cch * d.cs] = (((float)sum / (float)(h1 - h0)) / (float)(w1 - w0) - 127.5f) * 0.0078125f;
+          finish(cs + s2 * nch * 16 + off, oy2, ox, cch, area_bin(oy2, ch, S));
         }
       }
       __builtin_amdgcn_wave_barrier();
@@ -686,28 +596,13 @@ __global__ void __launch_bounds__(256) crop_resize_rows_kernel(const uint8_t* __
     return;
   }
   for (int oy = oy_lo + wave; oy < oy_hi; oy += 4) {
-    const int h0 = (oy * ch) / S, h1 = ((oy + 1) * ch + S - 1) / S;
-    for (int cbase = 0; cbase < nch; cbase += 64) {
-      const int c = cbase + lane;
-      if (c < nch) {
-        unsigned acc[16];
-        colsum(c, h0, h1, acc);
-        uint4* dst = reinterpret_cast<uint4*>(cs + c * 16);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          dst[j] = uint4{acc[8 * j] | (acc[8 * j + 1] << 16), acc[8 * j + 2] | (acc[8 * j + 3] << 16),
-                         acc[8 * j + 4] | (acc[8 * j + 5] << 16), acc[8 * j + 6] | (acc[8 * j + 7] << 16)};
-      }
-    }
+    const AreaBin bh = area_bin(oy, ch, S);
+    for (int c = lane; c < nch; c += 64) colsum(c, bh, cs + c * 16);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const float kh = (float)(h1 - h0);
     for (int q = lane; q < 3 * S; q += 64) {
       const int cch = q / S, ox = q - cch * S;
-      const int w0 = (ox * cw) / S, w1 = ((ox + 1) * cw + S - 1) / S;
-      unsigned sum = 0;
-      for (int xx = w0; xx < w1; ++xx) sum += cs[off + xx * 3 + cch];
-      o[(oy * S + ox) * d.ps + cch * d.cs] = (((float)sum / kh) / (float)(w1 - w0) - 127.5f) * 0.0078125f;
+      finish(cs + off, oy, ox, cch, bh);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -1140,7 +1035,6 @@ __global__ void pack_results_kernel(const int* __restrict__ cnt_block, int ncnt,
 // launchers (mtcnn.h)
 hipError_t launch_pyramid(const uint8_t* frames, int B, int H, int W, const LevelTable& t, float* lvl, const int* row_order,
                           hipStream_t s) {
-  // bin sums must stay exact in fp32 (< 2^24): always true below 256x256-pixel bins
   if (row_order) {
     int rows = 0;
     for (int l = 0; l < t.n; ++l) rows += t.l[l].Hs;
@@ -1184,11 +1078,10 @@ hipError_t launch_nms_stage1(const Cand* cand, const int* cells, const int* cand
 
 hipError_t launch_crop_resize(const uint8_t* frames, int B, int H, int W, const Row* rows, const int* row_cnt, int maxc, int S,
                               float* out, int* status, const int* offs, int c0, int cap, int KR, hipStream_t s) {
-  if (frames_aligned(frames, W))
-    // S / 8 row groups per candidate: 8 output rows per workgroup = 4 waves x 2 rows (measured best of 2..8 groups)
-    hipLaunchKernelGGL(crop_resize_rows_kernel, dim3(maxc, B, S / 8), dim3(256), 0, s, frames, H, W, rows, row_cnt, S, out, status, offs, c0, cap, KR);
-  else
-    hipLaunchKernelGGL(crop_resize_kernel, dim3(maxc, B), dim3(256), 0, s, frames, H, W, rows, row_cnt, S, out, status, offs, c0, cap, KR);
+  // S / 8 row groups per candidate: 8 output rows per workgroup = 4 waves x 2 rows (measured best of 2..8 groups); one
+  // where the kernel gathers every candidate in its first group
+  const int groups = frames_aligned(frames, W) ? S / 8 : 1;
+  hipLaunchKernelGGL(crop_resize_rows_kernel, dim3(maxc, B, groups), dim3(256), 0, s, frames, H, W, rows, row_cnt, S, out, status, offs, c0, cap, KR);
   return hipGetLastError();
 }
 
