@@ -7,7 +7,8 @@ transforms_default (the reference imports a name that does not exist); images ar
 shape so mixed 181x181 / 127x127 directories work, and crops that are not 160x160 are
 centre-cropped or zero-padded to the encoder's 160x160 input; the empty trailing batch the
 reference always appends is skipped.  `-w` may be a local state_dict path; `-dv GPU` is the only
-device (there is no CPU path)."""
+device (there is no CPU path).  `-enc` / `-eargs` (build extension): another encoder of the plugin registry with its
+JSON kwargs, as demo_image.py resolves it; crops are then fitted to that encoder's input size."""
 import argparse
 import os
 from pathlib import Path
@@ -17,6 +18,8 @@ import torch
 from PIL import Image
 
 from vn_celeb_face_recognition_amd import dist as vdist
+from vn_celeb_face_recognition_amd import models as model_md
+from vn_celeb_face_recognition_amd.cli_utils import read_json
 from vn_celeb_face_recognition_amd.models import InceptionResnetV1
 from vn_celeb_face_recognition_amd.pipeline import transforms_default
 
@@ -64,7 +67,7 @@ def cal_embedding(data_dir, batch_size, model, transforms, output_dir, device, r
     def batches():
         for idx, batch_file in enumerate(list_batch_files):
             print('Processing for {}/{} batchs:'.format(idx, n_batchs))
-            yield create_image_tensors(Path(data_dir), batch_file, transforms)
+            yield create_image_tensors(Path(data_dir), batch_file, transforms, size=model.input_size)
 
     # batches are independent: up to three are in flight on rotating streams (the next batch's decode and upload
     # and the previous batch's .npz writes overlap the GPU work)
@@ -82,12 +85,21 @@ if __name__ == "__main__":
     args_parser.add_argument('-dv', '--device', default='GPU')
     args_parser.add_argument('--compute_dtype', default='f16x2', choices=['f16x2', 'f32', 'bf16', 'f16'],
                              help='f16x2 (default): the <=1e-4 parity path all CLIs share; bf16/f16: faster, 5e-3 / 6e-4 embedding error')
+    args_parser.add_argument('-enc', '--encoder', default='InceptionResnetV1', type=str)
+    args_parser.add_argument('-eargs', '--encoder_args', default=None, type=str,
+                             help='JSON kwargs of the encoder (cfg/embedding/*.json); without it InceptionResnetV1 takes -w')
     args = args_parser.parse_args()
     if args.device != 'GPU':
         raise SystemExit("this build runs on MI355X only: use -dv GPU (there is no CPU path)")
     rank, world, local = vdist.init_from_env()
     device = 'cuda:%d' % local
     pre = None if args.pre_trained in ('none', 'None', 'generator') else args.pre_trained
-    model = InceptionResnetV1(pretrained=pre, device=device, compute_dtype=args.compute_dtype,
-                              max_batch=max(args.batch_size, 1))
+    if args.encoder_args is None and args.encoder == 'InceptionResnetV1':
+        model = InceptionResnetV1(pretrained=pre, device=device, compute_dtype=args.compute_dtype,
+                                  max_batch=max(args.batch_size, 1))
+    else:
+        kwargs = read_json(args.encoder_args) if args.encoder_args else {}
+        kwargs.setdefault('compute_dtype', args.compute_dtype)
+        kwargs.setdefault('max_batch', max(args.batch_size, 1))
+        model = getattr(model_md, args.encoder)(**kwargs).to(device)
     cal_embedding(args.data_dir, args.batch_size, model, transforms_default, args.output_dir, device, rank, world)

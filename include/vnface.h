@@ -73,6 +73,7 @@ extern "C" {
 #define VNF_ARCH_IRV1 0   /* InceptionResnetV1, 160x160 input, L2-normalised 512-d output */
 #define VNF_ARCH_IR100 1  /* IResNet-100 (ArcFace), 112x112 input, 512-d BN1d features */
 #define VNF_ARCH_RN50_2B 2 /* ResNet-50 with class + projection heads (emotions), 224x224 input: vnf_emotion_create only */
+#define VNF_ARCH_SEIR101 3 /* SE-IR ResNet-101 (resnet_encoder.py resnet101(use_se=True)), 112x112 input, L2-normalised 512-d output */
 
 typedef struct vnf_handle_s* vnf_handle;
 
@@ -131,7 +132,7 @@ int vnf_encoder_set_contexts(vnf_handle h, int n);
  * (vnf_encoder_create ignores logits.* and builds no head.)  The head reads the fp32 features the plan leaves before its
  * last op -- last_bn's output before the L2 normalisation for IRv1, `features` for IR-100 -- and is one exact-f32
  * linear layer in every compute_dtype.  Everything else about the handle is as vnf_encoder_create makes it: vnf_embed
- * returns the same embeddings. */
+ * returns the same embeddings.  VNF_ARCH_SEIR101 is refused (VNF_E_INVALID): resnet_encoder.py has no `logits` layer. */
 int vnf_encoder_create_classifier(int arch, const vnf_tensor_desc* weights, int n_weights, int compute_dtype,
                                   int max_batch, int num_classes, vnf_handle* out);
 /* forward() of a classify model (inception_resnet_v1.py:298-300 F.log_softmax, iresnet_encoder.py:155-157): the plan,
@@ -186,6 +187,16 @@ int vnf_softmax_topk(const float* logits, int n, int c, int k, int32_t* idx, flo
  * layouts: dtype VNF_F32 | VNF_BF16 | VNF_F16 (C % 4 / 8 / 8 == 0) or VNF_F16X2 (4-byte (hi, lo) pairs, C % 4 == 0;
  * planar != 0: 8-channel units [8 hi][8 lo], C % 8 == 0, what the encoders keep).  Padding compares as -inf. */
 int vnf_maxpool3s2p1(const void* x, int dtype, int planar, int n, int h, int w, int c, void* y, void* stream);
+
+/* The tail of an IRBlock of the SE-IR ResNet-101 (resnet_encoder.py:98-113,142-149) on its own, for parity of the
+ * plan's squeeze-and-excitation kernels at their own shapes:
+ *     y = prelu(t * gate + res, slope_out),   gate = sigmoid(w2 . prelu(w1 . mean_hw(t) + b1, slope_se) + b2)
+ * t, res, y: device NHWC (N,H,W,C) in one of the encoders' storage layouts (dtype VNF_F32 | VNF_BF16 | VNF_F16, or
+ * VNF_F16X2 with planar != 0: 8-channel units [8 hi][8 lo]); w1 (C/16,C), b1 (C/16), w2 (C,C/16), b2 (C): device fp32;
+ * C % 16 == 0, C <= 1024.  Sums and the gate are fp32, the result is rounded once to the storage type.  The call is
+ * bitwise repeatable, an image's result does not depend on N, and it returns after the work on `stream` is done. */
+int vnf_se_block(const void* t, const void* res, int dtype, int planar, int n, int h, int w, int c, const float* w1,
+                 const float* b1, float slope_se, const float* w2, const float* b2, float slope_out, void* y, void* stream);
 
 /* classifier ------------------------------------------------------------------------------- */
 int vnf_mlp_create(const vnf_tensor_desc* weights, int n_weights, int input_dim, int num_classes,

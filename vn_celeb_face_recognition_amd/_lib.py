@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvnface.so")
 
 VNF_F32, VNF_BF16, VNF_F16, VNF_I64, VNF_U8, VNF_F16X2 = 0, 1, 2, 3, 4, 5
-VNF_ARCH_IRV1, VNF_ARCH_IR100, VNF_ARCH_RN50_2B = 0, 1, 2
+VNF_ARCH_IRV1, VNF_ARCH_IR100, VNF_ARCH_RN50_2B, VNF_ARCH_SEIR101 = 0, 1, 2, 3
 
 
 class VnfError(RuntimeError):
@@ -60,6 +60,7 @@ SIGNATURES = {
     "vnf_augment_faces": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _P, _P]),
     "vnf_softmax_topk": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "vnf_maxpool3s2p1": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vnf_se_block": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, ctypes.c_float, _P, _P]),
     "vnf_mlp_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vnf_classify": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "vnf_mlp_trainer_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float,

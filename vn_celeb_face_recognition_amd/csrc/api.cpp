@@ -67,7 +67,10 @@ int vnf_encoder_create(int arch, const vnf_tensor_desc* weights, int n_weights, 
                        vnf_handle* out) {
   API_GUARD_BEGIN
   return create_encoder(arch, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
-    return arch == VNF_ARCH_IRV1 ? build_irv1(e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(e, wm) : fail(VNF_E_INVALID, "unknown arch");
+    return arch == VNF_ARCH_IRV1    ? build_irv1(e, wm)
+           : arch == VNF_ARCH_IR100 ? build_ir100(e, wm)
+           : arch == VNF_ARCH_SEIR101 ? build_seir101(e, wm)
+                                      : fail(VNF_E_INVALID, "unknown arch");
   });
   API_GUARD_END
 }
@@ -97,6 +100,8 @@ int vnf_encoder_create_classifier(int arch, const vnf_tensor_desc* weights, int 
                                   int num_classes, vnf_handle* out) {
   API_GUARD_BEGIN
   if (num_classes < 1 || num_classes > (1 << 20)) return fail(VNF_E_INVALID, "vnf_encoder_create_classifier: num_classes must be 1..2^20");
+  if (arch == VNF_ARCH_SEIR101)
+    return fail(VNF_E_INVALID, "vnf_encoder_create_classifier: the SE-IR ResNet-101 has no `logits` layer (models/resnet_encoder.py:154-222)");
   return create_encoder(arch, weights, n_weights, compute_dtype, max_batch, out, [&](Encoder& e, WeightMap& wm) {
     const int r = arch == VNF_ARCH_IRV1 ? build_irv1(e, wm) : arch == VNF_ARCH_IR100 ? build_ir100(e, wm) : fail(VNF_E_INVALID, "unknown arch");
     return r != VNF_OK ? r : attach_head(e, wm, num_classes);
@@ -165,6 +170,14 @@ int vnf_encoder_tap(vnf_handle h, const char* name, int n, float* host_out, int6
   if (!e || !name) return fail(VNF_E_INVALID, "not an encoder handle");
   auto it = e->taps.find(name);
   if (it == e->taps.end()) return fail(VNF_E_INVALID, std::string("no such tap: ") + name);
+  if (it->second.buf == -2) {   // the fp32 features of the last call (emb_raw), as (n,C,1,1)
+    const int C = it->second.C;
+    if (shape_out) { shape_out[0] = n; shape_out[1] = C; shape_out[2] = 1; shape_out[3] = 1; }
+    if (n > e->max_batch || (int64_t)n * C > capacity || !host_out) return fail(VNF_E_CAPACITY, "tap capacity");
+    for (int i = 0; i < n; ++i)
+      VNF_HIP(hipMemcpy(host_out + (size_t)i * C, e->emb_raw + (size_t)i * e->emb_ld + it->second.coff, (size_t)C * 4, hipMemcpyDeviceToHost));
+    return VNF_OK;
+  }
   if (!e->buf_materialised(it->second.buf))
     return fail(VNF_E_INVALID, std::string("tap '") + name + "' is computed inside a fused kernel and never reaches memory in this "
                 "compute dtype: create the encoder under VNF_FUSE=0 (or use a dtype without fused stacks) to read it");
@@ -345,6 +358,29 @@ int vnf_maxpool3s2p1(const void* x, int dtype, int planar, int n, int h, int w, 
   const PoolWindow win = {3, 1, false};
   if ((size_t)n * pool_out_size(h, win) * pool_out_size(w, win) * (size_t)c >= ((size_t)1 << 31)) return fail(VNF_E_CAPACITY, "tensor too large");
   VNF_HIP(launch_maxpool(x, c, y, c, dt, n, h, w, c, win, (hipStream_t)stream));
+  return VNF_OK;
+  API_GUARD_END
+}
+
+int vnf_se_block(const void* t, const void* res, int dtype, int planar, int n, int h, int w, int c, const float* w1, const float* b1,
+                 float slope_se, const float* w2, const float* b2, float slope_out, void* y, void* stream) {
+  API_GUARD_BEGIN
+  if (n < 0 || h < 1 || w < 1 || c < 1 || (n > 0 && (!t || !res || !y)) || !w1 || !b1 || !w2 || !b2) return fail(VNF_E_INVALID, "bad argument");
+  if (dtype != VNF_F32 && dtype != VNF_BF16 && dtype != VNF_F16 && dtype != VNF_F16X2) return fail(VNF_E_INVALID, "bad dtype");
+  if (dtype == VNF_F16X2 && !planar) return fail(VNF_E_INVALID, "vnf_se_block: split-f16 tensors in the planar layout only");
+  const int dt = dtype == VNF_F16X2 ? F16P : dtype;
+  if (c % 16 || c > 1024) return fail(VNF_E_INVALID, "vnf_se_block: c must be a multiple of 16, at most 1024");
+  if ((size_t)h * w * (size_t)c >= ((size_t)1 << 31) || n > 65535) return fail(VNF_E_CAPACITY, "tensor too large");
+  const int slices = se_slices(dt, h * w, c);
+  if (slices < 1) return fail(VNF_E_INVALID, "vnf_se_block: unsupported shape");
+  if (n == 0) return VNF_OK;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = nullptr;
+  VNF_HIP(hipMalloc(&part, (size_t)n * slices * c * 4));
+  hipError_t err = launch_se_block(t, res, y, dt, n, h * w, c, SeWeights{w1, b1, w2, b2, slope_se, slope_out}, part, (size_t)slices * c, s);
+  if (err == hipSuccess) err = hipStreamSynchronize(s);   // the scratch is freed here
+  (void)hipFree(part);
+  if (err != hipSuccess) return fail(VNF_E_HIP, hipGetErrorString(err));
   return VNF_OK;
   API_GUARD_END
 }

@@ -313,6 +313,9 @@ static const struct { PoolWindow w; int dtype; void (*go)(const PoolArgs&); } kP
     {{3, 1, false}, F32, maxpool_go<float, 3, 1, false>},    {{3, 1, false}, BF16, maxpool_go<__bf16, 3, 1, false>},
     {{3, 1, false}, F16, maxpool_go<_Float16, 3, 1, false>}, {{3, 1, false}, F16X2, maxpool_go<sf16, 3, 1, false>},
     {{3, 1, false}, F16P, maxpool_go<pf16, 3, 1, false>},
+    // 2x2 floor: SE-IR ResNet-101 stem
+    {{2, 0, false}, F32, maxpool_go<float, 2, 0, true>},     {{2, 0, false}, BF16, maxpool_go<__bf16, 2, 0, true>},
+    {{2, 0, false}, F16, maxpool_go<_Float16, 2, 0, true>},  {{2, 0, false}, F16P, maxpool_go<pf16, 2, 0, true>},
 };
 
 hipError_t launch_maxpool(const void* x, int ldx, void* y, int ldy, int dtype, int n, int H, int W, int C, PoolWindow w,

@@ -327,6 +327,15 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
             VNF_HIP(launch_upsample_add(at_f32(op.src, n0), ib->H, ib->W, at_f32(op.dst, n0), ob.H, ob.W, ob.C, nn, dtype == F16X2, s));
             break;
           }
+          case Op::SE: {
+            const SeLayer& L = ses[op.layer];
+            const Buf& pb = bufs[L.part_buf];
+            hipError_t err = launch_se_block(at(op.src, n0), at(op.res, n0), at(op.dst, n0), dtype, nn, ib->H * ib->W, L.C,
+                                             SeWeights{L.w1, L.b1, L.w2, L.b2, L.slope_se, L.slope_out}, (float*)at(L.part_buf, n0),
+                                             pb.elems_per_image() * dtype_size(dtype) / 4, s);
+            if (err != hipSuccess) return fail(VNF_E_HIP, L.name + ": " + hipGetErrorString(err));
+            break;
+          }
           case Op::HEADS: {
             const float* raw = emb_raw + (size_t)n0 * emb_ld;
             if (out) VNF_HIP(launch_copy_rows_f32(raw, emb_ld, out + (size_t)n0 * op.n_cls, op.n_cls, nn, op.n_cls, s));
@@ -359,6 +368,7 @@ static const char* op_label(const Op& op) {
     case Op::RSTEM: return "retina_stem (u8 frames -> conv0)";
     case Op::DWPW: return "dw3x3+pw1x1 fused";
     case Op::HEADS: return "heads";
+    case Op::SE: return "se";
   }
   return "?";
 }
@@ -400,6 +410,12 @@ int Encoder::write_report(std::vector<hipEvent_t>& prof_ev, const std::vector<in
       const double gf = 2.0 * convs[op.layer].macs_alg * n / 1e9;
       snprintf(line, sizeof line, "%-28s %-60s %8.4f ms  %8.1f GFLOP %8.1f TFLOP/s\n", "conv2d_1a (direct, NCHW in)",
                "3x3 s2 3->32 on the caller's tensor, exact f32 (MFMA / VALU)", t, gf, tflops(gf));
+    } else if (op.kind == Op::SE) {
+      // algorithmic traffic: t twice (mean, product), the residual once, the result once
+      const Buf& b = bufs[op.src];
+      const double mb = 4.0 * b.elems_per_image() * dtype_size(dtype) * n / 1e6;
+      snprintf(line, sizeof line, "%-28s se %dx%dx%-4d squeeze + excite/apply %24s %8.4f ms  %8.1f MB    %8.3f TB/s\n",
+               ses[op.layer].name.c_str(), b.H, b.W, b.C, "", t, mb, t > 0 ? mb / t / 1e3 : 0.0);
     } else {
       snprintf(line, sizeof line, "%-28s %-8s %60s %8.4f ms\n", "", op_label(op), "", t);
     }

@@ -80,10 +80,11 @@ struct ConvLayer {
 };
 
 struct Op {
-  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, STEM1, DWCONV, UPADD, RSTEM, DWPW, HEADS } kind;
+  enum Kind { PACK, CONV, MAXPOOL, AVGPOOL, L2NORM, COPYOUT, STEM1, DWCONV, UPADD, RSTEM, DWPW, HEADS, SE } kind;
   int src = -1;                   // source buffer
   int dst = -1, dst_coff = 0;     // destination buffer and the channel offset of the slice written in it
-  int layer = -1;                 // index into Encoder::convs (CONV, STEM1), dws (DWCONV) or dwpws (DWPW)
+  int layer = -1;                 // index into Encoder::convs (CONV, STEM1), dws (DWCONV), dwpws (DWPW) or ses (SE)
+  int res = -1;                   // SE: the residual buffer
   PoolWindow window = {0, 0, false};   // MAXPOOL: stride-2 window (launch_maxpool)
   int frame_h = 0, frame_w = 0;   // RSTEM: size of the u8 frames the caller passes as x
   int n_cls = 0, n_proj = 0, proj_col = 0;   // HEADS: widths of the two heads, first projection column of emb_raw
@@ -103,6 +104,7 @@ struct Op {
   static Op dwpw(int layer) { Op o{DWPW}; o.layer = layer; return o; }
   static Op upadd(int src, int dst) { Op o{UPADD}; o.src = src; o.dst = dst; return o; }   // dst += nearest-upsampled src
   static Op rstem(int frame_h, int frame_w, int dst) { Op o{RSTEM}; o.frame_h = frame_h; o.frame_w = frame_w; o.dst = dst; return o; }
+  static Op se(int layer, int src, int res, int dst) { Op o{SE}; o.layer = layer; o.src = src; o.res = res; o.dst = dst; return o; }   // dst = prelu(src * gate + res)
   static Op heads(int n_cls, int n_proj, int proj_col) { Op o{HEADS}; o.n_cls = n_cls; o.n_proj = n_proj; o.proj_col = proj_col; return o; }
 };
 
@@ -117,6 +119,13 @@ struct DwPwLayer {   // conv_dw in one kernel (launch_dwpw): depthwise 3x3 + BN 
   float *dw = nullptr, *dbias = nullptr, *pw = nullptr, *pbias = nullptr;
   float slope = 0.f;
   std::string name;
+};
+
+struct SeLayer {   // squeeze-and-excitation + residual + PReLU behind conv2 / bn2 of an IRBlock (launch_se_block)
+  std::string name;
+  int C, part_buf;   // part_buf: plan buffer that holds the squeeze launch's fp32 slice sums
+  float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+  float slope_se = 0.f, slope_out = 0.f;
 };
 
 struct Group { int first, last, chunk; };
@@ -145,7 +154,7 @@ struct FusedStack {
   int end() const { return ext ? ext_last : last; }   // one past the last op the stack's launch replaces
 };  // ops [first,last) run per `chunk` images (L3 residency)
 
-struct Tap { int buf, coff, C; };
+struct Tap { int buf, coff, C; };   // buf -2: columns [coff, coff + C) of emb_raw
 
 // Every switch an encoder takes from the environment (VNF_<FIELD NAME>; INTEGRATION.md has the table), read once, when
 // the Encoder is constructed.  Plans, fused stacks, the autotuner and the launchers take their values from here.
@@ -179,6 +188,7 @@ struct Encoder : HandleBase {
   std::vector<ConvLayer> convs;
   std::vector<DwLayer> dws;
   std::vector<DwPwLayer> dwpws;
+  std::vector<SeLayer> ses;
   float *rstem_wa = nullptr, *rstem_bias = nullptr;   // RetinaFace stem (Op::RSTEM): MFMA lane table [7][64], bias [8]
   std::vector<Op> ops;
   std::vector<Group> groups;
@@ -239,6 +249,8 @@ const char* fused_detail(const FusedStack& f);
 // the plan builders (plan_*.cpp)
 int build_irv1(Encoder& e, WeightMap& wm);
 int build_ir100(Encoder& e, WeightMap& wm);
+// SE-IR ResNet-101 (models/resnet_encoder.py:116-222, use_se=True), 112 x 112 input, L2-normalised output
+int build_seir101(Encoder& e, WeightMap& wm);
 // ResNet-50 with a class head and a projection head (models/resnet_2_branch.py:12-70), 224 x 224 input
 int build_rn50_2b(Encoder& e, WeightMap& wm, int num_classes, int num_projections);
 // RetinaFace (mobilenet0.25) on the exact-f32 core for an H x W input: buffer 0 = NHWC4 mean-subtracted input (written by

@@ -69,6 +69,7 @@ hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int 
 //   3x3 ceil   F32 F16X2                 nn.MaxPool2d(3, 2, ceil_mode=True)  R-Net, O-Net
 //   2x2 ceil   F32 F16X2                 nn.MaxPool2d(2, 2, ceil_mode=True)  O-Net
 //   3x3 pad 1  F32 BF16 F16 F16X2 F16P   nn.MaxPool2d(3, 2, 1)               ResNet-50, vnf_maxpool3s2p1
+//   2x2 floor  F32 BF16 F16 F16P         nn.MaxPool2d(2, 2)                  SE-IR ResNet-101 stem
 // ldx, ldy and C are multiples of the layout's storage unit (dtype_chan_align); a floor-mode window fits the image
 struct PoolWindow { int k, pad; bool ceil; };
 inline int pool_out_size(int in, PoolWindow w) {   // < 1: the image is smaller than a floor-mode window
@@ -97,6 +98,16 @@ hipError_t launch_copy_rows_f32(const float* src, int lds, float* dst, int ldd, 
 
 // global average pool NHWC (n,HW,C) -> (n,C); C and ldx are multiples of the layout's storage unit (dtype_chan_align)
 hipError_t launch_avgpool(const void* x, int ldx, void* y, int dtype, int n, int HW, int C, hipStream_t s);
+
+// Squeeze-and-excitation tail of an IRBlock (se_block.hip), dense NHWC tensors (n,HW,C) of F32 / BF16 / F16 / F16P:
+//   y = prelu(t * gate + res, slope_out),  gate = sigmoid(w2 . prelu(w1 . mean_hw(t) + b1, slope_se) + b2)
+// w1 [C/16][C], b1 [C/16], w2 [C][C/16], b2 [C]: device fp32; C % 16 == 0, 16 <= C <= 1024.  Two launches; `part` is their
+// scratch: se_slices(dtype, HW, C) * C channel sums per image (0 slices: the shape is not supported), images part_stride
+// floats apart.  Bitwise repeatable, and an image's result does not depend on the batch around it.  y may be t or res.
+struct SeWeights { const float *w1, *b1, *w2, *b2; float slope_se, slope_out; };
+int se_slices(int dtype, int HW, int C);
+hipError_t launch_se_block(const void* t, const void* res, void* y, int dtype, int n, int HW, int C, const SeWeights& w, float* part,
+                           size_t part_stride, hipStream_t s);
 
 // rows of fp32 (n,C): y = x / max(||x||_2, 1e-12)
 hipError_t launch_l2norm(const float* x, float* y, int n, int C, hipStream_t s);

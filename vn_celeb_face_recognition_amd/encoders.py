@@ -2,6 +2,7 @@
 
   InceptionResnetV1  <-  /root/reference/models/inception_resnet_v1.py:184-303
   iresnet100         <-  /root/reference/models/iresnet_encoder.py:64-196
+  resnet101          <-  /root/reference/models/resnet_encoder.py:98-254 (use_se=True: the SE-IR ResNet-101)
 
 Same constructor kwargs, `.to()`, `.eval()`, `load_state_dict()`, and `__call__((N,3,S,S)) ->
 (N,512)` on the same device (demo_image.py:30-34, find_embedding.py:58).  All arithmetic runs in
@@ -355,4 +356,37 @@ def iresnet100(pretrained=False, progress=True, freeze_weights=False, checkpoint
         m.load_state_dict(_load_checkpoint_file(checkpoint_path), strict=False)
     if freeze_weights and n_classes is not None:
         print("Freezing weights !")    # iresnet_encoder.py:174-179: only `logits` would train; nothing trains here
+    return m
+
+
+class _SEIResNet101(_Encoder):
+    _arch = _lib.VNF_ARCH_SEIR101
+    input_size = 112
+
+    def _spec(self):
+        from .weights import seir_spec
+        return seir_spec()
+
+
+def resnet101(use_se=False, pretrained=False, img_size=112, cp_path=None, compute_dtype="f16x2", max_batch=256, seed=0):
+    """Drop-in for models.resnet101 (resnet_encoder.py:246-254); kwargs of cfg/embedding/resnet101_se.json.  Only the
+    squeeze-and-excitation variant at 112 x 112 is built: the one every config of the reference names
+    (cfg/train_cfg_aug_emb_classify.json:80-88) and the only one with a published checkpoint.  (N,3,112,112) -> (N,512)
+    unit rows.  Without cp_path the weights are the deterministic generator's (the reference: torch's random init);
+    cp_path is a plain state_dict file, loaded strictly as the reference loads it -- a missing key raises.
+    compute_dtype / max_batch / seed are build extensions, as for the other encoders."""
+    if not use_se:
+        raise NotImplementedError("resnet101(use_se=False) is not built: only the SE-IR ResNet-101 (use_se=True), the variant "
+                                  "the reference's configs name and the only one with a published checkpoint")
+    if pretrained:
+        raise NotImplementedError("resnet101(pretrained=True) downloads torchvision's ImageNet ResNet-101, whose keys are not "
+                                  "this network's (resnet_encoder.py:248-249) and which cannot be fetched here: pass cp_path")
+    if img_size != 112:
+        raise NotImplementedError("resnet101(img_size=%r): only the 112 x 112 network (fc over 512 x 7 x 7) is built" % (img_size,))
+    m = _SEIResNet101(compute_dtype=compute_dtype, max_batch=max_batch)
+    m._sd = generate_state_dict("seir101", seed)
+    if cp_path:
+        if not os.path.exists(cp_path):
+            raise FileNotFoundError("resnet101: checkpoint %s not found" % cp_path)
+        m.load_state_dict(torch.load(cp_path, map_location="cpu", weights_only=True), strict=True)
     return m

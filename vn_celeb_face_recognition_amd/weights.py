@@ -10,6 +10,7 @@ travelling.  Key names follow:
                           36-181 (blocks), 219-258 (top level)
   * MLPModel           -- models/mlp_model.py:6-8 (dense_1, dense_2)
   * IResNet-100        -- models/iresnet_encoder.py:26-61 (IBasicBlock), 83-99, 117-137
+  * SE-IR ResNet-101   -- models/resnet_encoder.py:98-151 (SEBlock, IRBlock), 154-202
   * ResNet2Branch      -- models/resnet_2_branch.py:14-28 (conv1, bn1, layer1-4, fc, proj),
                           models/resnet_2_branch_utils/resnet.py:71-82 (Bottleneck)
   * MTCNN P/R/O-Net    -- models/mtcnn.py:19-28, 62-74, 112-128 (real weights ship as
@@ -26,7 +27,7 @@ from collections import OrderedDict
 import numpy as np
 
 __all__ = [
-    "irv1_spec", "mlp_spec", "iresnet_spec", "rn50_2b_spec", "mtcnn_spec", "retina_spec", "generate_state_dict",
+    "irv1_spec", "mlp_spec", "iresnet_spec", "seir_spec", "rn50_2b_spec", "mtcnn_spec", "retina_spec", "generate_state_dict",
     "IRV1_MACS_PER_IMAGE", "IR100_MACS_PER_IMAGE",
 ]
 
@@ -46,12 +47,13 @@ def _basic_conv(spec, prefix, cin, cout, k):
     _bn(spec, prefix + ".bn", cout)
 
 
-def _bn(spec, prefix, c, res=False):
+def _bn(spec, prefix, c, res=False, nbt=True):
     spec.append((prefix + ".weight", (c,), "bn_w_res" if res else "bn_w"))
     spec.append((prefix + ".bias", (c,), "bn_b"))
     spec.append((prefix + ".running_mean", (c,), "bn_m"))
     spec.append((prefix + ".running_var", (c,), "bn_v"))
-    spec.append((prefix + ".num_batches_tracked", (), "nbt"))
+    if nbt:
+        spec.append((prefix + ".num_batches_tracked", (), "nbt"))
 
 
 def _logits(spec, num_classes):
@@ -150,6 +152,42 @@ def iresnet_spec(layers=(3, 13, 30, 3), num_features=512, n_classes=None):
     _bn(s, "features", num_features)
     if n_classes is not None:
         _logits(s, n_classes)
+    return s
+
+
+def seir_spec(layers=(3, 4, 23, 3)):
+    """ResNet(IRBlock, layers, use_se=True, im_size=112) state_dict layout (resnet_encoder.py:116-202; default layers ==
+    resnet101), in the module's own order and without the BatchNorms' num_batches_tracked counters (a plain dict loads
+    strictly without them).  Every PReLU is nn.PReLU(): ONE slope, shape (1,).  bn2 of every block draws the small
+    residual gain so 33 blocks stay O(1); the SE layers draw wide (se_w) and se.fc.2.bias wider still (se_b), so the
+    gates are spread over (0,1) and differ from image to image."""
+    s = [("conv1.weight", (64, 3, 3, 3), "conv")]
+    _bn(s, "bn1", 64, nbt=False)
+    s.append(("prelu.weight", (1,), "prelu"))
+    inplanes = 64
+    for li, (planes, nblk) in enumerate(zip((64, 128, 256, 512), layers), start=1):
+        for b in range(nblk):
+            p = "layer%d.%d" % (li, b)
+            cin = inplanes if b == 0 else planes
+            _bn(s, p + ".bn0", cin, nbt=False)
+            s.append((p + ".conv1.weight", (cin, cin, 3, 3), "conv_lin"))
+            _bn(s, p + ".bn1", cin, nbt=False)
+            s.append((p + ".prelu.weight", (1,), "prelu"))
+            s.append((p + ".conv2.weight", (planes, cin, 3, 3), "conv_res"))
+            _bn(s, p + ".bn2", planes, res=True, nbt=False)
+            if b == 0 and li > 1:
+                s.append((p + ".downsample.0.weight", (planes, cin, 1, 1), "conv_lin"))
+                _bn(s, p + ".downsample.1", planes, nbt=False)
+            s.append((p + ".se.fc.0.weight", (planes // 16, planes), "se_w"))
+            s.append((p + ".se.fc.0.bias", (planes // 16,), "bias"))
+            s.append((p + ".se.fc.1.weight", (1,), "prelu"))
+            s.append((p + ".se.fc.2.weight", (planes, planes // 16), "se_w"))
+            s.append((p + ".se.fc.2.bias", (planes,), "se_b"))
+        inplanes = planes
+    _bn(s, "bn2", 512, nbt=False)
+    s.append(("fc.weight", (512, 512 * 49), "linear"))
+    s.append(("fc.bias", (512,), "bias"))
+    _bn(s, "bn3", 512, nbt=False)
     return s
 
 
@@ -299,6 +337,12 @@ def _draw(rng, shape, kind):
         a = rng.uniform(0.6, 1.4, shape)
     elif kind == "prelu":
         a = rng.uniform(0.1, 0.3, shape)
+    elif kind == "se_w":
+        # squeeze-and-excitation layers: the pooled vector they start from is a per-channel MEAN (a few tenths), so the
+        # weights are wide enough that the gate's logit moves by O(1) with the image
+        a = rng.standard_normal(shape) * (4.0 / np.sqrt(fan_in))
+    elif kind == "se_b":
+        a = rng.standard_normal(shape) * 1.5
     elif kind == "bn_v_pix":
         a = rng.uniform(3000.0, 7000.0, shape)
     elif kind == "cls_w":
@@ -316,6 +360,7 @@ _SPECS = {
     "irv1": irv1_spec,
     "mlp": mlp_spec,
     "iresnet100": iresnet_spec,
+    "seir101": seir_spec,
     "rn50_2b": rn50_2b_spec,
     "pnet": lambda: mtcnn_spec("pnet"),
     "rnet": lambda: mtcnn_spec("rnet"),
