@@ -32,6 +32,11 @@
  *                                    models/iresnet_encoder.py:100-103,155-157,174-179 (n_classes)
  *   vnf_logits_eval                  trainer/classification_trainer.py:42-80 (_validate_epoch: nll_loss, accuracy,
  *                                    argmax / exp for the result rows) + trainer/base_trainer.py:177-200 (eval)
+ *   vnf_encoder_features             what `logits` reads: models/inception_resnet_v1.py:296-298 (last_bn's output) and
+ *                                    models/iresnet_encoder.py:153 (features)
+ *   vnf_head_trainer_create / vnf_head_train_step
+ *                                    trainer/classification_trainer.py:9-40 (one optimisation step) for
+ *                                    models/iresnet_encoder.py:174-179 (freeze_weights: `logits` alone trains)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -141,6 +146,11 @@ int vnf_encoder_create_classifier(int arch, const vnf_tensor_desc* weights, int 
  * N > max_batch: VNF_E_CAPACITY; a handle without a head: VNF_E_INVALID; N == 0: no-op. */
 int vnf_encoder_logprobs(vnf_handle h, const void* x, int n, int x_dtype, float* logp_out, int32_t* amax_out,
                          float* prob_out, void* stream);
+/* The fp32 (N,512) rows the handle's `logits` layer reads (or would read: the handle need not have a head): last_bn's
+ * output before the L2 normalisation (InceptionResnetV1), `features` (IResNet-100).  x as for vnf_embed; feat_out: device
+ * (N,512) fp32, written on `stream` with no host synchronisation.  N > max_batch: VNF_E_CAPACITY; the emotion handle:
+ * VNF_E_INVALID; N == 0: no-op. */
+int vnf_encoder_features(vnf_handle h, const void* x, int n, int x_dtype, float* feat_out, void* stream);
 /* What a validation step does with a batch of logits (trainer/classification_trainer.py:42-80, losses/metrics.py:3-7):
  * logits device (n,c) fp32 with row stride ld >= c; target device (n) int64, may be NULL when nll, hit and sums are.
  * Outputs, all device, each may be NULL:
@@ -226,6 +236,26 @@ int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t* target, in
 int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
 int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
 int vnf_mlp_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
+
+/* training of a frozen encoder's `logits` layer ---------------------------- */
+/* One optimisation step of trainer/classification_trainer.py:13-21 for nn.Linear(512, num_classes) + log_softmax on
+ * precomputed features (vnf_encoder_features), torch.optim.Adam semantics (coupled weight decay, no amsgrad), fp32 end
+ * to end.  weights: logits.weight (num_classes,512) and logits.bias (num_classes) (initial values; other entries are
+ * ignored).  The handle owns the two parameters and their Adam moments; the gradient of the weight never exists in memory. */
+int vnf_head_trainer_create(const vnf_tensor_desc* weights, int n_weights, int num_classes, int max_batch,
+                            float beta1, float beta2, float eps, float weight_decay, vnf_handle* out);
+/* feat: device (b,512) fp32; target: device (b,) int64 (a label outside [0,num_classes) is never used as an index: the
+ * loss becomes NaN).  train != 0: forward, NLL loss, backward, Adam step with learning rate lr (four launches);
+ * train == 0: forward + loss only, parameters, moments and step count untouched.  loss_out: device fp32 scalar (mean
+ * NLL of the batch, rows summed in index order); hits_out: device int32 scalar (first argmax == target count).
+ * Bitwise repeatable.  b > max_batch: VNF_E_CAPACITY.  Enqueued on `stream`, no synchronisation. */
+int vnf_head_train_step(vnf_handle h, const float* feat, const int64_t* target, int b, float lr, int train,
+                        float* loss_out, int32_t* hits_out, void* stream);
+/* checkpoint access, as vnf_mlp_trainer_*: name = logits.weight | logits.bias, kind 0 = parameter, 1 = Adam exp_avg,
+ * 2 = Adam exp_avg_sq; host fp32 arrays of exactly numel elements.  Synchronise. */
+int vnf_head_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
+int vnf_head_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
+int vnf_head_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
 
 /* training-time augmentation --------------------------------------------- */
 /* transforms_facenet_aug (data_loader/__init__.py:58-65) for the images VNCelebDataset serves

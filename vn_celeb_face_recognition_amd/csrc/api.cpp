@@ -164,6 +164,29 @@ int vnf_embed(vnf_handle h, const void* x, int n, int x_dtype, float* emb_out, v
   API_GUARD_END
 }
 
+int vnf_encoder_features(vnf_handle h, const void* x, int n, int x_dtype, float* feat_out, void* stream) {
+  API_GUARD_BEGIN
+  Encoder* e = handle_cast<Encoder>(h);
+  if (!e) return fail(VNF_E_INVALID, "not an encoder handle");
+  if (e->arch == VNF_ARCH_RN50_2B) return fail(VNF_E_INVALID, "emotion handle: use vnf_emotion_forward");
+  if (n < 0 || (n > 0 && (!x || !feat_out))) return fail(VNF_E_INVALID, "bad argument");
+  if (x_dtype != VNF_F32 && x_dtype != VNF_BF16 && x_dtype != VNF_F16) return fail(VNF_E_INVALID, "bad x_dtype");
+  if (n > e->max_batch) return fail(VNF_E_CAPACITY, "batch exceeds max_batch");
+  if (n == 0) return VNF_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // the plan's last op writes the embeddings to feat_out; where those are not the features themselves (a normalising
+  // plan), emb_raw of the activation context this run used then replaces them
+  const int r = e->run(x, n, x_dtype, feat_out, s);
+  if (r != VNF_OK || e->arch == VNF_ARCH_IR100) return r;
+  VNF_HIP(hipMemcpyAsync(feat_out, e->emb_raw, (size_t)n * 512 * 4, hipMemcpyDeviceToDevice, s));
+  if (e->n_ctx > 1) {   // the context is free again only after this copy
+    const int c = (e->next_ctx + e->n_ctx - 1) % e->n_ctx;
+    VNF_HIP(hipEventRecord(e->ctx_ev[c], s));
+  }
+  return VNF_OK;
+  API_GUARD_END
+}
+
 int vnf_encoder_tap(vnf_handle h, const char* name, int n, float* host_out, int64_t capacity, int64_t shape_out[4]) {
   API_GUARD_BEGIN
   Encoder* e = handle_cast<Encoder>(h);

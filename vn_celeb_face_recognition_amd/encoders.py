@@ -10,6 +10,8 @@ hand-written HIP kernels; torch only owns the input/output device memory and the
 With their own `logits` head (InceptionResnetV1(classify=True, ...), iresnet100(n_classes=...):
 inception_resnet_v1.py:260-265,298-300, iresnet_encoder.py:100-103,155-157) the models return (N,C)
 log-probabilities, `.logprobs(x)` adds argmax and probability, `.embed(x)` still gives the embeddings.
+`.features(x)` gives the (N,512) rows the head reads, head or no head; with freeze_weights that head is what
+trainer.TrainableHead trains (the backbone stays as it is: nothing here runs backward through an encoder).
 There is no CPU path: calling a model that is not on a CUDA(ROCm) device raises.
 """
 import ctypes
@@ -43,8 +45,9 @@ def _load_checkpoint_file(path):
 class _Encoder:
     """nn.Module-shaped wrapper around a vnf encoder handle."""
     _arch = None
-    _arch_name = None
+    arch_name = None    # type(model).__name__ of the reference's module: what a checkpoint's "arch" holds
     input_size = None
+    freeze_weights = False   # only `logits` may train (trainer.TrainableHead)
     _out_dim = 512      # columns of the tensor vnf_encoder_profile writes
 
     def __init__(self, device=None, compute_dtype="f16x2", max_batch=256):
@@ -194,6 +197,21 @@ class _Encoder:
                                          ctypes.c_void_p(out[n0:].data_ptr()), _lib.current_stream_ptr()))
         return out
 
+    def features(self, x):
+        """(N,3,S,S) cuda -> (N,512) fp32 cuda: the rows the `logits` layer reads (vnf_encoder_features) -- last_bn's
+        output before the normalisation (InceptionResnetV1), `features` (IResNet-100); head or no head."""
+        h = self._ensure_handle()
+        x = self._checked_input(x)
+        n = x.shape[0]
+        out = torch.empty((n, 512), dtype=torch.float32, device=x.device)
+        lib = _lib.load()
+        with torch.cuda.device(x.device):
+            for n0 in range(0, n, self.max_batch):
+                nn = min(self.max_batch, n - n0)
+                _lib.check(lib.vnf_encoder_features(h, ctypes.c_void_p(x[n0:n0 + nn].data_ptr()), nn, _lib.torch_dtype_code(x.dtype),
+                                                    ctypes.c_void_p(out[n0:].data_ptr()), _lib.current_stream_ptr()))
+        return out
+
     def set_streams(self, max_streams):
         """Cap the encoder's internal batch split (vnf_encoder_set_streams): 1 when other work shares the GPU."""
         _lib.check(_lib.load().vnf_encoder_set_streams(self._ensure_handle(), int(max_streams)))
@@ -282,19 +300,24 @@ class InceptionResnetV1(_Encoder):
     classify=True: the model ends in its `logits` layer and returns log-probabilities.  With num_classes the head is a
     fresh generator-seeded (num_classes, 512) layer (the reference: torch's random init) until load_state_dict brings a
     trained one; without it the head is the pretrained file's own.  The head runs in exact fp32 in every compute_dtype.
+
+    freeze_weights (build extension; the reference has no such flag and would fine-tune every layer): with classify, only
+    `logits` may train -- the model train.py accepts for head training (trainer.TrainableHead).
     """
     _arch = _lib.VNF_ARCH_IRV1
+    arch_name = "InceptionResnetV1"
     input_size = 160
     _FILES = {"vggface2": "20180402-114759-vggface2.pt", "casia-webface": "20180408-102900-casia-webface.pt"}
 
     def __init__(self, pretrained=None, classify=False, num_classes=None, dropout_prob=0.6, device=None,
-                 compute_dtype="f16x2", max_batch=256, seed=0):
+                 compute_dtype="f16x2", max_batch=256, seed=0, freeze_weights=False):
         if pretrained is None and classify and num_classes is None:
             # inception_resnet_v1.py:214-215
             raise Exception('If "pretrained" is not specified and "classify" is True, "num_classes" must be specified')
         self.pretrained = pretrained
         self.classify = classify
         self.num_classes = num_classes
+        self.freeze_weights = bool(freeze_weights and classify)
         super().__init__(device=None, compute_dtype=compute_dtype, max_batch=max_batch)
         if pretrained is None:
             self._sd = generate_state_dict("irv1", seed)
@@ -330,6 +353,7 @@ class InceptionResnetV1(_Encoder):
 
 class _IResNet100(_Encoder):
     _arch = _lib.VNF_ARCH_IR100
+    arch_name = "IResNet"
     input_size = 112
 
     def _spec(self):
@@ -342,7 +366,8 @@ def iresnet100(pretrained=False, progress=True, freeze_weights=False, checkpoint
     """Drop-in for models.iresnet100 (iresnet_encoder.py:162-181,194-196); kwargs of
     cfg/embedding/iresnet100_enc.json.  pretrained=True needs checkpoint_path (a file holding
     {'state_dict': ...}); the URL branch of the reference cannot run offline.  n_classes (iresnet_encoder.py:100-103):
-    the model gets a `logits` layer (generator weights until a checkpoint brings its own) and returns log-probabilities."""
+    the model gets a `logits` layer (generator weights until a checkpoint brings its own) and returns log-probabilities.
+    freeze_weights with n_classes (iresnet_encoder.py:174-179): only `logits` may train, which trainer.TrainableHead does."""
     if kwargs:
         raise TypeError("unexpected keyword arguments: %s" % sorted(kwargs))
     m = _IResNet100(compute_dtype=compute_dtype, max_batch=max_batch)
@@ -355,7 +380,8 @@ def iresnet100(pretrained=False, progress=True, freeze_weights=False, checkpoint
         print("Loaded encoder state dict from checkpoint path {}".format(checkpoint_path))
         m.load_state_dict(_load_checkpoint_file(checkpoint_path), strict=False)
     if freeze_weights and n_classes is not None:
-        print("Freezing weights !")    # iresnet_encoder.py:174-179: only `logits` would train; nothing trains here
+        print("Freezing weights !")    # iresnet_encoder.py:174-179: only `logits` trains (trainer.TrainableHead)
+        m.freeze_weights = True
     return m
 
 

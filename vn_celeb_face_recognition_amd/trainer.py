@@ -10,6 +10,11 @@ the optimisation step itself in libvnface.so (csrc/mlp_train.hip):
   AugClassificationTrainer <- /root/reference/trainer/online_aug_trainer.py:6-97 (images -> augmentation -> frozen
                              encoder -> MLP step, all on the device: augment.py, csrc/augment.hip)
 
+  TrainableHead           <- models/iresnet_encoder.py:174-179 (freeze_weights: `logits` alone trains)
+                             under trainer/classification_trainer.py:9-40 on a VNCelebDataset
+                             (cfg/train_cfg_img_classify.json): images -> augmentation -> frozen encoder's features ->
+                             fused grad + Adam step of the head (csrc/head_train.hip)
+
   EvalModel, write_result_csv, ClassificationTrainer.eval
                           <- /root/reference/trainer/base_trainer.py:177-200, classification_trainer.py:42-80 (evaluation of
                              a trained model: MLPModel or an encoder with its own head; csrc/head_eval.hip)
@@ -33,6 +38,8 @@ import torch
 from . import _lib
 
 PARAMS = ("dense_1.weight", "dense_1.bias", "dense_2.weight", "dense_2.bias")
+HEAD_PARAMS = ("logits.weight", "logits.bias")
+_X_DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}   # 16-bit storage paths take 16-bit images
 
 
 class VNCelebEmbDataset(torch.utils.data.Dataset):
@@ -227,6 +234,148 @@ class TrainableMLP:
             self._step_count(int(float(osd["state"][0]["step"])))
 
 
+def _check_labels(target, num_classes):
+    """torch's nll_loss raises on a label outside [0, C) (trainer/classification_trainer.py:22 F.nll_loss): so does this,
+    before any launch.  Returns the labels as an int64 host tensor."""
+    th = torch.as_tensor(target).to(dtype=torch.int64)
+    if th.numel() and (int(th.min()) < 0 or int(th.max()) >= num_classes):
+        raise IndexError("Target %d is out of bounds." % int(th.max() if int(th.max()) >= num_classes else th.min()))
+    return th
+
+
+def head_param_layout(spec):
+    """(P, index of logits.weight, index of logits.bias) in `Adam(model.parameters())` of the reference module whose
+    state_dict `spec` (weights.py) lists: parameters() follows the state_dict's order without the BatchNorms' running
+    statistics and step counters, and freeze_weights (iresnet_encoder.py:174-179) leaves every parameter in the group."""
+    params = [name for name, _, kind in spec if kind not in ("bn_m", "bn_v", "nbt")]
+    return len(params), params.index(HEAD_PARAMS[0]), params.index(HEAD_PARAMS[1])
+
+
+class TrainableHead:
+    """The `logits` layer of a frozen encoder + its Adam state, resident on the GPU (vnf_head_trainer_*): the
+    counterpart of TrainableMLP for iresnet100(n_classes=..., freeze_weights=True) / InceptionResnetV1(classify=True,
+    freeze_weights=True).  The encoder only ever runs forward, in eval mode; the initial head is the encoder's own."""
+
+    def __init__(self, encoder, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_batch=1024):
+        if encoder.head_classes is None:
+            raise RuntimeError("%s was built without a classification head (classify=True / n_classes)" % type(encoder).__name__)
+        self.encoder, self.num_classes, self.max_batch = encoder, int(encoder.head_classes), int(max_batch)
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
+        self.device = torch.device(encoder.device)
+        if self.device.type != "cuda":
+            raise RuntimeError("training runs on MI355X only (there is no CPU path)")
+        self.encoder.eval()
+        self.arch_name = encoder.arch_name
+        self.input_size = encoder.input_size
+        self.x_dtype = _X_DTYPES.get(encoder.compute_dtype, torch.float32)
+        self.n_params, self._iw, self._ib = head_param_layout(encoder._spec())
+        self._shapes = {HEAD_PARAMS[0]: (self.num_classes, 512), HEAD_PARAMS[1]: (self.num_classes,)}
+        self.training = True
+        esd = encoder.state_dict()
+        lib = _lib.load()
+        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(dev):
+            _lib.check(lib.vnf_init(dev))
+            descs, n, keep = _lib.make_descs(OrderedDict((k, esd[k]) for k in HEAD_PARAMS))
+            h = ctypes.c_void_p()
+            _lib.check(lib.vnf_head_trainer_create(descs, n, self.num_classes, self.max_batch, self.betas[0], self.betas[1],
+                                                   self.eps, self.weight_decay, ctypes.byref(h)))
+            del keep
+        self._h = h
+        self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                _lib.load().vnf_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def train(self, mode=True):
+        """The head's mode.  The backbone stays in eval mode whatever this says: frozen means frozen."""
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def to(self, device):
+        return self
+
+    def features(self, x):
+        """(N,3,S,S) cuda -> (N,512) fp32 cuda: what the head reads (encoders._Encoder.features)."""
+        return self.encoder.features(x)
+
+    def step(self, features, target, train):
+        """One batch of features (b,512): forward + loss (+ the fused gradient / Adam launch when train).  Returns
+        (mean NLL, correct count)."""
+        b = int(features.shape[0])
+        if features.dim() != 2 or features.shape[1] != 512:
+            raise ValueError("expected (b,512) features, got %s" % (tuple(features.shape),))
+        th = _check_labels(target, self.num_classes)
+        if th.numel() != b:
+            raise ValueError("%d targets for a batch of %d" % (th.numel(), b))
+        x = features.to(self.device, dtype=torch.float32).contiguous()
+        t = th.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().vnf_head_train_step(
+                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()), b, self.lr, 1 if train else 0,
+                ctypes.c_void_p(self._loss.data_ptr()), ctypes.c_void_p(self._hits.data_ptr()), _lib.current_stream_ptr()))
+        return float(self._loss.item()), int(self._hits.item())
+
+    # ---- checkpoint access
+    def _get(self, name, kind):
+        a = np.empty(self._shapes[name], dtype=np.float32)
+        _lib.check(_lib.load().vnf_head_trainer_get(self._h, name.encode(), kind, a.ctypes.data, a.size))
+        return torch.from_numpy(a)
+
+    def _set(self, name, kind, value):
+        a = np.ascontiguousarray(torch.as_tensor(value).detach().cpu().float().numpy())
+        if a.shape != self._shapes[name]:
+            raise RuntimeError("size mismatch for %s: %s vs %s" % (name, a.shape, self._shapes[name]))
+        _lib.check(_lib.load().vnf_head_trainer_set(self._h, name.encode(), kind, a.ctypes.data, a.size))
+
+    def state_dict(self):
+        """The encoder's full state_dict with `logits.*` replaced by the trained values."""
+        sd = self.encoder.state_dict()
+        for k in HEAD_PARAMS:
+            sd[k] = self._get(k, 0)
+        return sd
+
+    def load_state_dict(self, sd):
+        """The backbone goes into the encoder (strictly, as nn.Module.load_state_dict), `logits.*` into the trainer."""
+        self.encoder.load_state_dict(sd)
+        for k in HEAD_PARAMS:
+            self._set(k, 0, sd[k])
+
+    def _step_count(self, value=None):
+        c = ctypes.c_int64(0 if value is None else int(value))
+        _lib.check(_lib.load().vnf_head_trainer_step_count(self._h, ctypes.byref(c), 0 if value is None else 1))
+        return int(c.value)
+
+    def optimizer_state_dict(self):
+        """state_dict() of the reference's Adam(model.parameters()) after freeze_weights: every parameter of the module
+        is in the group, only the two of `logits` ever got a gradient and therefore a state entry."""
+        step = float(self._step_count())
+        state = {i: {"step": torch.tensor(step), "exp_avg": self._get(k, 1), "exp_avg_sq": self._get(k, 2)}
+                 for i, k in zip((self._iw, self._ib), HEAD_PARAMS)} if step > 0 else {}
+        group = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps,
+                                 weight_decay=self.weight_decay).state_dict()["param_groups"][0]
+        group["params"] = list(range(self.n_params))
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, osd):
+        g = osd["param_groups"][0]
+        self.lr = float(g["lr"])
+        if osd["state"]:
+            for i, k in zip((self._iw, self._ib), HEAD_PARAMS):
+                self._set(k, 1, osd["state"][i]["exp_avg"])
+                self._set(k, 2, osd["state"][i]["exp_avg_sq"])
+            self._step_count(int(float(osd["state"][self._iw]["step"])))
+
+
 class EvalModel:
     """A trained model under evaluation (eval.py): an inference MLPModel (classifier.py) or an encoder with its own
     `logits` head (encoders.py), anything that maps a cuda batch to cuda (n,C) log-probabilities.  evaluate() is the
@@ -242,8 +391,7 @@ class EvalModel:
         self.model.eval()
         self.training = False
         self.input_size = getattr(model, "input_size", None)   # encoders: side of the images they take
-        cd = getattr(model, "compute_dtype", None)
-        self.x_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}.get(cd, torch.float32)
+        self.x_dtype = _X_DTYPES.get(getattr(model, "compute_dtype", None), torch.float32)
 
     def eval(self):
         return self
@@ -366,29 +514,54 @@ class ClassificationTrainer:
         self.logger = logging.getLogger("trainer")
         self.do_val, self.val_step = tc["do_validation"], tc["validation_step"]
         self.mnt_best = float("inf") if self.mode_monitor == "min" else -float("inf")
+        self._kept = {}    # TrainableHead: features of a whole data set under the default transform, by `train`
         if tc["resume_path"] != "":
             self.resume_checkpoint(tc["resume_path"])
 
     def setup_loader(self, train_loader, val_loader):
         self.train_loader, self.val_loader = train_loader, val_loader
 
+    def _images(self, ds, data, transform):
+        """Rows `data` of the resident image set through `transform`, as the model's input tensor."""
+        from . import augment
+        index = torch.as_tensor(data, dtype=torch.int64)
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
+            raise IndexError("sample index outside the data set")
+        t = getattr(self.model, "input_size", None)
+        if t is None:
+            raise NotImplementedError("VNCelebDataset under ClassificationTrainer needs a model that takes images")
+        if ds.size != t:
+            raise ValueError("the images are %dx%d but the model takes %dx%d: transforms.resize is not built (DESIGN.md 8)"
+                             % (ds.size, ds.size, t, t))
+        params = augment.get_transform(transform).params(int(index.numel()), ds.size, t)
+        return augment.augment_faces_device(ds.faces_device(self.model.device), index, params, t, dtype=self.model.x_dtype)
+
+    def _head_features(self, ds, data, train):
+        """A TrainableHead's input: the frozen encoder's features of rows `data`.  The default transform draws nothing and
+        the backbone never changes, so under it the features of the whole set are computed once and kept: always for
+        validation (train.py:30-34), for training when transforms.name is default."""
+        tf = self.config.get("transforms")
+        name = (tf.get("name") if isinstance(tf, dict) else tf) if train else "default"
+        if name != "default":
+            return self.model.features(self._images(ds, data, name))
+        if train not in self._kept:
+            bs = self.model.encoder.max_batch
+            self._kept[train] = torch.cat([self.model.features(self._images(ds, torch.arange(i, min(i + bs, len(ds))), "default"))
+                                           for i in range(0, len(ds), bs)]) if len(ds) else torch.zeros((0, 512), device=self.model.device)
+        index = torch.as_tensor(data, dtype=torch.int64)
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
+            raise IndexError("sample index outside the data set")
+        return self._kept[train][index.to(self._kept[train].device)]
+
     def _batch_input(self, data, train):
-        """What the loader yields -> what the model takes: the embeddings themselves; for a VNCelebDataset under
-        evaluation (rows of the resident image set) the images through the default transform (eval.py:24-40)."""
+        """What the loader yields -> what the model takes: the embeddings themselves; for a VNCelebDataset (rows of the
+        resident image set) the frozen encoder's features when the model is a TrainableHead in the training loop, and
+        under evaluation the images through the default transform (eval.py:24-40)."""
         ds = (self.train_loader if train else self.val_loader).dataset
+        if isinstance(ds, VNCelebDataset) and isinstance(self.model, TrainableHead):
+            return self._head_features(ds, data, train)
         if isinstance(ds, VNCelebDataset) and not train:
-            from . import augment
-            index = torch.as_tensor(data, dtype=torch.int64)
-            if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
-                raise IndexError("sample index outside the data set")
-            t = getattr(self.model, "input_size", None)
-            if t is None:
-                raise NotImplementedError("VNCelebDataset under ClassificationTrainer needs a model that takes images")
-            if ds.size != t:
-                raise ValueError("the images are %dx%d but the model takes %dx%d: transforms.resize is not built (DESIGN.md 8)"
-                                 % (ds.size, ds.size, t, t))
-            params = augment.get_transform("default").params(int(index.numel()), ds.size, t)
-            return augment.augment_faces_device(ds.faces_device(self.model.device), index, params, t, dtype=self.model.x_dtype)
+            return self._images(ds, data, "default")
         return data
 
     def resume_checkpoint(self, checkpoint_path):
@@ -401,7 +574,7 @@ class ClassificationTrainer:
         self.logger.info("Checkpoint loaded. Resume training from epoch {}".format(self.start_epoch))
 
     def save_checkpoint(self, epoch, save_best):
-        state = {"arch": "MLPModel", "epoch": epoch, "state_dict": self.model.state_dict(),
+        state = {"arch": getattr(self.model, "arch_name", "MLPModel"), "epoch": epoch, "state_dict": self.model.state_dict(),
                  "optimizer": self.model.optimizer_state_dict(), "monitor_best": self.mnt_best, "config": self.config}
         filename = str(self.save_dir / "checkpoint-epoch{}.pth".format(epoch))
         torch.save(state, filename)
@@ -433,12 +606,16 @@ class ClassificationTrainer:
 
     def _evaluator(self, save_result):
         """Who scores a validation batch: the model itself when it is an EvalModel; None for the training model inside
-        the training loop (its own forward + loss, TrainableMLP.step); and, when the rows are wanted from a training
-        model, an inference MLPModel of its current weights."""
+        the training loop (its own forward + loss, TrainableMLP.step / TrainableHead.step); and, when the rows are wanted
+        from a training model, an inference model of its current weights: an MLPModel, or the encoder with the current head."""
         if hasattr(self.model, "evaluate"):
             return self.model
         if not save_result:
             return None
+        if isinstance(self.model, TrainableHead):
+            enc = self.model.encoder
+            enc.load_state_dict(self.model.state_dict())
+            return EvalModel(enc, self.model.num_classes, device=self.model.device)
         from .classifier import MLPModel
         mlp = MLPModel(self.model.input_dim, self.model.num_classes, max_batch=self.model.max_batch)
         mlp.load_state_dict(self.model.state_dict())
@@ -453,8 +630,9 @@ class ClassificationTrainer:
         self.logger.info("Validation: ")
         evaluator = self._evaluator(save_result)
         result = []
+        head_rows = evaluator is not None and isinstance(self.model, TrainableHead)   # the encoder itself scores: it takes images
         for batch_idx, (data, target, id_img) in enumerate(self.val_loader):
-            data = self._batch_input(data, train=False)
+            data = self._images(self.val_loader.dataset, data, "default") if head_rows else self._batch_input(data, train=False)
             n = data.size(0)
             if evaluator is None:
                 loss, hits = self.model.step(data, target, train=False)
