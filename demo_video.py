@@ -10,7 +10,9 @@ and rank 0 classifies the gathered tensor and writes the tracker rows in frame o
 Annotated frames are written only with -sfr (the reference's test at l.149 is always true and
 PNG-encodes every frame).  Input: a directory of frames, a .npy array of
 (T,H,W,3) RGB frames, a Motion-JPEG .avi, or any video file when OpenCV is installed; -ov exports the annotated frames
-as a video (MP4V with OpenCV, Motion-JPEG .avi without)."""
+as a video (MP4V with OpenCV, Motion-JPEG .avi without).  JPEG frames (a Motion-JPEG .avi, .jpg files) are decoded on the
+GPU (jpeg.py: Huffman decode on host threads, IDCT / upsampling / colour in HIP), bit-exact to the host decoder;
+--host_decode keeps them on Pillow."""
 import os
 import time
 
@@ -48,7 +50,8 @@ def main(args, pipe, rank, world, source=None, device=None):
             print('Processing for frame: {}, time: {}'.format(inf[-1][1], convert_sec_to_max_time_quantity(inf[-1][0])))
 
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
-                                 on_frame=on_frame if args.save_frame_recognized else None, log=log)
+                                 on_frame=on_frame if args.save_frame_recognized else None, log=log,
+                                 decode="host" if getattr(args, "host_decode", False) else "device")
     if world > 1:
         tot = torch.tensor([processed], device=device if device is not None else 'cuda')
         dist.all_reduce(tot)
@@ -71,6 +74,8 @@ if __name__ == '__main__':
     p.add_argument('-sfr', '--save_frame_recognized', action='store_true')
     p.add_argument('--log_step', default=100, type=int)
     p.add_argument('--n_frames', default=16, type=int)
+    p.add_argument('--host_decode', action='store_true',
+                   help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
     args = p.parse_args()
     if args.inference_method != 'par_fd_vs_aln':
         raise SystemExit("use --inference_method par_fd_vs_aln (seq_fd_vs_aln needs the FAN landmark network, outside "

@@ -37,6 +37,9 @@
  *   vnf_head_trainer_create / vnf_head_train_step
  *                                    trainer/classification_trainer.py:9-40 (one optimisation step) for
  *                                    models/iresnet_encoder.py:174-179 (freeze_weights: `logits` alone trains)
+ *   vnf_jpeg_probe / vnf_jpeg_entropy_decode / vnf_jpeg_decode_frames
+ *                                    cv2.VideoCapture.read as demo_video.py:78-110 calls it (a frame of a
+ *                                    Motion-JPEG stream: bitstream walk on the host, pixels on the device)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -407,6 +410,61 @@ int vnf_extract_faces(const uint8_t* frames, int b, int height, int width,
                       const int32_t* rects /* device (n,5): frame, x1, y1, x2, y2 */, int n, int s,
                       int standardize, void* x_out /* (n,3,s,s) */, int out_dtype /* VNF_F32|VNF_BF16|VNF_F16 */,
                       uint8_t* u8_out /* (n,s,s,3) */, void* stream);
+
+/* JPEG video frames ------------------------------------------------------------------------ */
+/* The reference reads its frames with cv2.VideoCapture.read (demo_video.py:78-110): a host decoder, one frame at a
+ * time.  Here a baseline JPEG frame (a Motion-JPEG AVI chunk, a .jpg file) is split: the serial bitstream walk stays
+ * on the host (vnf_jpeg_probe, vnf_jpeg_entropy_decode: plain C++, no HIP call, usable without a GPU, thread-safe,
+ * one frame per call), everything after it -- dequantisation, 8x8 IDCT, chroma upsampling, YCbCr -> RGB -- runs on the
+ * device (vnf_jpeg_decode_frames).  The arithmetic is libjpeg's public baseline path (islow IDCT, "fancy" triangle
+ * upsampling, 16-bit fixed-point colour), all integer, so the bytes are those libjpeg / libjpeg-turbo produce. */
+#define VNF_JPEG_NOT_TAKEN 1 /* the one positive status: a valid JPEG this decoder leaves to the host decoder */
+
+/* sampling codes of a frame (luma factors; chroma is 1x1) */
+#define VNF_JPEG_GRAY 0 /* one component */
+#define VNF_JPEG_444 1  /* 1x1 */
+#define VNF_JPEG_422 2  /* 2x1 */
+#define VNF_JPEG_420 3  /* 2x2 */
+
+typedef struct {
+  int32_t width, height;
+  int32_t components;       /* 1 or 3 */
+  int32_t sampling;         /* VNF_JPEG_* */
+  int32_t h[3], v[3];       /* sampling factors per component (1x1 for a single component) */
+  int32_t restart_interval; /* MCUs between RSTn markers, 0: none */
+  int32_t blocks_w[3], blocks_h[3]; /* 8x8 blocks per row / column of each component plane, MCU-padded */
+  uint8_t quant[3][64];     /* the component's 8-bit quantisation table in natural (row-major) order */
+  int64_t coef_count;       /* int16 coefficients of a frame: 64 * sum(blocks_w * blocks_h) */
+} vnf_jpeg_info;
+
+/* Walks the markers of data[0, len) up to the first scan (SOI; APPn / COM skipped; DQT, SOF0, DHT, DRI, SOS) and fills
+ * *info.  VNF_OK: vnf_jpeg_entropy_decode takes this frame.  VNF_E_INVALID: not a JPEG / corrupt or truncated header.
+ * VNF_JPEG_NOT_TAKEN: a JPEG outside this decoder -- any SOF but baseline SOF0, 12-bit samples, arithmetic coding,
+ * 2 or 4 components, three components that are RGB (Adobe APP14 transform 0, ids 'R','G','B'), no DHT in the frame
+ * (the abbreviated frames some cameras write), 16-bit quantisation tables, a scan that does not hold every component
+ * (more than one scan), sampling other than 1x1 / 2x1 / 2x2 luma over 1x1 chroma. */
+int vnf_jpeg_probe(const uint8_t* data, int64_t len, vnf_jpeg_info* info);
+/* Huffman-decodes the one scan of a frame vnf_jpeg_probe accepted (info: what it filled, for the same bytes) into
+ * coefs[0, info->coef_count): QUANTISED coefficients in natural order, 64 per block, the blocks of a component plane in
+ * raster order (blocks_w per row), the planes one after another.  FF 00 stuffing, DC prediction and restart markers
+ * (predictors reset, RSTn sequence checked) are undone here.  Every read is checked against len, every write against
+ * capacity (in coefficients): VNF_E_CAPACITY when capacity < coef_count, VNF_E_INVALID for a truncated or
+ * inconsistent stream or an info that does not belong to these bytes -- never a partial success (coefs then holds
+ * unspecified values inside [0, capacity)).  A missing EOI after the last MCU is accepted. */
+int vnf_jpeg_entropy_decode(const uint8_t* data, int64_t len, const vnf_jpeg_info* info, int16_t* coefs,
+                            int64_t capacity);
+/* bytes of device workspace vnf_jpeg_decode_frames needs for n frames of this geometry (the component planes between
+ * its two launches), or a negative VNF_E_* code */
+int64_t vnf_jpeg_workspace_bytes(int n, int width, int height, int sampling);
+/* n frames of ONE geometry (width, height, sampling code), each with its own tables:
+ *   coefs_dev: device (n, coef_count) int16 as vnf_jpeg_entropy_decode writes them; quant_dev: device (n,3,64) u8
+ *   (vnf_jpeg_info.quant; rows 1..2 unused for VNF_JPEG_GRAY); frames_out: device (n,height,width,3) u8 RGB
+ *   (R = G = B for VNF_JPEG_GRAY); workspace: device, 16-byte aligned.
+ * Two launches (planes, then upsample + colour), nothing allocated, no synchronisation.  n == 0: no-op.
+ * VNF_E_INVALID: n < 0, a NULL or misaligned pointer, width or height outside 1..65535, an unknown sampling code;
+ * VNF_E_CAPACITY: workspace_bytes below vnf_jpeg_workspace_bytes(...). */
+int vnf_jpeg_decode_frames(const int16_t* coefs_dev, const uint8_t* quant_dev, int n, int width, int height,
+                           int sampling, uint8_t* frames_out, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,13 @@ class RetinaCfg(ctypes.Structure):
                 ("keep_top_k", ctypes.c_int32), ("vis_thres", ctypes.c_float), ("compute_dtype", ctypes.c_int32)]
 
 
+class JpegInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("h", ctypes.c_int32 * 3), ("v", ctypes.c_int32 * 3),
+                ("restart_interval", ctypes.c_int32), ("blocks_w", ctypes.c_int32 * 3), ("blocks_h", ctypes.c_int32 * 3),
+                ("quant", (ctypes.c_uint8 * 64) * 3), ("coef_count", ctypes.c_int64)]
+
+
 _lib = None
 
 # every symbol include/vnface.h declares, with its ctypes signature
@@ -89,6 +96,10 @@ SIGNATURES = {
     "vnf_retina_debug_heads": (_I, [_P, _I, _I, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
     "vnf_align": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "vnf_extract_faces": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "vnf_jpeg_probe": (_I, [_P, ctypes.c_int64, ctypes.POINTER(JpegInfo)]),
+    "vnf_jpeg_entropy_decode": (_I, [_P, ctypes.c_int64, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64]),
+    "vnf_jpeg_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
+    "vnf_jpeg_decode_frames": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, ctypes.c_int64, _P]),
 }
 
 

@@ -144,7 +144,14 @@ def open_frame_source(path):
     from .video import FrameSource
     if os.path.isdir(path):
         files = sorted(f for f in os.listdir(path) if f.lower().endswith(('.png', '.jpg', '.jpeg', '.bmp')))
-        return FrameSource([os.path.join(path, f) for f in files], 25.0, load=read_rgb)
+        paths = [os.path.join(path, f) for f in files]
+
+        def jpeg_bytes(i):
+            if not paths[i].lower().endswith(('.jpg', '.jpeg')):
+                return None
+            with open(paths[i], 'rb') as f:
+                return f.read()
+        return FrameSource(paths, 25.0, load=read_rgb, compressed=jpeg_bytes)
     if path.endswith('.npy'):
         return FrameSource(np.load(path, mmap_mode='r'), 30.0)
     if path.endswith('.npz'):
@@ -160,7 +167,7 @@ def open_frame_source(path):
         except (ValueError, OSError) as e:
             raise RuntimeError("decoding %r needs OpenCV, which is not installed (%s): pass a Motion-JPEG .avi, a directory "
                                "of frames or a .npy array of (T,H,W,3) uint8 RGB frames instead" % (path, e))
-        return FrameSource(frames, fps)
+        return FrameSource(frames, fps, compressed=frames.compressed)
     cap = cv2.VideoCapture(path)
     fps = cap.get(cv2.CAP_PROP_FPS) or 25.0
 

@@ -121,10 +121,14 @@ class MjpegFrames:
     def __len__(self):
         return len(self._spans)
 
+    def compressed(self, i):
+        """the JPEG bytes of frame i, not decoded (jpeg.decode_batch_device takes them)"""
+        ps, sz = self._spans[i]
+        return bytes(self._data[ps:ps + sz])
+
     def __getitem__(self, i):
         from PIL import Image
-        ps, sz = self._spans[i]
-        return np.asarray(Image.open(io.BytesIO(bytes(self._data[ps:ps + sz]))).convert("RGB"))
+        return np.asarray(Image.open(io.BytesIO(self.compressed(i))).convert("RGB"))
 
     def __iter__(self):
         return (self[i] for i in range(len(self)))

@@ -37,6 +37,7 @@ class FrameUploader:
         self._dev_state = [None] * self.depth  # None: free | "out": handed out, not released | event: released behind it
         self._dnext = 0
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(threads))) if threads > 1 else None
+        self._scratch = None                   # device bytes used on the copy stream only (jpeg.decode_batch_device)
         self.bytes = 0                         # uploaded so far (bench / tests)
         self.last_slot = -1                    # device slot of the last upload (for release())
 
@@ -72,6 +73,26 @@ class FrameUploader:
                 buf = self._dev[k] = torch.empty((n,), dtype=torch.uint8, device=self.device)
         self._dev_state[k] = "out"
         return buf[:n].view(shape), k
+
+    def take_device_slot(self, shape):
+        """A (B,H,W,3) u8 buffer of the device ring for a producer that fills it ON THE COPY STREAM itself (a decoder
+        whose kernels run there): -> (tensor, slot), handed back with `release(slot, event)` like an upload's."""
+        dev, slot = self._device_slot(tuple(int(s) for s in shape))
+        self.last_slot = slot
+        return dev, slot
+
+    def scratch(self, nbytes):
+        """At least `nbytes` of device memory that lives between a copy and the kernels behind it on the copy stream:
+        one buffer is enough, the stream orders its users."""
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            with torch.cuda.stream(self.stream):
+                self._scratch = torch.empty((int(nbytes),), dtype=torch.uint8, device=self.device)
+        return self._scratch
+
+    def staged(self, k, event, nbytes):
+        """Pinned staging slot k was read by a copy the caller enqueued on the copy stream; `event` follows that copy."""
+        self._busy[k] = event
+        self.bytes += int(nbytes)
 
     def release(self, slot, event):
         """The consumer of device slot `slot` is done once `event` has passed (None: it is done now)."""

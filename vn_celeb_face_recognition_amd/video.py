@@ -40,10 +40,13 @@ def tracker_row(time_in_video, frame_idx, names, bboxes, frame_shape):
 class FrameSource:
     """Batches of a frame stream for one rank.  `frames` is either a random-access sequence (len + __getitem__: a list
     of image paths is decoded with `load`, an array is indexed) or a plain iterator (a decoder: the other ranks' frames
-    are pulled and dropped).  Frame numbers start at 1 and time = number / fps, as demo_video.py:84-90 counts them."""
+    are pulled and dropped).  Frame numbers start at 1 and time = number / fps, as demo_video.py:84-90 counts them.
+    compressed: optional callable i -> the JPEG bytes of frame i of a random-access source, or None for a frame that is
+    no JPEG (a Motion-JPEG AVI's chunks, the .jpg files of a directory): what `rank_batches(compressed=True)` yields."""
 
-    def __init__(self, frames, fps, load=None):
+    def __init__(self, frames, fps, load=None, compressed=None):
         self.frames, self.fps, self.load = frames, float(fps), load
+        self.compressed = compressed if (compressed is not None and hasattr(frames, "__getitem__")) else None
         self.random_access = hasattr(frames, "__getitem__") and hasattr(frames, "__len__")
         self.reads = 0   # frames this rank actually fetched (tests)
         self.total = len(frames) if self.random_access else None   # frames in the stream (iterators: known once exhausted)
@@ -53,13 +56,28 @@ class FrameSource:
         f = self.frames[i]
         return self.load(f) if self.load is not None else np.asarray(f)
 
-    def rank_batches(self, n_frames, rank=0, world=1):
-        """yields (batch_index, [frames], [[time, frame_number], ...]) for batches with batch_index % world == rank"""
+    def _get_compressed(self, idx):
+        """jpeg.CompressedBatch of the frames idx when every one of them is a JPEG, else None"""
+        from .jpeg import CompressedBatch
+        out = CompressedBatch()
+        for i in idx:
+            d = self.compressed(i)
+            if d is None:
+                return None
+            out.append(d)
+        self.reads += len(out)
+        return out
+
+    def rank_batches(self, n_frames, rank=0, world=1, compressed=False):
+        """yields (batch_index, [frames], [[time, frame_number], ...]) for batches with batch_index % world == rank.
+        compressed=True: a batch whose frames are all JPEGs comes as a jpeg.CompressedBatch of their bytes, not
+        decoded; every other batch as decoded frames, as without it."""
         if self.random_access:
             total = len(self.frames)
             for b in range(rank, (total + n_frames - 1) // n_frames, world):
                 idx = range(b * n_frames, min(total, (b + 1) * n_frames))
-                yield b, [self._get(i) for i in idx], [[(i + 1) / self.fps, i + 1] for i in idx]
+                q = self._get_compressed(idx) if (compressed and self.compressed is not None) else None
+                yield b, q if q is not None else [self._get(i) for i in idx], [[(i + 1) / self.fps, i + 1] for i in idx]
             return
         b, q, inf, count = 0, [], [], 0
         for frame in self.frames:
@@ -83,7 +101,8 @@ class FrameSource:
         return iter(self.frames)
 
 
-def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None):
+def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
+               decode="device"):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
 
     pipe: FacePipeline-like -- .submit(frames_dev, classify=False[, ready=event]) -> ticket with .result() ->
@@ -93,6 +112,10 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     on_frame(frame_rgb, frame_number, names, boxes): called on the rank that owns the frame (annotated-frame writer);
     requesting it makes every rank classify the gathered embeddings (the names are needed where the pixels are).
     cap: faces per rank and round carried by the fixed-size exchange (default max(256, 16 * n_frames)).
+    decode: "device" (default) -- on a GPU, a batch the source can hand over as JPEG bytes (FrameSource.compressed) is
+    decoded by jpeg.decode_batch_device: entropy decode on host threads, pixels on the upload stream; a batch it does
+    not take is decoded by Pillow and uploaded, as every batch is with decode="host".  The frames are the same bytes
+    either way; on_frame receives a jpeg.HostFrame (shape + pixels on demand) for a device-decoded frame.
     Returns (rows: {frame_number: csv row}, complete on rank 0; frames processed by this rank)."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     on_gpu = dev.type == "cuda"
@@ -231,13 +254,28 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     def uploads():
         """this rank's batches with the upload one batch AHEAD: submit() blocks on the detector's single read-back, so
         the next batch's host -> HBM copy has to be in flight before it, or copy and detection would take turns"""
-        it = source.rank_batches(n_frames, rank, world)
-        nxt = next(it, None)
-        up = (uploader.upload(nxt[1]) + (uploader.last_slot,)) if (nxt is not None and uploader is not None) else None
+        if decode not in ("device", "host"):
+            raise ValueError("run_stream: decode must be 'device' or 'host', got %r" % (decode,))
+        if uploader is not None and decode == "device" and getattr(source, "compressed", None) is not None:
+            it = source.rank_batches(n_frames, rank, world, compressed=True)
+        else:
+            it = source.rank_batches(n_frames, rank, world)
+
+        def start(item):
+            """enqueue a batch's way into HBM -> (item with host-side frames, (frames_dev, ready, slot) or None)"""
+            if item is None or uploader is None:
+                return item, None
+            from .jpeg import CompressedBatch, decode_batch
+            b, q, inf = item
+            if isinstance(q, CompressedBatch):
+                frames_dev, ev, slot, q = decode_batch(q, dev, uploader)
+                return (b, q, inf), (frames_dev, ev, slot)
+            return item, uploader.upload(q) + (uploader.last_slot,)
+
+        nxt, up = start(next(it, None))
         while nxt is not None:
             cur, cur_up = nxt, up
-            nxt = next(it, None)
-            up = (uploader.upload(nxt[1]) + (uploader.last_slot,)) if (nxt is not None and uploader is not None) else None
+            nxt, up = start(next(it, None))
             yield cur, cur_up
 
     rounds = 0
