@@ -466,6 +466,46 @@ int64_t vnf_jpeg_workspace_bytes(int n, int width, int height, int sampling);
 int vnf_jpeg_decode_frames(const int16_t* coefs_dev, const uint8_t* quant_dev, int n, int width, int height,
                            int sampling, uint8_t* frames_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One-convolution probe (debug / test entry) -------------------------------------------------- */
+/* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile
+ * configurations (three kernel families, each compiled for five storage layouts).  A probe is a plan of exactly ONE
+ * convolution of the caller's geometry, packed as the plans pack theirs, that runs one NAMED configuration on the
+ * caller's device buffers, so that every instantiation can be compared with a reference of
+ *     out[m][co] = store(act(sum_k x[pix(m) + tap(k)] * w[co][k] + bias[class(m)][co] + res[m][co]))
+ * Nothing is tuned and nothing falls back.  Release with vnf_destroy. */
+typedef struct {
+  int32_t n, h, w, cin;          /* input: n images of h x w pixels, cin channels consumed */
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t cout;                  /* multiple of 8 */
+  int32_t x_coff, ldx;           /* the input is channels [x_coff, x_coff + cin) of an NHWC buffer ldx channels wide */
+  int32_t nseg;                  /* 1..4: output channels [seg_c0[i], seg_c1[i]) go to channels [seg_coff[i], ...) of */
+  int32_t seg_c0[4], seg_c1[4];  /*   buffer i, seg_ld[i] channels wide; the segments tile [0, cout), all four numbers */
+  int32_t seg_ld[4], seg_coff[4];/*   multiples of 8 */
+  int32_t has_res, ldres, res_coff; /* residual: channels [res_coff, res_coff + cout) of an (n,Ho,Wo,ldres) buffer */
+  int32_t act;                   /* 0 none, 1 ReLU, 2 PReLU (per-channel slopes) */
+  int32_t out_f32;               /* outputs are fp32 whatever the dtype */
+  int32_t dtype, planar;         /* VNF_F32 | VNF_BF16 | VNF_F16 | VNF_F16X2; planar: with VNF_F16X2, the encoders'
+                                    8-channel units [8 hi][8 lo] instead of interleaved (hi, lo) pairs */
+} vnf_conv_probe_geom;
+/* w: host fp32 [cout][cin][kh][kw]; bias, slope (with act 2, else NULL), pre_s / pre_t (a BatchNorm x * pre_s[c] +
+ * pre_t[c] on the unpadded input, folded into the weights and nine border-class biases; both or neither): host fp32
+ * per channel, may be NULL.  The persistent switch of the wave-specialised kernels is VNF_WS_PERSIST as it is now, as
+ * for every handle.  VNF_E_INVALID: a geometry, alignment or layout the convolution core does not take. */
+int vnf_conv_probe_create(const vnf_conv_probe_geom* geom, const float* w, const float* bias, const float* slope,
+                          const float* pre_s, const float* pre_t, vnf_handle* out);
+/* Returns the number of tile configurations (or a negative VNF_E_* code).  admitted (NULL, or `capacity` >= that number
+ * of entries): 1 where the launcher admits configuration id for this convolution, else 0.  family_sizes (may be NULL):
+ * how many of the ids are ring, patch and wave-specialised tiles, in id order. */
+int vnf_conv_probe_cfgs(vnf_handle probe, int32_t* admitted, int capacity, int32_t family_sizes[3]);
+/* The tile of configuration cfg, whatever the convolution: {family (0 ring, 1 patch, 2 wave-specialised), BM, BN, waves
+ * along M, waves along N, ring stages}.  Host only.  VNF_E_INVALID: no such id. */
+int vnf_conv_cfg_tile(int cfg, int32_t tile[6]);
+/* One launch of configuration cfg (-1: the launcher's heuristic) and a synchronisation of `stream`.  x, out[0..nseg) and
+ * res are device pointers to the WHOLE buffers of the geometry, in the storage layout; the call writes the output
+ * slices' first n*Ho*Wo rows and nothing else.  VNF_E_INVALID when the configuration is not admitted (never another
+ * one in its place); VNF_E_HIP with the error of that launch; no retry. */
+int vnf_conv_probe_run(vnf_handle probe, int cfg, const void* x, void* const* out, const void* res, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, REPO, load_image, seeded_normal
+from conv_reference import from_planar as _from_planar, to_planar as _to_planar
 from seir_restatement import seir101_forward
 
 pytestmark = pytest.mark.gpu
@@ -146,24 +147,6 @@ def _se_call(t, res, code, planar, n, h, w, c, wts, slope_se, slope_out):
                                         p[0], p[1], slope_se, p[2], p[3], slope_out, ctypes.c_void_p(y.data_ptr()),
                                         _lib.current_stream_ptr()))
     return y
-
-
-def _split(x):
-    hi = x.half()
-    lo = (x - hi.float()).half()
-    return hi, lo
-
-
-def _to_planar(x):   # (n,H,W,C) fp32 -> the encoders' 8-channel units [8 hi][8 lo], and the values the pairs stand for
-    n, H, W, C = x.shape
-    hi, lo = _split(x)
-    p = torch.stack([hi.view(n, H, W, C // 8, 8), lo.view(n, H, W, C // 8, 8)], dim=-2).contiguous().view(torch.int32).view(x.shape)
-    return p, hi.float() + lo.float()
-
-
-def _from_planar(p):
-    n, H, W, C = p.shape
-    return p.view(torch.float16).view(n, H, W, C // 8, 2, 8).float().sum(-2).reshape(n, H, W, C)
 
 
 def _ordered16(t):   # 16-bit floats as integers in value order: neighbours differ by 1

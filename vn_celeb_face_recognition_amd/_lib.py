@@ -40,6 +40,12 @@ class JpegInfo(ctypes.Structure):
                 ("quant", (ctypes.c_uint8 * 64) * 3), ("coef_count", ctypes.c_int64)]
 
 
+class ConvProbeGeom(ctypes.Structure):   # vnf_conv_probe_geom
+    _fields_ = ([(k, ctypes.c_int32) for k in ("n", "h", "w", "cin", "kh", "kw", "sh", "sw", "ph", "pw", "cout", "x_coff", "ldx", "nseg")] +
+                [(k, ctypes.c_int32 * 4) for k in ("seg_c0", "seg_c1", "seg_ld", "seg_coff")] +
+                [(k, ctypes.c_int32) for k in ("has_res", "ldres", "res_coff", "act", "out_f32", "dtype", "planar")])
+
+
 _lib = None
 
 # every symbol include/vnface.h declares, with its ctypes signature
@@ -68,6 +74,10 @@ SIGNATURES = {
     "vnf_softmax_topk": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "vnf_maxpool3s2p1": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vnf_se_block": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _P, ctypes.c_float, _P, _P]),
+    "vnf_conv_probe_create": (_I, [ctypes.POINTER(ConvProbeGeom), _P, _P, _P, _P, _P, ctypes.POINTER(_P)]),
+    "vnf_conv_probe_cfgs": (_I, [_P, ctypes.POINTER(ctypes.c_int32), _I, ctypes.POINTER(ctypes.c_int32)]),
+    "vnf_conv_cfg_tile": (_I, [_I, ctypes.POINTER(ctypes.c_int32)]),
+    "vnf_conv_probe_run": (_I, [_P, _I, _P, ctypes.POINTER(_P), _P, _P]),
     "vnf_mlp_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "vnf_classify": (_I, [_P, _P, _I, _P, _P, _P, _P]),
     "vnf_mlp_trainer_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float,

@@ -466,11 +466,13 @@ constexpr int patch_epi_bytes(int bm, int bn, int wm) {
 }
 int patch_num_cfgs();
 bool patch_cfg_ok(const ConvArgs& a, int pcfg);
+bool patch_cfg_tile(int pcfg, ConvTile& t);
 hipError_t launch_patch(const ConvArgs& a, const KArgs& k, int pcfg, hipStream_t s);
 
 // ---- conv_ws.hip (wave-specialised big-tile kernel; configuration ids follow the patch kernel's)
 int ws_num_cfgs();
 bool ws_cfg_ok(const ConvArgs& a, int wcfg);
+bool ws_cfg_tile(int wcfg, ConvTile& t);
 hipError_t launch_ws(const ConvArgs& a, const KArgs& k, int wcfg, hipStream_t s);
 
 }  // namespace vnf

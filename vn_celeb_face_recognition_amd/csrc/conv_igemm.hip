@@ -332,6 +332,14 @@ static constexpr TileCfg kCfgs[] = {
 constexpr int kNumCfgs = (int)(sizeof(kCfgs) / sizeof(kCfgs[0]));
 
 int conv_num_cfgs() { return kNumCfgs + patch_num_cfgs() + ws_num_cfgs(); }
+void conv_family_sizes(int sizes[3]) { sizes[0] = kNumCfgs; sizes[1] = patch_num_cfgs(); sizes[2] = ws_num_cfgs(); }
+bool conv_cfg_tile(int cfg, ConvTile& t) {
+  if (cfg >= kNumCfgs + patch_num_cfgs()) return ws_cfg_tile(cfg - kNumCfgs - patch_num_cfgs(), t);
+  if (cfg >= kNumCfgs) return patch_cfg_tile(cfg - kNumCfgs, t);
+  if (cfg < 0) return false;
+  t = ConvTile{0, kCfgs[cfg].bm, kCfgs[cfg].bn, kCfgs[cfg].wm, kCfgs[cfg].wn, kCfgs[cfg].s};
+  return true;
+}
 
 static bool dma_capable(const ConvArgs& a) { return (a.Kpad / (128 / dtype_size(a.dtype))) * 8 * 16 <= 24 * 1024; }
 

@@ -277,6 +277,11 @@ static constexpr PatchCfg kPatch[] = {
 constexpr int kNumPatch = (int)(sizeof(kPatch) / sizeof(kPatch[0]));
 
 int patch_num_cfgs() { return kNumPatch; }
+bool patch_cfg_tile(int pcfg, ConvTile& t) {
+  if (pcfg < 0 || pcfg >= kNumPatch) return false;
+  t = ConvTile{1, kPatch[pcfg].bm, kPatch[pcfg].bn, kPatch[pcfg].wm, kPatch[pcfg].wn, kPatch[pcfg].s};
+  return true;
+}
 
 // most virtual input rows any BM-pixel tile of a (Ho x Wo, KH) layer touches
 static int patch_rows_max(int Wo, int Ho, int KH, int BM) {

@@ -602,6 +602,11 @@ static constexpr WsCfg kWs[] = {
 constexpr int kNumWs = (int)(sizeof(kWs) / sizeof(kWs[0]));
 
 int ws_num_cfgs() { return kNumWs; }
+bool ws_cfg_tile(int wcfg, ConvTile& t) {
+  if (wcfg < 0 || wcfg >= kNumWs) return false;
+  t = ConvTile{2, kWs[wcfg].bm, kWs[wcfg].bn, kWs[wcfg].wm, kWs[wcfg].wn, kWs[wcfg].s};
+  return true;
+}
 
 bool ws_cfg_ok(const ConvArgs& a, int wcfg) {
   if (wcfg < 0 || wcfg >= kNumWs) return false;

@@ -53,6 +53,13 @@ struct ConvArgs {
 hipError_t launch_conv(const ConvArgs& a, hipStream_t s);
 int conv_num_cfgs();
 bool conv_cfg_ok(const ConvArgs& a, int cfg);  // is tile configuration `cfg` usable for this convolution
+// the ids are three families one after another: ring tiles (conv_igemm.hip), patch tiles (conv_patch.hip),
+// wave-specialised tiles (conv_ws.hip); their sizes add up to conv_num_cfgs()
+void conv_family_sizes(int sizes[3]);
+// the tile of configuration `cfg`: family (0 ring, 1 patch, 2 wave-specialised), BM x BN, waves along M and N (the
+// wave-specialised family: consumer waves), ring stages; false: no such id
+struct ConvTile { int family, bm, bn, wm, wn, stages; };
+bool conv_cfg_tile(int cfg, ConvTile& t);
 
 // NCHW (n,3,S,S) of x_dtype -> NHWC8 of dtype (channels 3..7 zero)
 hipError_t launch_pack_input(const void* x, int x_dtype, void* out, int dtype, int n, int hw, hipStream_t s);

@@ -25,6 +25,12 @@ int add_conv(Encoder& e, const ConvSpec& s) {
   L.cout = cout;
   L.cout_pad = (cout + 127) / 128 * 128;
   L.ncls = s.pre_s ? 9 : 1;
+  // The nine border-class biases below, and the epilogue that picks one by ho == 0 / ho == Ho - 1 (wo alike), hold where
+  // row 0 loses exactly the ph top taps, row Ho - 1 exactly the ph bottom taps and no row between them any: stride 1,
+  // at most one padding row / column, and a first and a last row / column that are two different ones.
+  if (s.pre_s && (!s.pre_t || s.sh != 1 || s.sw != 1 || s.ph > 1 || s.pw > 1 || (s.ph > 0 && L.Ho < 2) || (s.pw > 0 && L.Wo < 2)))
+    return fail(VNF_E_INVALID, s.name + ": a folded pre-conv BatchNorm needs stride 1, padding <= 1 and, where it pads, "
+                               "at least two output rows / columns");
   if (cout % 8) return fail(VNF_E_INVALID, s.name + ": cout % 8");
 
   std::vector<float> wpk((size_t)L.cout_pad * L.Kpad, 0.f);
