@@ -12,7 +12,10 @@ PNG-encodes every frame).  Input: a directory of frames, a
 (T,H,W,3) RGB frames, a Motion-JPEG .avi, or any video file when OpenCV is installed; -ov exports the annotated frames
 as a video (MP4V with OpenCV, Motion-JPEG .avi without).  JPEG frames (a Motion-JPEG .avi, .jpg files) are decoded on the
 GPU (jpeg.py: Huffman decode on host threads, IDCT / upsampling / colour in HIP), bit-exact to the host decoder;
---host_decode keeps them on Pillow."""
+--host_decode keeps them on Pillow.  -ov x.avi WITHOUT -sfr never makes a PNG: boxes and names are drawn on the frames
+where they lie in HBM and the frames are JPEG-encoded there (jpeg_encode.py: overlay, colour, down-sampling, DCT and
+quantisation in HIP, the Huffman pass on host threads), the same files Pillow would write (--ov_quality,
+--ov_subsampling)."""
 import os
 import time
 
@@ -29,8 +32,9 @@ from vn_celeb_face_recognition_amd.pipeline import FacePipeline
 from vn_celeb_face_recognition_amd.video import run_stream, tracker_row  # noqa: F401  (tracker_row: part of this module's surface)
 
 
-def main(args, pipe, rank, world, source=None, device=None):
-    """demo_video.py:46-199 on the resident pipeline; identical control flow for every world size (video.run_stream)."""
+def main(args, pipe, rank, world, source=None, device=None, encoder=None):
+    """demo_video.py:46-199 on the resident pipeline; identical control flow for every world size (video.run_stream).
+    encoder: a jpeg_encode.VideoEncoder that receives every annotated frame (-ov without -sfr), or None."""
     if rank == 0:
         os.makedirs(args.output_frame, exist_ok=True)
         with open(args.output_tracker, 'w') as f:
@@ -51,7 +55,7 @@ def main(args, pipe, rank, world, source=None, device=None):
 
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
                                  on_frame=on_frame if args.save_frame_recognized else None, log=log,
-                                 decode="host" if getattr(args, "host_decode", False) else "device")
+                                 decode="host" if getattr(args, "host_decode", False) else "device", encoder=encoder)
     if world > 1:
         tot = torch.tensor([processed], device=device if device is not None else 'cuda')
         dist.all_reduce(tot)
@@ -76,21 +80,47 @@ if __name__ == '__main__':
     p.add_argument('--n_frames', default=16, type=int)
     p.add_argument('--host_decode', action='store_true',
                    help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
+    p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov without -sfr (1..100)')
+    p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
+                   help='chroma subsampling of the frames of -ov without -sfr')
     args = p.parse_args()
     if args.inference_method != 'par_fd_vs_aln':
         raise SystemExit("use --inference_method par_fd_vs_aln (seq_fd_vs_aln needs the FAN landmark network, outside "
                          "the hot path and broken in the reference for list input)")
-    if args.output_video and not args.save_frame_recognized:
-        raise SystemExit("-ov assembles the annotated frames of --output_frame: add -sfr (the reference writes every frame "
-                         "unconditionally, demo_video.py:149)")
+    device_video = bool(args.output_video) and not args.save_frame_recognized
+    if device_video and not args.output_video.lower().endswith('.avi'):
+        raise SystemExit("-ov without -sfr encodes the annotated frames on the GPU into a Motion-JPEG AVI: give -ov a name "
+                         "ending in .avi, or add -sfr to assemble the PNGs of --output_frame on the host")
+    if device_video and not 1 <= args.ov_quality <= 100:
+        raise SystemExit("--ov_quality must be in 1..100")
     rank, world, local = vdist.init_from_env()
     device = 'cuda:%d' % local
     torch.cuda.set_device(local)
     label2name_df, detection_md, emb_model, classify_model = build_models(args, device)
     pipe = FacePipeline(detection_md, emb_model, classify_model, label2name_df, args.target_face_size, args.recog_threshold,
                         embed_batch=256)
-    main(args, pipe, rank, world, device=device)
-    if args.output_video and rank == 0:
+    encoder = None
+    if device_video:
+        from vn_celeb_face_recognition_amd.jpeg_encode import VideoEncoder
+        encoder = VideoEncoder(args.output_video, args.fps_video, device, args.ov_quality, args.ov_subsampling, rank, world)
+    try:
+        main(args, pipe, rank, world, device=device, encoder=encoder)
+    except BaseException:
+        if encoder is not None:
+            encoder.abort()                                   # no half-written video, no spool file of this rank
+        raise
+    if encoder is not None:
+        try:
+            encoder.close()
+        except ValueError as e:                               # a stream without frames
+            raise SystemExit("-ov: {}".format(e))
+        if world > 1:
+            dist.barrier()                                    # every rank's spool file is complete
+            if rank == 0:
+                encoder.merge()
+        if rank == 0:
+            print('Save exported video in {} ...'.format(args.output_video))
+    elif args.output_video and rank == 0:
         export_video_face_recognition(args.output_frame, args.fps_video, args.output_video)     # demo_video.py:285-287
     if world > 1:
         dist.destroy_process_group()

@@ -40,6 +40,10 @@
  *   vnf_jpeg_probe / vnf_jpeg_entropy_decode / vnf_jpeg_decode_frames
  *                                    cv2.VideoCapture.read as demo_video.py:78-110 calls it (a frame of a
  *                                    Motion-JPEG stream: bitstream walk on the host, pixels on the device)
+ *   vnf_jpeg_encode_frames / vnf_jpeg_entropy_encode / vnf_overlay_draw
+ *                                    demo_video.py:25-43,149-152 (cv2.rectangle / putText on the frame, cv2.imwrite,
+ *                                    cv2.VideoWriter.write: the annotated frame is drawn and transformed on the
+ *                                    device, the Huffman pass and the container stay on the host)
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -465,6 +469,74 @@ int64_t vnf_jpeg_workspace_bytes(int n, int width, int height, int sampling);
  * VNF_E_CAPACITY: workspace_bytes below vnf_jpeg_workspace_bytes(...). */
 int vnf_jpeg_decode_frames(const int16_t* coefs_dev, const uint8_t* quant_dev, int n, int width, int height,
                            int sampling, uint8_t* frames_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* JPEG video frames, written --------------------------------------------------------------- */
+/* The way out of the device: the reference draws on every frame with OpenCV and hands it to cv2.VideoWriter
+ * (demo_video.py:25-43,149-152), one frame at a time on the host.  Here the annotated frame is drawn (vnf_overlay_draw),
+ * colour-converted, down-sampled, DCT-transformed and quantised (vnf_jpeg_encode_frames) where it already lives; the
+ * serial Huffman pass (vnf_jpeg_entropy_encode: plain C++, no HIP call, usable without a GPU, thread-safe, one frame per
+ * call) writes the file.  The arithmetic is libjpeg's public baseline encoder (16-bit fixed-point colour, box
+ * down-sampling with alternating bias, islow forward DCT, quantisation by division), all integer, so the coefficients --
+ * and with the annex K Huffman tables the files -- are those libjpeg / libjpeg-turbo write without `optimize`. */
+
+/* The annex K.1 tables scaled as libjpeg's jpeg_set_quality does (quality < 50: 5000 / quality, else 200 - 2 quality;
+ * entry = (base * scale + 50) / 100 clamped to 1..255), natural (row-major) order.  Host only.  quality outside 1..100 or
+ * a NULL pointer: VNF_E_INVALID. */
+int vnf_jpeg_quant_tables(int quality, uint8_t luma[64], uint8_t chroma[64]);
+/* What vnf_jpeg_probe fills for a width x height RGB frame written with this sampling and quality: factors, blocks_w/h
+ * (MCU-padded), quant (rows 1 and 2 both the chroma table), coef_count, restart_interval 0.  Host only.  VNF_E_INVALID:
+ * width or height outside 1..65535, quality outside 1..100, a sampling other than VNF_JPEG_444 / _422 / _420
+ * (VNF_JPEG_GRAY is refused: frames are RGB). */
+int vnf_jpeg_encode_info(int width, int height, int sampling, int quality, vnf_jpeg_info* out);
+/* bytes of device workspace vnf_jpeg_encode_frames needs for n frames of this geometry (the component planes between
+ * its two launches), or a negative VNF_E_* code */
+int64_t vnf_jpeg_encode_workspace_bytes(int n, int width, int height, int sampling);
+/* n frames of ONE geometry through colour conversion, down-sampling, forward DCT and quantisation with ONE pair of tables:
+ *   frames_dev: device (n,height,width,3) u8 RGB; quant_dev: device (2,64) u8, luma then chroma, natural order, 8-byte
+ *   aligned (a zero entry is read as 1); coefs_out: device (n, coef_count) int16, 16-byte aligned, in EXACTLY the layout
+ *   vnf_jpeg_entropy_decode writes and vnf_jpeg_decode_frames reads: planes one after another, blocks in raster order,
+ *   blocks_w per row, the dummy blocks that pad the luma plane to whole MCUs included (zero but for the DC libjpeg gives
+ *   them); workspace: device, 16-byte aligned.
+ * Two launches (planes, then DCT + quantisation), nothing allocated, no synchronisation.  n == 0: no-op.
+ * VNF_E_INVALID: n < 0, a NULL or misaligned pointer, width or height outside 1..65535, a sampling other than
+ * VNF_JPEG_444 / _422 / _420; VNF_E_CAPACITY: workspace_bytes below vnf_jpeg_encode_workspace_bytes(...). */
+int vnf_jpeg_encode_frames(const uint8_t* frames_dev, int n, int width, int height, int sampling, const uint8_t* quant_dev,
+                           int16_t* coefs_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Huffman-encodes coefs[0, info->coef_count) (the layout above; info as vnf_jpeg_encode_info or vnf_jpeg_probe fill it:
+ * three components, no restart interval, quant[1] == quant[2]) into a complete baseline JFIF file in out[0, capacity):
+ * SOI, APP0, two DQT, SOF0, four DHT (the annex K.3 tables), SOS, one interleaved scan (FF bytes stuffed, the last byte
+ * padded with 1-bits), EOI.  *len_out receives the file's length.  Host only, thread-safe, one frame per call.
+ * VNF_E_CAPACITY: the file does not fit -- nothing was written outside [0, capacity) and *len_out is the length that
+ * would have fitted; VNF_E_INVALID: a NULL pointer, an info outside the above, or a coefficient outside the baseline
+ * range (an AC magnitude category above 10, a DC difference category above 11). */
+int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info* info, uint8_t* out, int64_t capacity,
+                            int64_t* len_out);
+
+/* frame overlay ---------------------------------------------------------------------------- */
+#define VNF_OVERLAY_RECT 0
+#define VNF_OVERLAY_LABEL 1
+/* One drawing step on one frame of a batch.
+ *   VNF_OVERLAY_RECT:  the outline, 2 pixels thick, of the rectangle with corners (x0,y0) and (x1,y1), both inside it
+ *                      (ImageDraw.rectangle(width=2) for corners truncated toward zero; boxes of 3 pixels and more);
+ *   VNF_OVERLAY_LABEL: (x0,y0) is where the top-left pixel of a coverage mask of x1 columns and y1 rows goes; the mask
+ *                      is masks[mask_offset, mask_offset + x1 * y1), row-major, 255 = full colour.
+ * rgb: the colour as r | g << 8 | b << 16. */
+typedef struct {
+  int32_t kind, frame;
+  int32_t x0, y0, x1, y1;
+  int32_t mask_offset;
+  uint32_t rgb;
+} vnf_overlay_op;
+/* cli_utils.draw_boxes_on_image (demo_image.py:150-158) on frames in device memory, in place, one launch: frames_dev
+ * device (b,height,width,3) u8; ops_dev device (n_ops) entries in DRAW ORDER (a later entry paints over an earlier one
+ * of the same frame; the entries of different frames may interleave); masks_dev device u8 (masks_bytes of them, may be
+ * NULL when that is 0).  A label pixel is blended per channel as v = bg (255 - m) + c m + 128, ((v >> 8) + v) >> 8.
+ * Everything is clipped to the frame.  The table lives in device memory, so the call cannot see its values: an entry
+ * whose frame is outside 0..b-1, whose kind is unknown or whose mask leaves [0, masks_bytes) paints nothing.
+ * Nothing allocated, no synchronisation.  b == 0 or n_ops == 0: no-op.  VNF_E_INVALID: a negative count, height or
+ * width outside 1..65535, a NULL frames_dev / ops_dev. */
+int vnf_overlay_draw(uint8_t* frames_dev, int b, int height, int width, const vnf_overlay_op* ops_dev, int n_ops,
+                     const uint8_t* masks_dev, int64_t masks_bytes, void* stream);
 
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile

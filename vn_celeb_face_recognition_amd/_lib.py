@@ -40,6 +40,10 @@ class JpegInfo(ctypes.Structure):
                 ("quant", (ctypes.c_uint8 * 64) * 3), ("coef_count", ctypes.c_int64)]
 
 
+class OverlayOp(ctypes.Structure):   # vnf_overlay_op
+    _fields_ = [(k, ctypes.c_int32) for k in ("kind", "frame", "x0", "y0", "x1", "y1", "mask_offset")] + [("rgb", ctypes.c_uint32)]
+
+
 class ConvProbeGeom(ctypes.Structure):   # vnf_conv_probe_geom
     _fields_ = ([(k, ctypes.c_int32) for k in ("n", "h", "w", "cin", "kh", "kw", "sh", "sw", "ph", "pw", "cout", "x_coff", "ldx", "nseg")] +
                 [(k, ctypes.c_int32 * 4) for k in ("seg_c0", "seg_c1", "seg_ld", "seg_coff")] +
@@ -110,6 +114,12 @@ SIGNATURES = {
     "vnf_jpeg_entropy_decode": (_I, [_P, ctypes.c_int64, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64]),
     "vnf_jpeg_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
     "vnf_jpeg_decode_frames": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, ctypes.c_int64, _P]),
+    "vnf_jpeg_quant_tables": (_I, [_I, _P, _P]),
+    "vnf_jpeg_encode_info": (_I, [_I, _I, _I, _I, ctypes.POINTER(JpegInfo)]),
+    "vnf_jpeg_encode_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
+    "vnf_jpeg_encode_frames": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "vnf_jpeg_entropy_encode": (_I, [_P, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
 }
 
 

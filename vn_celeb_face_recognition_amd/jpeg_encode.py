@@ -1,0 +1,360 @@
+"""Annotated video frames encoded on the device (include/vnface.h, "JPEG video frames, written" and "frame overlay").
+
+The reference draws boxes and names on every frame with OpenCV and hands the frame to cv2.VideoWriter
+(/root/reference/demo_video.py:25-43,149-152); this package decoded the frame again on the host, drew with Pillow, wrote a
+PNG and, after the run, read every PNG back to JPEG-encode it on one thread.  Here the frame stays where the detector
+read it:
+
+  * boxes and names are painted in place by one launch (csrc/overlay.hip; `overlay_ops` builds its table -- the label
+    masks are rendered by Pillow's own font code, so the glyphs are Pillow's);
+  * colour conversion, chroma down-sampling, forward DCT and quantisation run on the MI355X (csrc/jpeg_encode.hip);
+  * one D2H copy brings the coefficients (not the pixels) into pinned memory, and the serial Huffman pass
+    (csrc/jpeg_huff_encode.cpp) runs on a few host threads, one frame each (ctypes releases the GIL).
+
+The files are libjpeg's (and so Pillow's `save(format="JPEG", quality=q, subsampling=s)`) byte for byte.
+"""
+import ctypes
+import math
+import os
+import struct
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import _lib
+from .jpeg import S420, S422, S444
+
+SAMPLINGS = {"4:4:4": S444, "4:2:2": S422, "4:2:0": S420}
+ENTROPY_THREADS = 8                             # fixed: the frames of a batch, never sized from the machine's CPU count
+RECT, LABEL = 0, 1                              # VNF_OVERLAY_*
+GREEN = (0, 255, 0)                             # cli_utils.draw_boxes_on_image
+OP_DTYPE = np.dtype([("kind", "<i4"), ("frame", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"),
+                     ("mask_offset", "<i4"), ("rgb", "<u4")])          # vnf_overlay_op
+_COORD = 1 << 30                                # table coordinates are clamped here: far outside any frame either way
+ENCODE_STREAM_ROLE = 8                          # streams.side_stream roles: 0..5 the pipeline's, 6 upload, 7 collective
+
+_pool = None
+
+
+def _entropy_pool():
+    global _pool
+    if _pool is None:
+        _pool = ThreadPoolExecutor(max_workers=ENTROPY_THREADS, thread_name_prefix="vnf-jpeg-enc")
+    return _pool
+
+
+def sampling_code(sampling):
+    if sampling in SAMPLINGS:
+        return SAMPLINGS[sampling]
+    if sampling in SAMPLINGS.values():
+        return int(sampling)
+    raise ValueError("sampling must be one of %s, got %r" % (", ".join(SAMPLINGS), sampling))
+
+
+def quant_tables(quality):
+    """(2,64) u8: libjpeg's luma and chroma tables for `quality` (1..100), natural order"""
+    out = np.zeros((2, 64), np.uint8)
+    _lib.check(_lib.load().vnf_jpeg_quant_tables(int(quality), out[0].ctypes.data, out[1].ctypes.data))
+    return out
+
+
+def encode_info(width, height, sampling, quality):
+    """the JpegInfo of a (height,width,3) RGB frame written with this sampling and quality"""
+    info = _lib.JpegInfo()
+    _lib.check(_lib.load().vnf_jpeg_encode_info(int(width), int(height), sampling_code(sampling), int(quality),
+                                                ctypes.byref(info)))
+    return info
+
+
+def entropy_encode(coefs, info):
+    """Huffman-encode one frame's coefficients (C-contiguous int16, info.coef_count of them) -> the JPEG file's bytes"""
+    if coefs.dtype != np.int16 or not coefs.flags.c_contiguous or coefs.size < info.coef_count:
+        raise ValueError("entropy_encode: coefs must be a contiguous int16 array of at least info.coef_count elements")
+    lib = _lib.load()
+    cap = 1024 + int(info.coef_count)           # a byte per coefficient covers all but noise at quality 100
+    n = ctypes.c_int64()
+    for _ in range(2):
+        out = np.empty((cap,), np.uint8)
+        rc = lib.vnf_jpeg_entropy_encode(coefs.ctypes.data, ctypes.byref(info), out.ctypes.data, cap, ctypes.byref(n))
+        if rc == 0:
+            return out[:n.value].tobytes()
+        if rc != -4:                            # VNF_E_CAPACITY reports the size that fits
+            break
+        cap = int(n.value)
+    raise _lib.VnfError("vnf_jpeg_entropy_encode failed (%d): a coefficient outside the baseline range or a bad info" % rc)
+
+
+def encode_frames(frames_dev, quant_dev, coefs_out, workspace, sampling, stream_ptr=None):
+    """vnf_jpeg_encode_frames on torch tensors: frames_dev (n,H,W,3) u8 cuda, contiguous; enqueues on `stream_ptr`
+    (default: the current stream)."""
+    if not (frames_dev.is_cuda and quant_dev.is_cuda and coefs_out.is_cuda and workspace.is_cuda):
+        raise RuntimeError("jpeg_encode.encode_frames needs cuda tensors (there is no CPU path)")
+    if frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or not frames_dev.is_contiguous():
+        raise ValueError("encode_frames: frames_dev must be a contiguous (n,H,W,3) u8 tensor")
+    n, h, w = (int(s) for s in frames_dev.shape[:3])
+    _lib.check(_lib.load().vnf_jpeg_encode_frames(
+        frames_dev.data_ptr(), n, w, h, sampling_code(sampling), quant_dev.data_ptr(), coefs_out.data_ptr(),
+        workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+        stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+    return coefs_out
+
+
+class BatchEncoder:
+    """Buffers of one (device, quality, sampling): the tables on the device, and -- grown to the largest batch seen --
+    the coefficient and plane buffers and the pinned landing area of the one D2H copy."""
+
+    def __init__(self, device, quality=92, sampling="4:2:0"):
+        import torch
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BatchEncoder needs a cuda device (there is no CPU path)")
+        self.quality, self.sampling = int(quality), sampling_code(sampling)
+        self.quant = torch.from_numpy(quant_tables(self.quality)).to(self.device)
+        self._coefs = self._ws = self._host = None
+        self.entropy_s = 0.0                    # host wall time of the last batch's threaded entropy pass (tools)
+
+    def enqueue(self, frames_dev, stream=None, timing=None):
+        """kernels + the D2H copy of the coefficients on `stream` (default: the current one) -> a handle for `finish`.
+        timing: optional dict; with timing["events"] set it receives 'kernel_events', two timed events around the
+        kernels."""
+        import torch
+        n, h, w = (int(s) for s in frames_dev.shape[:3])
+        info = encode_info(w, h, self.sampling, self.quality)
+        cc = int(info.coef_count)
+        ws = int(_lib.load().vnf_jpeg_encode_workspace_bytes(n, w, h, self.sampling))
+        if ws < 0:
+            _lib.check(ws)
+        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(stream):
+            if self._coefs is None or self._coefs.numel() < n * cc:
+                self._coefs = torch.empty((n * cc,), dtype=torch.int16, device=self.device)
+            if self._ws is None or self._ws.numel() < ws:
+                self._ws = torch.empty((ws,), dtype=torch.uint8, device=self.device)
+            if self._host is None or self._host.numel() < n * cc:
+                self._host = torch.empty((n * cc,), dtype=torch.int16).pin_memory()
+            if timing is not None and timing.get("events"):
+                e0 = torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+            encode_frames(frames_dev, self.quant, self._coefs, self._ws, self.sampling, ctypes.c_void_p(stream.cuda_stream))
+            if timing is not None and timing.get("events"):
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record(stream)
+                timing["kernel_events"] = (e0, e1)
+            kernels = stream.record_event()
+            self._host[:n * cc].copy_(self._coefs[:n * cc], non_blocking=True)
+            copied = stream.record_event()
+        return {"n": n, "cc": cc, "info": info, "kernels": kernels, "copied": copied}
+
+    def finish(self, job):
+        """wait for the copy, entropy-encode the frames on the pool -> list of JPEG files (bytes)"""
+        import time
+        job["copied"].synchronize()
+        n, cc, info = job["n"], job["cc"], job["info"]
+        host = self._host.numpy()[:n * cc].reshape(n, cc)
+        t0 = time.perf_counter()
+        one = lambda i: entropy_encode(host[i], info)
+        out = list(_entropy_pool().map(one, range(n))) if n > 1 else [one(0)]
+        self.entropy_s = time.perf_counter() - t0
+        return out
+
+    def encode(self, frames_dev, stream=None):
+        return self.finish(self.enqueue(frames_dev, stream))
+
+
+# one BatchEncoder per (device, quality, sampling) a caller of encode_batch_device has used, kept for the life of the
+# process: each holds the device coefficient / plane buffers and the pinned landing area of its largest batch (about
+# 9.4 MB + 6.3 MB pinned per 1080p 4:2:0 frame).  A caller that cycles through settings or wants the memory back owns
+# a BatchEncoder itself and drops it.
+_encoders = {}
+
+
+def encode_batch_device(frames_dev, quality=92, sampling="4:2:0", stream=None):
+    """frames_dev: (n,H,W,3) u8 cuda tensor -> a list of n JPEG files (bytes), the ones Pillow writes for these pixels
+    with save(format="JPEG", quality=quality, subsampling=sampling).  stream: a torch stream, or an object with a
+    `.stream` (upload.FrameUploader); default: the current stream.  Synchronises with the host (one D2H copy)."""
+    stream = getattr(stream, "stream", stream)
+    key = (str(frames_dev.device), int(quality), sampling_code(sampling))
+    if key not in _encoders:
+        _encoders[key] = BatchEncoder(frames_dev.device, quality, sampling)
+    return _encoders[key].encode(frames_dev, stream)
+
+
+# overlay -------------------------------------------------------------------------------------------------------------
+
+_font = None
+
+
+def _label_mask(name, fx, fy):
+    """The coverage of `name` as ImageDraw.text paints it with the pen at the sub-pixel offset (fx, fy) of a tile's
+    origin -> ((th,tw) u8 cut to the ink, its column and row inside the tile), or (None, 0, 0) for no ink.  Pillow
+    puts a text at int(anchor) with the signed fraction math.modf leaves as FreeType's start; drawing at (fx, fy)
+    makes exactly that call.  Ink left of or above the tile's origin is cut off: with a negative fraction the anchor is
+    negative, the origin lies at or outside the frame's edge, and those pixels are outside the frame too."""
+    from PIL import Image, ImageDraw
+    global _font
+    if _font is None:
+        _font = ImageDraw.Draw(Image.new("L", (1, 1))).getfont()
+    probe = ImageDraw.Draw(Image.new("L", (1, 1)))
+    _, _, r, b = probe.textbbox((fx, fy), name, font=_font)
+    im = Image.new("L", (max(1, int(math.ceil(r)) + 2), max(1, int(math.ceil(b)) + 2)), 0)
+    ImageDraw.Draw(im).text((fx, fy), name, fill=255, font=_font)
+    a = np.asarray(im)
+    ys, xs = np.nonzero(a)
+    if ys.size == 0:
+        return None, 0, 0
+    y0, x0 = int(ys.min()), int(xs.min())
+    return np.ascontiguousarray(a[y0:int(ys.max()) + 1, x0:int(xs.max()) + 1]), x0, y0
+
+
+def _trunc(v):
+    v = float(v)
+    if v != v:
+        raise ValueError("overlay_ops: a box coordinate is NaN")
+    return int(max(-_COORD, min(_COORD, v)))
+
+
+def overlay_ops(boxes, names, colour=GREEN):
+    """The host side of vnf_overlay_draw: what cli_utils.draw_boxes_on_image(frame, boxes[f], names[f]) paints on
+    every frame f of a batch, as a table.  boxes: per frame a list of (x1,y1,x2,y2); names: per frame as many strings.
+    -> (ops: OP_DTYPE array in draw order, masks: u8 array).  A frame's rectangle comes before its label, a face after
+    the faces before it.  Inverted boxes (Pillow raises on them) get no rectangle."""
+    if len(boxes) != len(names):
+        raise ValueError("overlay_ops: boxes and names must list the same frames")
+    rgb = (int(colour[0]) & 255) | (int(colour[1]) & 255) << 8 | (int(colour[2]) & 255) << 16
+    ops, masks, at = [], [], 0
+    for f, (bx, nm) in enumerate(zip(boxes, names)):
+        if len(bx) != len(nm):
+            raise ValueError("overlay_ops: frame %d has %d boxes and %d names" % (f, len(bx), len(nm)))
+        for box, name in zip(bx, nm):
+            x0, y0, x1, y1 = (_trunc(v) for v in box[:4])
+            if x1 >= x0 and y1 >= y0:
+                ops.append((RECT, f, x0, y0, x1, y1, 0, rgb))
+            ax, ay = float(box[2]), float(box[1])
+            if not (abs(ax) < _COORD and abs(ay) < _COORD):
+                continue                          # nowhere near a frame
+            (fx, ix), (fy, iy) = math.modf(ax), math.modf(ay)
+            m, ox, oy = _label_mask(str(name), fx, fy)
+            if m is None:
+                continue
+            ops.append((LABEL, f, int(ix) + ox, int(iy) + oy, m.shape[1], m.shape[0], at, rgb))
+            masks.append(m.reshape(-1))
+            at += m.size
+    return (np.array(ops, dtype=OP_DTYPE) if ops else np.zeros((0,), OP_DTYPE),
+            np.concatenate(masks) if masks else np.zeros((0,), np.uint8))
+
+
+def overlay_draw(frames_dev, ops_dev, masks_dev, stream_ptr=None):
+    """vnf_overlay_draw on torch tensors: frames_dev (b,H,W,3) u8 cuda, contiguous, painted in place; ops_dev: the
+    bytes of an OP_DTYPE table on the device; masks_dev: u8 cuda (may be empty)."""
+    if not (frames_dev.is_cuda and ops_dev.is_cuda and masks_dev.is_cuda):
+        raise RuntimeError("jpeg_encode.overlay_draw needs cuda tensors (there is no CPU path)")
+    if frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or not frames_dev.is_contiguous():
+        raise ValueError("overlay_draw: frames_dev must be a contiguous (b,H,W,3) u8 tensor")
+    b, h, w = (int(s) for s in frames_dev.shape[:3])
+    n_ops = ops_dev.numel() * ops_dev.element_size() // OP_DTYPE.itemsize
+    _lib.check(_lib.load().vnf_overlay_draw(
+        frames_dev.data_ptr(), b, h, w, ops_dev.data_ptr(), int(n_ops), masks_dev.data_ptr() if masks_dev.numel() else None,
+        int(masks_dev.numel()), stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+    return frames_dev
+
+
+def draw_boxes_device(frames_dev, boxes, names, stream=None):
+    """draw_boxes_on_image for every frame of a device batch, in place, on `stream` (default: the current one)"""
+    import torch
+    ops, masks = overlay_ops(boxes, names)
+    if ops.shape[0] == 0:
+        return frames_dev
+    stream = stream if stream is not None else torch.cuda.current_stream(frames_dev.device)
+    with torch.cuda.stream(stream):
+        packed = np.concatenate([ops.view(np.uint8), masks])            # one upload; the table first keeps it aligned
+        dev = torch.from_numpy(packed).to(frames_dev.device, non_blocking=False)
+        nb = ops.nbytes
+        overlay_draw(frames_dev, dev[:nb], dev[nb:], ctypes.c_void_p(stream.cuda_stream))
+        dev.record_stream(stream)
+    return frames_dev
+
+
+# the video writer video.run_stream drives --------------------------------------------------------------------------
+
+PART_MAGIC = b"VNFMJPG1"
+
+
+class VideoEncoder:
+    """`encoder` of video.run_stream: draws on a round's own device frames, encodes them and appends them, in frame
+    order, to a Motion-JPEG AVI (one process) or to this rank's spool file `<path>.rank<r>.part` (several; rank 0
+    merges them with `merge` once every rank has closed its own)."""
+
+    def __init__(self, path, fps, device, quality=92, sampling="4:2:0", rank=0, world=1):
+        import torch
+        from .mjpeg_avi import MjpegAviWriter
+        from .streams import side_stream
+        if not str(path).lower().endswith(".avi"):
+            raise ValueError("the device encoder writes a Motion-JPEG AVI: give the video a name ending in .avi, got %r" % (path,))
+        self.path, self.fps, self.rank, self.world = str(path), float(fps), int(rank), int(world)
+        self.device = torch.device(device)
+        self.enc = BatchEncoder(self.device, quality, sampling)
+        self.stream = side_stream(self.device, ENCODE_STREAM_ROLE)
+        self.frames = 0
+        if self.world == 1:
+            self._avi, self._part = MjpegAviWriter(self.path, self.fps), None
+        else:
+            self._avi, self._part = None, open(self.part_path(self.path, self.rank), "wb")
+            self._part.write(PART_MAGIC)
+
+    @staticmethod
+    def part_path(path, rank):
+        return "%s.rank%d.part" % (path, rank)
+
+    def write_batch(self, frames_dev, numbers, boxes, names, after=None):
+        """frames_dev: the batch in HBM, drawn on IN PLACE: the caller hands it over for good -- a buffer nobody reads
+        again, never a caller's own source frames (run_stream passes its upload-ring slot, or a copy) -- and its other
+        readers are done once `after`, an event, has passed.  numbers: the frames' numbers (ascending); boxes / names: per frame.
+        -> the event behind the last kernel that reads frames_dev."""
+        if after is not None:
+            self.stream.wait_event(after)
+        if any(len(n) for n in names):
+            draw_boxes_device(frames_dev, boxes, names, self.stream)
+        job = self.enc.enqueue(frames_dev, self.stream)
+        h, w = int(frames_dev.shape[1]), int(frames_dev.shape[2])
+        for num, data in zip(numbers, self.enc.finish(job)):
+            if self._avi is not None:
+                self._avi.append(data, (w, h))
+            else:
+                self._part.write(struct.pack("<IIII", int(num), len(data), w, h))
+                self._part.write(data)
+            self.frames += 1
+        return job["kernels"]
+
+    def close(self):
+        """finish this process's file.  One process: the AVI (a stream without frames is an error: there is no video to
+        write); several: this rank's spool file, which may be empty."""
+        if self._avi is not None:
+            avi, self._avi = self._avi, None
+            if not len(avi):
+                raise ValueError("no frame reached the video encoder: %r is not written" % (self.path,))
+            avi.close()
+        if self._part is not None:
+            self._part.close()
+            self._part = None
+
+    def abort(self):
+        """give up after an error: close and remove what this process wrote (a half-written AVI, its spool file)"""
+        if self._avi is not None:
+            self._avi.abort()
+            self._avi = None
+        if self._part is not None:
+            self._part.close()
+            self._part = None
+        part = self.part_path(self.path, self.rank)
+        if self.world > 1 and os.path.exists(part):
+            os.remove(part)
+
+    def merge(self, remove=True):
+        """rank 0, after every rank's close(): the spool files -> the AVI, frames in number order"""
+        from .mjpeg_avi import merge_mjpeg_parts
+        parts = [self.part_path(self.path, r) for r in range(self.world)]
+        n = merge_mjpeg_parts(parts, self.path, self.fps)
+        if remove:
+            for p in parts:
+                os.remove(p)
+        return n

@@ -102,7 +102,7 @@ class FrameSource:
 
 
 def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
-               decode="device"):
+               decode="device", encoder=None):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
 
     pipe: FacePipeline-like -- .submit(frames_dev, classify=False[, ready=event]) -> ticket with .result() ->
@@ -116,6 +116,12 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     decoded by jpeg.decode_batch_device: entropy decode on host threads, pixels on the upload stream; a batch it does
     not take is decoded by Pillow and uploaded, as every batch is with decode="host".  The frames are the same bytes
     either way; on_frame receives a jpeg.HostFrame (shape + pixels on demand) for a device-decoded frame.
+    encoder: None, or a jpeg_encode.VideoEncoder-like object (GPU only) that writes the annotated video: every batch's
+    DEVICE frames are then kept until the round's names are known and handed over with
+    .write_batch(frames_dev, numbers, boxes, names, after=event) -> event, in frame order on the rank that owns them;
+    it draws on them in place (frames without faces go through unannotated; a batch that is not a slot of the upload
+    ring -- a source that hands out cuda tensors -- is copied first, the source's frames are never painted).  Like on_frame it makes every rank
+    classify.  The batch's slot of the upload ring is released behind the encoder's event, not the embedding's.
     Returns (rows: {frame_number: csv row}, complete on rank 0; frames processed by this rank)."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     on_gpu = dev.type == "cuda"
@@ -124,10 +130,13 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
         from .streams import side_stream
         from .upload import FrameUploader
         comm = side_stream(dev, 7)          # the collective's stream (roles 0..6 belong to the pipeline, streams.py)
-        uploader = FrameUploader(dev, depth=lag + 3)
+        # with an encoder a batch keeps its device slot one round past its exchange (until consume() has its names)
+        uploader = FrameUploader(dev, depth=lag + 3 + (2 if encoder is not None else 0))
+    elif encoder is not None:
+        raise RuntimeError("run_stream: the video encoder works on frames in device memory (there is no CPU path)")
     cap = int(cap) if cap else max(256, 16 * int(n_frames))
     WIDTH = 517                             # 512 embedding + 4 box + 1 frame slot
-    classify_here = rank == 0 or on_frame is not None
+    classify_here = rank == 0 or on_frame is not None or encoder is not None
     rows, inflight, pending = {}, [], []    # inflight: (round, ticket or None, frames, info); pending: issued exchanges
     state = {"processed": 0, "shape": None}
 
@@ -147,11 +156,11 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     def issue(item):
         """enqueue round `rnd`'s exchange (+ classification of the gathered embeddings) on the side stream, behind
         this batch's own event only; nothing here waits on the host"""
-        rnd, t, q, inf = item
+        rnd, t, q, inf, frames_dev = item
         n, payload = 0, None
         if t is not None:
             counts, boxes, emb, _, _ = t.result()
-            if uploader is not None:
+            if uploader is not None and encoder is None:
                 # the batch's frames were last read by its warp, which precedes its embedding event (a batch without
                 # faces: by its detection, whose read-back the host has already waited for)
                 uploader.release(getattr(t, "upload_slot", -1), getattr(t, "event", None))
@@ -161,6 +170,13 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
                 extra = np.concatenate([np.asarray(boxes, np.float32).reshape(n, 4), slot[:, None]], axis=1)
                 payload = torch.cat([emb.to(dev).float(), torch.from_numpy(extra).to(dev, non_blocking=True)], dim=1)
         rec = {"rnd": rnd, "q": q, "inf": inf, "own": t is not None, "n": n, "spill": None, "hdr": None}
+        if encoder is not None and t is not None:
+            # the frames stay with the round: the encoder draws on them once the detector and the warp are done with
+            # them (the ticket's embedding event; a batch without faces: the detection the host has waited for)
+            # A batch outside the upload ring (slot -1) may be the source's own tensor -- FrameUploader.upload returns a
+            # cuda tensor it is handed as it is --, and the overlay paints in place: the encoder then gets a copy.
+            slot = getattr(t, "upload_slot", -1)
+            rec["video"] = (frames_dev if slot is not None and slot >= 0 else frames_dev.clone(), slot, getattr(t, "event", None))
         if comm is not None:
             comm.wait_stream(torch.cuda.current_stream(dev))
         with (torch.cuda.stream(comm) if comm is not None else _null()):
@@ -233,13 +249,20 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             nm, bx, sl = names[o:o + k], ex[:, 0:4], ex[:, 4].astype(np.int64)
             o += k
             if r == rank and rec["own"]:                      # my own frames: pixels, times and numbers are here
+                b_names, b_boxes = [], []
                 for i, (tm, num) in enumerate(inf):
                     sel = np.nonzero(sl == i)[0]
                     f_names, f_boxes = [nm[j] for j in sel], [bx[j] for j in sel]
+                    b_names.append(f_names)
+                    b_boxes.append(f_boxes)
                     if on_frame is not None:
                         on_frame(q[i], num, f_names, f_boxes)
                     if rank == 0:
                         rows[num] = tracker_row(tm, num, f_names, f_boxes, q[i].shape)
+                if encoder is not None:
+                    frames_dev, slot, after = rec.pop("video")
+                    done = encoder.write_batch(frames_dev, [num for _, num in inf], b_boxes, b_names, after=after)
+                    uploader.release(slot, done)
             elif rank == 0:                                   # another rank's frames: number and time follow from the batch index
                 for i in np.unique(sl):
                     sel = np.nonzero(sl == i)[0]
@@ -289,7 +312,7 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
         else:
             frames_dev, _ = pipe.detector._to_device_frames(q)
             ticket = pipe.submit(frames_dev, classify=False)
-        inflight.append((b // world, ticket, q, inf))
+        inflight.append((b // world, ticket, q, inf, frames_dev))
         rounds = b // world + 1
         state["processed"] += len(q)
         if log is not None:
@@ -303,7 +326,7 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     total_batches = (total_frames + n_frames - 1) // n_frames
     total_rounds = (total_batches + world - 1) // world
     for rnd in range(rounds, total_rounds):
-        inflight.append((rnd, None, None, None))
+        inflight.append((rnd, None, None, None, None))
     if hasattr(pipe, "flush"):
         pipe.flush()
     while inflight:
