@@ -238,11 +238,12 @@ int vnf_mlp_trainer_create(const vnf_tensor_desc* weights, int n_weights, int in
 int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t* target, int b,
                        const float* dropout_mask, float lr, int train, float* loss_out,
                        int32_t* hits_out, void* stream);
-/* checkpoint access (trainer/base_trainer.py:83-105): name = a state_dict key, kind 0 = parameter,
- * 1 = Adam exp_avg, 2 = Adam exp_avg_sq; host fp32 arrays of exactly numel elements.  Synchronise. */
-int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
-int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
-int vnf_mlp_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
+/* checkpoint access of either trainer handle (trainer/base_trainer.py:83-105): name = a state_dict key of what the handle
+ * trains (the four of MLPModel; logits.weight | logits.bias), kind 0 = parameter, 1 = Adam exp_avg, 2 = Adam exp_avg_sq;
+ * host fp32 arrays of exactly numel elements.  Synchronise. */
+int vnf_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
+int vnf_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
+int vnf_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
 
 /* training of a frozen encoder's `logits` layer ---------------------------- */
 /* One optimisation step of trainer/classification_trainer.py:13-21 for nn.Linear(512, num_classes) + log_softmax on
@@ -258,11 +259,6 @@ int vnf_head_trainer_create(const vnf_tensor_desc* weights, int n_weights, int n
  * Bitwise repeatable.  b > max_batch: VNF_E_CAPACITY.  Enqueued on `stream`, no synchronisation. */
 int vnf_head_train_step(vnf_handle h, const float* feat, const int64_t* target, int b, float lr, int train,
                         float* loss_out, int32_t* hits_out, void* stream);
-/* checkpoint access, as vnf_mlp_trainer_*: name = logits.weight | logits.bias, kind 0 = parameter, 1 = Adam exp_avg,
- * 2 = Adam exp_avg_sq; host fp32 arrays of exactly numel elements.  Synchronise. */
-int vnf_head_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel);
-int vnf_head_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel);
-int vnf_head_trainer_step_count(vnf_handle h, int64_t* step_io, int set);  /* Adam's step counter */
 
 /* training-time augmentation --------------------------------------------- */
 /* transforms_facenet_aug (data_loader/__init__.py:58-65) for the images VNCelebDataset serves

@@ -87,16 +87,13 @@ SIGNATURES = {
     "vnf_mlp_trainer_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                    ctypes.c_float, ctypes.POINTER(_P)]),
     "vnf_mlp_train_step": (_I, [_P, _P, _P, _I, _P, ctypes.c_float, _I, _P, _P, _P]),
-    "vnf_mlp_trainer_get": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
-    "vnf_mlp_trainer_set": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
-    "vnf_mlp_trainer_step_count": (_I, [_P, ctypes.POINTER(ctypes.c_int64), _I]),
+    "vnf_trainer_get": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
+    "vnf_trainer_set": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
+    "vnf_trainer_step_count": (_I, [_P, ctypes.POINTER(ctypes.c_int64), _I]),
     "vnf_encoder_features": (_I, [_P, _P, _I, _I, _P, _P]),
     "vnf_head_trainer_create": (_I, [ctypes.POINTER(TensorDesc), _I, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.POINTER(_P)]),
     "vnf_head_train_step": (_I, [_P, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P]),
-    "vnf_head_trainer_get": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
-    "vnf_head_trainer_set": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_int64]),
-    "vnf_head_trainer_step_count": (_I, [_P, ctypes.POINTER(ctypes.c_int64), _I]),
     "vnf_mtcnn_create": (_I, [ctypes.POINTER(TensorDesc), _I, ctypes.POINTER(TensorDesc), _I,
                               ctypes.POINTER(TensorDesc), _I, ctypes.POINTER(MtcnnCfg), ctypes.POINTER(_P)]),
     "vnf_mtcnn_detect": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, ctypes.POINTER(ctypes.c_int32), _P]),

@@ -42,6 +42,16 @@ T* handle_cast(vnf_handle h) {
   return (b && b->kind == T::KIND) ? static_cast<T*>(b) : nullptr;
 }
 
+// The handle as T, the common base of several handle types (it names their kinds as T::KINDS), or nullptr.
+template <class T>
+T* handle_cast_base(vnf_handle h) {
+  HandleBase* b = reinterpret_cast<HandleBase*>(h);
+  if (b)
+    for (HandleKind k : T::KINDS)
+      if (b->kind == k) return static_cast<T*>(b);
+  return nullptr;
+}
+
 // state_dict lookup -----------------------------------------------------------------------
 struct WeightMap {
   std::unordered_map<std::string, const vnf_tensor_desc*> m;

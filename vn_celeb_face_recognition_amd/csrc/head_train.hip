@@ -12,12 +12,10 @@
 // applies weight decay and Adam to W, exp_avg and exp_avg_sq straight from them.  dz (b,C) and feat (b,512) are both
 // batch-major, which is the k-major form both 16x16x4 operands load in, so nothing is transposed.  No atomics, one fixed
 // summation order: a step is bitwise repeatable.  Tails (b % 4, C % 16, C < 16) are masked in the loads and stores.
-#include <cmath>
-#include <cstring>
+#include <memory>
 #include <string>
 
-#include "engine.h"
-#include "train_rows.h"
+#include "adam_params.h"
 
 namespace vnf {
 
@@ -56,18 +54,6 @@ __global__ void __launch_bounds__(256) head_logits_kernel(const float* __restric
       if (m < Bn) z[(size_t)m * C + c] = acc[r] + bv;
     }
   }
-}
-
-// torch.optim.Adam on one element, in adam_kernel's (mlp_train.hip) operation order
-__device__ __forceinline__ void adam_update(float grad, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, float b1,
-                                            float b2, float eps, float wd, float step_size, float bc2_sqrt) {
-  const float pi = *p;
-  grad = grad + wd * pi;
-  const float mi = *m + (1.f - b1) * (grad - *m);
-  const float vi = *v * b2 + ((1.f - b2) * grad) * grad;
-  *m = mi; *v = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  *p = pi + (-step_size) * (mi / denom);
 }
 
 // dW[c][k] = sum_b dz[b][c] feat[b][k], consumed in registers.  A workgroup owns 16 classes x 128 inputs, a wave 16 x 32
@@ -120,20 +106,15 @@ __global__ void __launch_bounds__(256) head_update_kernel(const float* __restric
   }
 }
 
-struct HeadTrainer : HandleBase {
+// params: logits.weight [C][512], logits.bias [C], no gradients in memory
+struct HeadTrainer : AdamTrainer {
   static constexpr HandleKind KIND = HandleKind::HeadTrainer;
-  HeadTrainer() : HandleBase(KIND) {}
-  int C = 0, max_batch = 0;
-  long long step = 0;
-  float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 0.f;
-  // parameters and Adam moments: logits.weight [C][512], logits.bias [C]
-  float *p[2] = {nullptr, nullptr}, *m[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
-  size_t numel[2] = {0, 0};
-  float *z = nullptr, *dz = nullptr, *loss_rows = nullptr;
-  int* hit_rows = nullptr;
+  HeadTrainer() : AdamTrainer(KIND) {}
+  int C = 0;
+  float *z = nullptr, *dz = nullptr;
 };
 
-static const char* kHeadNames[2] = {"logits.weight", "logits.bias"};
+static const char* const kHeadNames[2] = {"logits.weight", "logits.bias"};
 
 }  // namespace vnf
 using namespace vnf;
@@ -145,39 +126,26 @@ extern "C" int vnf_head_trainer_create(const vnf_tensor_desc* weights, int n_wei
       return fail(VNF_E_INVALID, "vnf_head_trainer_create: bad argument");
     *out = nullptr;
     WeightMap wm(weights, n_weights);
-    HeadTrainer* t = new HeadTrainer();
+    std::unique_ptr<HeadTrainer> t(new HeadTrainer());
     t->C = num_classes; t->max_batch = max_batch;
     t->b1 = beta1; t->b2 = beta2; t->eps = eps; t->wd = weight_decay;
-    (void)hipGetDevice(&t->device);
     const size_t C = num_classes, B = max_batch;
     const size_t ne[2] = {C * HEAD_K, C};
-    for (int i = 0; i < 2; ++i) {
-      t->numel[i] = ne[i];
-      const float* src = wm.get(kHeadNames[i], (int64_t)ne[i]);
-      if (!src) { delete t; return fail(VNF_E_MISSING, "vnf_head_trainer_create: missing weight: " + wm.missing); }
-      t->p[i] = (float*)t->upload(src, ne[i] * 4);
-      t->m[i] = (float*)t->dalloc(ne[i] * 4);
-      t->v[i] = (float*)t->dalloc(ne[i] * 4);
-      if (!t->p[i] || !t->m[i] || !t->v[i]) { delete t; return VNF_E_HIP; }
-      hipError_t me = hipMemset(t->m[i], 0, ne[i] * 4);
-      if (me == hipSuccess) me = hipMemset(t->v[i], 0, ne[i] * 4);
-      if (me != hipSuccess) { delete t; return fail(VNF_E_HIP, std::string("vnf_head_trainer_create: hipMemset: ") + hipGetErrorString(me)); }
-    }
+    if (const int rc = t->init_params(wm, "vnf_head_trainer_create", kHeadNames, ne, 2, false)) return rc;
     t->z = (float*)t->dalloc(B * C * 4);
     t->dz = (float*)t->dalloc(B * C * 4);
-    t->loss_rows = (float*)t->dalloc(B * 4);
-    t->hit_rows = (int*)t->dalloc(B * 4);
-    if (!t->z || !t->dz || !t->loss_rows || !t->hit_rows) { delete t; return VNF_E_HIP; }
+    if (!t->z || !t->dz) return VNF_E_HIP;
     const hipError_t se = hipDeviceSynchronize();
-    if (se != hipSuccess) { delete t; return fail(VNF_E_HIP, std::string("vnf_head_trainer_create: ") + hipGetErrorString(se)); }
-    *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(t));
+    if (se != hipSuccess) return fail(VNF_E_HIP, std::string("vnf_head_trainer_create: ") + hipGetErrorString(se));
+    *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(t.release()));
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
   }
 }
 
-// forward (+ loss / hits); train != 0: backward + Adam step with learning rate lr.
+// forward (+ loss / hits); train != 0: backward + Adam step with learning rate lr.  Checkpoint access: vnf_trainer_get /
+// _set / _step_count (mlp_train.hip).
 extern "C" int vnf_head_train_step(vnf_handle h, const float* feat, const int64_t* target, int b, float lr, int train, float* loss_out,
                                    int32_t* hits_out, void* stream) {
   try {
@@ -187,59 +155,17 @@ extern "C" int vnf_head_train_step(vnf_handle h, const float* feat, const int64_
     if (!feat || !target) return fail(VNF_E_INVALID, "vnf_head_train_step: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int C = t->C;
-    hipLaunchKernelGGL(head_logits_kernel, dim3((C + 63) / 64, (b + 15) / 16), dim3(256), 0, s, feat, t->p[0], t->p[1], t->z, b, C);
-    hipLaunchKernelGGL(softmax_nll_kernel, dim3((b + 3) / 4), dim3(256), 0, s, t->z, C, b, target, train ? t->dz : nullptr, t->loss_rows,
-                       t->hit_rows, 1.f / (float)b);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, s, t->loss_rows, t->hit_rows, b, loss_out, hits_out);
-    VNF_HIP(hipGetLastError());
+    const AdamParam &W = t->params[0], &B = t->params[1];
+    hipLaunchKernelGGL(head_logits_kernel, dim3((C + 63) / 64, (b + 15) / 16), dim3(256), 0, s, feat, W.p, B.p, t->z, b, C);
+    VNF_HIP(launch_loss_rows(*t, t->z, C, b, target, train ? t->dz : nullptr, loss_out, hits_out, s));
     if (!train) return VNF_OK;
-    t->step += 1;
-    const double bc1 = 1.0 - std::pow((double)t->b1, (double)t->step), bc2 = 1.0 - std::pow((double)t->b2, (double)t->step);
-    const float step_size = (float)((double)lr / bc1), bc2s = (float)std::sqrt(bc2);
-    hipLaunchKernelGGL(head_update_kernel, dim3(HEAD_K / 128, (C + 15) / 16), dim3(256), 0, s, t->dz, feat, b, C, t->p[0], t->m[0], t->v[0],
-                       t->p[1], t->m[1], t->v[1], t->b1, t->b2, t->eps, t->wd, step_size, bc2s);
+    float step_size, bc2s;
+    t->begin_step(lr, &step_size, &bc2s);
+    hipLaunchKernelGGL(head_update_kernel, dim3(HEAD_K / 128, (C + 15) / 16), dim3(256), 0, s, t->dz, feat, b, C, W.p, W.m, W.v, B.p, B.m, B.v,
+                       t->b1, t->b2, t->eps, t->wd, step_size, bc2s);
     VNF_HIP(hipGetLastError());
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
   }
-}
-
-// kind: 0 parameter, 1 Adam exp_avg, 2 Adam exp_avg_sq; name: logits.weight or logits.bias.  Synchronous copies.
-static float* head_buf(HeadTrainer* t, const char* name, int kind, size_t* numel) {
-  for (int i = 0; i < 2; ++i)
-    if (name && !strcmp(name, kHeadNames[i])) {
-      *numel = t->numel[i];
-      return kind == 0 ? t->p[i] : kind == 1 ? t->m[i] : kind == 2 ? t->v[i] : nullptr;
-    }
-  return nullptr;
-}
-
-extern "C" int vnf_head_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel) {
-  HeadTrainer* t = handle_cast<HeadTrainer>(h);
-  if (!t) return fail(VNF_E_INVALID, "not a head trainer handle");
-  size_t n = 0;
-  float* src = head_buf(t, name, kind, &n);
-  if (!src || !host_out || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_head_trainer_get: unknown tensor or size mismatch");
-  VNF_HIP(hipDeviceSynchronize());
-  VNF_HIP(hipMemcpy(host_out, src, n * 4, hipMemcpyDeviceToHost));
-  return VNF_OK;
-}
-
-extern "C" int vnf_head_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel) {
-  HeadTrainer* t = handle_cast<HeadTrainer>(h);
-  if (!t) return fail(VNF_E_INVALID, "not a head trainer handle");
-  size_t n = 0;
-  float* dst = head_buf(t, name, kind, &n);
-  if (!dst || !host_in || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_head_trainer_set: unknown tensor or size mismatch");
-  VNF_HIP(hipDeviceSynchronize());
-  VNF_HIP(hipMemcpy(dst, host_in, n * 4, hipMemcpyHostToDevice));
-  return VNF_OK;
-}
-
-extern "C" int vnf_head_trainer_step_count(vnf_handle h, int64_t* step_io, int set) {
-  HeadTrainer* t = handle_cast<HeadTrainer>(h);
-  if (!t || !step_io) return fail(VNF_E_INVALID, "not a head trainer handle");
-  if (set) t->step = *step_io; else *step_io = t->step;
-  return VNF_OK;
 }

@@ -12,13 +12,10 @@
 // Every product is one NT GEMM C[M][N] = sum_k A[m][k] B[n][k] (both operands k-contiguous); the three products that
 // are not in that form get their operand transposed by a small tile-transpose kernel first.  Sizes are tiny (batch 64:
 // ~1.2 GFLOP per step), so the kernels are simple 64x64 LDS-tiled MFMA loops with bounds checks, not the inference core.
-#include <cmath>
-#include <cstring>
+#include <memory>
 #include <string>
-#include <vector>
 
-#include "engine.h"
-#include "train_rows.h"
+#include "adam_params.h"
 
 namespace vnf {
 
@@ -112,38 +109,25 @@ __global__ void relu_mask_grad_kernel(float* __restrict__ dh, const float* __res
   dh[i] = v;
 }
 
-// torch.optim.Adam (no amsgrad, coupled weight decay), in the operation order of torch/optim/adam.py _single_tensor_adam:
-//   g = g + wd*p ; m.lerp_(g, 1-b1) ; v = v*b2 + ((1-b2)*g)*g ; p += (-step_size) * (m / (sqrt(v)/bc2_sqrt + eps))
-// step_size = lr / (1 - b1^t) and bc2_sqrt = sqrt(1 - b2^t) are formed on the host in double, as Python does.
+// adam_update (adam_params.h) over a tensor whose gradient is in memory
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
                             float b1, float b2, float eps, float wd, float step_size, float bc2_sqrt) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float grad = g[i] + wd * p[i];
-  const float mi = m[i] + (1.f - b1) * (grad - m[i]);
-  const float vi = v[i] * b2 + ((1.f - b2) * grad) * grad;
-  m[i] = mi; v[i] = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p[i] = p[i] + (-step_size) * (mi / denom);
+  adam_update(g[i], p + i, m + i, v + i, b1, b2, eps, wd, step_size, bc2_sqrt);
 }
 
-struct MlpTrainer : HandleBase {
+// params: W1 [H][D], b1 [H], W2 [C][H], b2 [C], with gradients
+struct MlpTrainer : AdamTrainer {
   static constexpr HandleKind KIND = HandleKind::MlpTrainer;
-  MlpTrainer() : HandleBase(KIND) {}
-  int D = 0, C = 0, H = 2048, max_batch = 0;
-  long long step = 0;
-  float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 0.f;
-  // parameters, gradients, Adam moments: W1 [H][D], b1 [H], W2 [C][H], b2 [C]
-  float *p[4] = {nullptr, nullptr, nullptr, nullptr}, *g[4] = {nullptr, nullptr, nullptr, nullptr};
-  float *m[4] = {nullptr, nullptr, nullptr, nullptr}, *v[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t numel[4] = {0, 0, 0, 0};
+  MlpTrainer() : AdamTrainer(KIND) {}
+  int D = 0, C = 0, H = 2048;
   // activations / scratch
   float *h = nullptr, *pre = nullptr, *z = nullptr, *dz = nullptr, *dh = nullptr, *dzT = nullptr, *hT = nullptr, *dhT = nullptr,
-        *xT = nullptr, *w2T = nullptr, *loss_rows = nullptr;
-  int* hit_rows = nullptr;
+        *xT = nullptr, *w2T = nullptr;
 };
 
-static const char* kParamNames[4] = {"dense_1.weight", "dense_1.bias", "dense_2.weight", "dense_2.bias"};
+static const char* const kParamNames[4] = {"dense_1.weight", "dense_1.bias", "dense_2.weight", "dense_2.bias"};
 
 static hipError_t gemm_nt(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, const float* bias,
                           int relu, const float* mask, float* pre, hipStream_t s) {
@@ -165,36 +149,21 @@ extern "C" int vnf_mlp_trainer_create(const vnf_tensor_desc* weights, int n_weig
     if (!out || !weights || input_dim <= 0 || num_classes <= 0 || max_batch <= 0) return fail(VNF_E_INVALID, "vnf_mlp_trainer_create: bad argument");
     *out = nullptr;
     WeightMap wm(weights, n_weights);
-    MlpTrainer* t = new MlpTrainer();
+    std::unique_ptr<MlpTrainer> t(new MlpTrainer());
     t->D = input_dim; t->C = num_classes; t->max_batch = max_batch;
     t->b1 = beta1; t->b2 = beta2; t->eps = eps; t->wd = weight_decay;
-    (void)hipGetDevice(&t->device);
     const size_t H = t->H, D = input_dim, C = num_classes, B = max_batch;
     const size_t ne[4] = {H * D, H, C * H, C};
-    for (int i = 0; i < 4; ++i) {
-      t->numel[i] = ne[i];
-      const float* src = wm.get(kParamNames[i], (int64_t)ne[i]);
-      if (!src) { delete t; return fail(VNF_E_MISSING, "vnf_mlp_trainer_create: missing weight: " + wm.missing); }
-      t->p[i] = (float*)t->upload(src, ne[i] * 4);
-      t->g[i] = (float*)t->dalloc(ne[i] * 4);
-      t->m[i] = (float*)t->dalloc(ne[i] * 4);
-      t->v[i] = (float*)t->dalloc(ne[i] * 4);
-      if (!t->p[i] || !t->g[i] || !t->m[i] || !t->v[i]) { delete t; return VNF_E_HIP; }
-      hipError_t me = hipMemset(t->m[i], 0, ne[i] * 4);
-      if (me == hipSuccess) me = hipMemset(t->v[i], 0, ne[i] * 4);
-      if (me != hipSuccess) { delete t; return fail(VNF_E_HIP, std::string("vnf_mlp_trainer_create: hipMemset: ") + hipGetErrorString(me)); }
-    }
-    float** bufs[] = {&t->h, &t->pre, &t->z, &t->dz, &t->dh, &t->dzT, &t->hT, &t->dhT, &t->xT, &t->w2T, &t->loss_rows};
-    const size_t sz[] = {B * H, B * H, B * C, B * C, B * H, C * B, H * B, H * B, D * B, H * C, B};
-    for (int i = 0; i < 11; ++i) {
+    if (const int rc = t->init_params(wm, "vnf_mlp_trainer_create", kParamNames, ne, 4, true)) return rc;
+    float** bufs[] = {&t->h, &t->pre, &t->z, &t->dz, &t->dh, &t->dzT, &t->hT, &t->dhT, &t->xT, &t->w2T};
+    const size_t sz[] = {B * H, B * H, B * C, B * C, B * H, C * B, H * B, H * B, D * B, H * C};
+    for (int i = 0; i < 10; ++i) {
       *bufs[i] = (float*)t->dalloc(sz[i] * 4);
-      if (!*bufs[i]) { delete t; return VNF_E_HIP; }
+      if (!*bufs[i]) return VNF_E_HIP;
     }
-    t->hit_rows = (int*)t->dalloc(B * 4);
-    if (!t->hit_rows) { delete t; return VNF_E_HIP; }
     const hipError_t se = hipDeviceSynchronize();
-    if (se != hipSuccess) { delete t; return fail(VNF_E_HIP, std::string("vnf_mlp_trainer_create: ") + hipGetErrorString(se)); }
-    *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(t));
+    if (se != hipSuccess) return fail(VNF_E_HIP, std::string("vnf_mlp_trainer_create: ") + hipGetErrorString(se));
+    *out = reinterpret_cast<vnf_handle>(static_cast<HandleBase*>(t.release()));
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
@@ -211,34 +180,33 @@ extern "C" int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t*
     if (!emb || !target) return fail(VNF_E_INVALID, "vnf_mlp_train_step: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const int D = t->D, C = t->C, H = t->H;
+    const AdamParam &W1 = t->params[0], &B1 = t->params[1], &W2 = t->params[2], &B2 = t->params[3];
     // forward
-    VNF_HIP(gemm_nt(emb, D, t->p[0], D, t->h, H, b, H, D, t->p[1], 1, train ? dropout_mask : nullptr, t->pre, s));
-    VNF_HIP(gemm_nt(t->h, H, t->p[2], H, t->z, C, b, C, H, t->p[3], 0, nullptr, nullptr, s));
-    hipLaunchKernelGGL(softmax_nll_kernel, dim3((b + 3) / 4), dim3(256), 0, s, t->z, C, b, target, train ? t->dz : nullptr, t->loss_rows,
-                       t->hit_rows, 1.f / (float)b);
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3(1), dim3(256), 0, s, t->loss_rows, t->hit_rows, b, loss_out, hits_out);
-    VNF_HIP(hipGetLastError());
+    VNF_HIP(gemm_nt(emb, D, W1.p, D, t->h, H, b, H, D, B1.p, 1, train ? dropout_mask : nullptr, t->pre, s));
+    VNF_HIP(gemm_nt(t->h, H, W2.p, H, t->z, C, b, C, H, B2.p, 0, nullptr, nullptr, s));
+    VNF_HIP(launch_loss_rows(*t, t->z, C, b, target, train ? t->dz : nullptr, loss_out, hits_out, s));
     if (!train) return VNF_OK;
     // backward
     VNF_HIP(transpose(t->dz, b, C, t->dzT, s));                                                   // [C][b]
     VNF_HIP(transpose(t->h, b, H, t->hT, s));                                                     // [H][b]
-    VNF_HIP(gemm_nt(t->dzT, b, t->hT, b, t->g[2], H, C, H, b, nullptr, 0, nullptr, nullptr, s));  // dW2 [C][H]
-    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256), dim3(256), 0, s, t->dz, b, C, t->g[3]);
-    VNF_HIP(transpose(t->p[2], C, H, t->w2T, s));                                                 // [H][C]
+    VNF_HIP(gemm_nt(t->dzT, b, t->hT, b, W2.g, H, C, H, b, nullptr, 0, nullptr, nullptr, s));     // dW2 [C][H]
+    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256), dim3(256), 0, s, t->dz, b, C, B2.g);
+    VNF_HIP(transpose(W2.p, C, H, t->w2T, s));                                                    // [H][C]
     VNF_HIP(gemm_nt(t->dz, C, t->w2T, C, t->dh, H, b, H, C, nullptr, 0, nullptr, nullptr, s));    // dh [b][H]
     const size_t nh = (size_t)b * H;
     hipLaunchKernelGGL(relu_mask_grad_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, t->dh, t->pre, dropout_mask, nh);
     VNF_HIP(transpose(t->dh, b, H, t->dhT, s));                                                   // [H][b]
     VNF_HIP(transpose(emb, b, D, t->xT, s));                                                      // [D][b]
-    VNF_HIP(gemm_nt(t->dhT, b, t->xT, b, t->g[0], D, H, D, b, nullptr, 0, nullptr, nullptr, s));  // dW1 [H][D]
-    hipLaunchKernelGGL(colsum_kernel, dim3((H + 255) / 256), dim3(256), 0, s, t->dh, b, H, t->g[1]);
+    VNF_HIP(gemm_nt(t->dhT, b, t->xT, b, W1.g, D, H, D, b, nullptr, 0, nullptr, nullptr, s));     // dW1 [H][D]
+    hipLaunchKernelGGL(colsum_kernel, dim3((H + 255) / 256), dim3(256), 0, s, t->dh, b, H, B1.g);
     // Adam
-    t->step += 1;
-    const double bc1 = 1.0 - std::pow((double)t->b1, (double)t->step), bc2 = 1.0 - std::pow((double)t->b2, (double)t->step);
-    const float step_size = (float)((double)lr / bc1), bc2s = (float)std::sqrt(bc2);
-    for (int i = 0; i < 4; ++i)
-      hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((t->numel[i] + 255) / 256)), dim3(256), 0, s, t->p[i], t->g[i], t->m[i], t->v[i],
-                         t->numel[i], t->b1, t->b2, t->eps, t->wd, step_size, bc2s);
+    float step_size, bc2s;
+    t->begin_step(lr, &step_size, &bc2s);
+    for (int i = 0; i < t->n_params; ++i) {
+      const AdamParam& a = t->params[i];
+      hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((a.numel + 255) / 256)), dim3(256), 0, s, a.p, a.g, a.m, a.v, a.numel, t->b1, t->b2,
+                         t->eps, t->wd, step_size, bc2s);
+    }
     VNF_HIP(hipGetLastError());
     return VNF_OK;
   } catch (const std::exception& ex) {
@@ -246,41 +214,33 @@ extern "C" int vnf_mlp_train_step(vnf_handle h, const float* emb, const int64_t*
   }
 }
 
-// kind: 0 parameter, 1 Adam exp_avg, 2 Adam exp_avg_sq; name: one of the four state_dict keys.  Synchronous copies.
-static float* trainer_buf(MlpTrainer* t, const char* name, int kind, size_t* numel) {
-  for (int i = 0; i < 4; ++i)
-    if (name && !strcmp(name, kParamNames[i])) {
-      *numel = t->numel[i];
-      return kind == 0 ? t->p[i] : kind == 1 ? t->m[i] : kind == 2 ? t->v[i] : nullptr;
-    }
-  return nullptr;
-}
-
-extern "C" int vnf_mlp_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel) {
-  MlpTrainer* t = handle_cast<MlpTrainer>(h);
-  if (!t) return fail(VNF_E_INVALID, "not an MLP trainer handle");
+// Checkpoint access of either trainer kind.  kind: 0 parameter, 1 Adam exp_avg, 2 Adam exp_avg_sq; name: one of the
+// handle's state_dict keys.  Synchronous copies.
+extern "C" int vnf_trainer_get(vnf_handle h, const char* name, int kind, float* host_out, int64_t numel) {
+  AdamTrainer* t = handle_cast_base<AdamTrainer>(h);
+  if (!t) return fail(VNF_E_INVALID, "not a trainer handle");
   size_t n = 0;
-  float* src = trainer_buf(t, name, kind, &n);
-  if (!src || !host_out || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_mlp_trainer_get: unknown tensor or size mismatch");
+  float* src = t->find(name, kind, &n);
+  if (!src || !host_out || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_trainer_get: unknown tensor or size mismatch");
   VNF_HIP(hipDeviceSynchronize());
   VNF_HIP(hipMemcpy(host_out, src, n * 4, hipMemcpyDeviceToHost));
   return VNF_OK;
 }
 
-extern "C" int vnf_mlp_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel) {
-  MlpTrainer* t = handle_cast<MlpTrainer>(h);
-  if (!t) return fail(VNF_E_INVALID, "not an MLP trainer handle");
+extern "C" int vnf_trainer_set(vnf_handle h, const char* name, int kind, const float* host_in, int64_t numel) {
+  AdamTrainer* t = handle_cast_base<AdamTrainer>(h);
+  if (!t) return fail(VNF_E_INVALID, "not a trainer handle");
   size_t n = 0;
-  float* dst = trainer_buf(t, name, kind, &n);
-  if (!dst || !host_in || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_mlp_trainer_set: unknown tensor or size mismatch");
+  float* dst = t->find(name, kind, &n);
+  if (!dst || !host_in || (int64_t)n != numel) return fail(VNF_E_INVALID, "vnf_trainer_set: unknown tensor or size mismatch");
   VNF_HIP(hipDeviceSynchronize());
   VNF_HIP(hipMemcpy(dst, host_in, n * 4, hipMemcpyHostToDevice));
   return VNF_OK;
 }
 
-extern "C" int vnf_mlp_trainer_step_count(vnf_handle h, int64_t* step_io, int set) {
-  MlpTrainer* t = handle_cast<MlpTrainer>(h);
-  if (!t || !step_io) return fail(VNF_E_INVALID, "not an MLP trainer handle");
+extern "C" int vnf_trainer_step_count(vnf_handle h, int64_t* step_io, int set) {
+  AdamTrainer* t = handle_cast_base<AdamTrainer>(h);
+  if (!t || !step_io) return fail(VNF_E_INVALID, "not a trainer handle");
   if (set) t->step = *step_io; else *step_io = t->step;
   return VNF_OK;
 }

@@ -119,30 +119,47 @@ class VNCelebDataset(torch.utils.data.Dataset):
         return self._dev
 
 
-class TrainableMLP:
-    """MLPModel(input_dim, num_classes) + its Adam state, resident on the GPU (vnf_mlp_trainer_*).  Initial weights are
-    drawn exactly as `nn.Linear(input_dim, 2048); nn.Linear(2048, num_classes)` draws them (same generator calls)."""
+def _check_labels(target, num_classes):
+    """torch's nll_loss raises on a label outside [0, C) (trainer/classification_trainer.py:22 F.nll_loss): so does this,
+    before any launch.  Returns the labels as an int64 host tensor."""
+    th = torch.as_tensor(target).to(dtype=torch.int64)
+    if th.numel() and (int(th.min()) < 0 or int(th.max()) >= num_classes):
+        raise IndexError("Target %d is out of bounds." % int(th.max() if int(th.max()) >= num_classes else th.min()))
+    return th
 
-    def __init__(self, input_dim, num_classes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_batch=1024,
-                 device="cuda:0"):
-        self.input_dim, self.num_classes, self.max_batch = int(input_dim), int(num_classes), int(max_batch)
+
+def _rows(ds, data):
+    """What a loader over `ds` yields as `data` (the sampler's indices) -> int64 host tensor; an index outside `ds` raises."""
+    index = torch.as_tensor(data, dtype=torch.int64)
+    if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
+        raise IndexError("sample index outside the data set")
+    return index
+
+
+class _AdamTrained:
+    """What TrainableMLP and TrainableHead share: a library handle that owns a set of Adam-trained tensors
+    (csrc/adam_params.h), its mode, checkpoint access (vnf_trainer_*) and torch.optim.Adam's state_dict layout.  A
+    subclass names its tensors: _shapes (state_dict key -> shape), _slots ((index in the Adam group, key), ...) and
+    _n_group_params (the size of that group)."""
+
+    def __init__(self, device, lr, betas, eps, weight_decay, max_batch):
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
+        self.max_batch = int(max_batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("training runs on MI355X only (there is no CPU path)")
         self.training = True
-        d1, d2 = torch.nn.Linear(self.input_dim, 2048), torch.nn.Linear(2048, self.num_classes)
-        sd = OrderedDict([("dense_1.weight", d1.weight), ("dense_1.bias", d1.bias), ("dense_2.weight", d2.weight),
-                          ("dense_2.bias", d2.bias)])
-        self._shapes = {k: tuple(v.shape) for k, v in sd.items()}
+
+    def _create(self, fn, state_dict, *args):
+        """The handle: library function `fn`(initial values of `state_dict`, *args, max_batch, Adam's constants)."""
         lib = _lib.load()
         dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev):
             _lib.check(lib.vnf_init(dev))
-            descs, n, keep = _lib.make_descs(OrderedDict((k, v.detach()) for k, v in sd.items()))
+            descs, n, keep = _lib.make_descs(state_dict)
             h = ctypes.c_void_p()
-            _lib.check(lib.vnf_mlp_trainer_create(descs, n, self.input_dim, self.num_classes, self.max_batch, self.betas[0],
-                                                  self.betas[1], self.eps, self.weight_decay, ctypes.byref(h)))
+            _lib.check(getattr(lib, fn)(descs, n, *args, self.max_batch, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                        ctypes.byref(h)))
             del keep
         self._h = h
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -166,38 +183,82 @@ class TrainableMLP:
     def to(self, device):
         return self
 
-    def step(self, data, target, train):
-        """One batch: forward + loss (+ backward + Adam when train).  Returns (mean NLL, correct count).  In training
-        mode the dropout factors of F.dropout(x, 0.5) are drawn from torch's CPU generator, as the reference's forward
-        on a CPU tensor would draw them (models/mlp_model.py:12)."""
-        b = int(data.shape[0])
-        x = data.to(self.device, dtype=torch.float32).contiguous()
-        th = torch.as_tensor(target).to(dtype=torch.int64)
-        if th.numel() and (int(th.min()) < 0 or int(th.max()) >= self.num_classes):
-            # torch's nll_loss raises on such a label (trainer/classification_trainer.py:22 F.nll_loss)
-            raise IndexError("Target %d is out of bounds." % int(th.max() if int(th.max()) >= self.num_classes else th.min()))
-        t = th.to(self.device).contiguous()
-        mask = None
-        if train:
-            mask = (torch.empty((b, 2048), dtype=torch.float32).bernoulli_(0.5) / 0.5).to(self.device)
+    def _run(self, fn, x, t, b, *extra):
+        """Library function `fn`(handle, x, t, b, *extra, loss, hits, stream) -> (mean NLL, correct count)."""
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().vnf_mlp_train_step(
-                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()), b,
-                ctypes.c_void_p(mask.data_ptr()) if mask is not None else None, self.lr, 1 if train else 0,
+            _lib.check(getattr(_lib.load(), fn)(
+                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()), b, *extra,
                 ctypes.c_void_p(self._loss.data_ptr()), ctypes.c_void_p(self._hits.data_ptr()), _lib.current_stream_ptr()))
         return float(self._loss.item()), int(self._hits.item())
 
     # ---- checkpoint access
     def _get(self, name, kind):
         a = np.empty(self._shapes[name], dtype=np.float32)
-        _lib.check(_lib.load().vnf_mlp_trainer_get(self._h, name.encode(), kind, a.ctypes.data, a.size))
+        _lib.check(_lib.load().vnf_trainer_get(self._h, name.encode(), kind, a.ctypes.data, a.size))
         return torch.from_numpy(a)
 
     def _set(self, name, kind, value):
         a = np.ascontiguousarray(torch.as_tensor(value).detach().cpu().float().numpy())
         if a.shape != self._shapes[name]:
             raise RuntimeError("size mismatch for %s: %s vs %s" % (name, a.shape, self._shapes[name]))
-        _lib.check(_lib.load().vnf_mlp_trainer_set(self._h, name.encode(), kind, a.ctypes.data, a.size))
+        _lib.check(_lib.load().vnf_trainer_set(self._h, name.encode(), kind, a.ctypes.data, a.size))
+
+    def _step_count(self, value=None):
+        c = ctypes.c_int64(0 if value is None else int(value))
+        _lib.check(_lib.load().vnf_trainer_step_count(self._h, ctypes.byref(c), 0 if value is None else 1))
+        return int(c.value)
+
+    def optimizer_state_dict(self):
+        """torch.optim.Adam.state_dict() layout over the reference's `Adam(model.parameters())` group, so the reference's
+        resume_checkpoint (base_trainer.py:73-80) can load it into a torch Adam and vice versa.  MLPModel: params 0..3 in
+        state_dict order.  A frozen encoder: every parameter of the module is in the group, only the two of `logits` ever
+        got a gradient and therefore a state entry."""
+        step = float(self._step_count())
+        state = {i: {"step": torch.tensor(step), "exp_avg": self._get(k, 1), "exp_avg_sq": self._get(k, 2)}
+                 for i, k in self._slots} if step > 0 else {}
+        group = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps,
+                                 weight_decay=self.weight_decay).state_dict()["param_groups"][0]
+        group["params"] = list(range(self._n_group_params))
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, osd):
+        g = osd["param_groups"][0]
+        self.lr = float(g["lr"])
+        if osd["state"]:
+            for i, k in self._slots:
+                self._set(k, 1, osd["state"][i]["exp_avg"])
+                self._set(k, 2, osd["state"][i]["exp_avg_sq"])
+            self._step_count(int(float(osd["state"][self._slots[0][0]]["step"])))
+
+
+class TrainableMLP(_AdamTrained):
+    """MLPModel(input_dim, num_classes) + its Adam state, resident on the GPU (vnf_mlp_trainer_create, vnf_mlp_train_step).
+    Initial weights are drawn exactly as `nn.Linear(input_dim, 2048); nn.Linear(2048, num_classes)` draws them (same
+    generator calls)."""
+
+    def __init__(self, input_dim, num_classes, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_batch=1024,
+                 device="cuda:0"):
+        self.input_dim, self.num_classes = int(input_dim), int(num_classes)
+        super().__init__(device, lr, betas, eps, weight_decay, max_batch)
+        d1, d2 = torch.nn.Linear(self.input_dim, 2048), torch.nn.Linear(2048, self.num_classes)
+        sd = OrderedDict([("dense_1.weight", d1.weight), ("dense_1.bias", d1.bias), ("dense_2.weight", d2.weight),
+                          ("dense_2.bias", d2.bias)])
+        self._shapes = {k: tuple(v.shape) for k, v in sd.items()}
+        self._slots, self._n_group_params = tuple(enumerate(PARAMS)), len(PARAMS)
+        self._create("vnf_mlp_trainer_create", OrderedDict((k, v.detach()) for k, v in sd.items()), self.input_dim, self.num_classes)
+
+    def step(self, data, target, train):
+        """One batch: forward + loss (+ backward + Adam when train).  Returns (mean NLL, correct count).  In training
+        mode the dropout factors of F.dropout(x, 0.5) are drawn from torch's CPU generator, as the reference's forward
+        on a CPU tensor would draw them (models/mlp_model.py:12)."""
+        b = int(data.shape[0])
+        x = data.to(self.device, dtype=torch.float32).contiguous()
+        t = _check_labels(target, self.num_classes).to(self.device).contiguous()
+        mask = None
+        if train:
+            mask = (torch.empty((b, 2048), dtype=torch.float32).bernoulli_(0.5) / 0.5).to(self.device)
+        return self._run("vnf_mlp_train_step", x, t, b, ctypes.c_void_p(mask.data_ptr()) if mask is not None else None, self.lr,
+                         1 if train else 0)
 
     def state_dict(self):
         return OrderedDict((k, self._get(k, 0)) for k in PARAMS)
@@ -208,40 +269,6 @@ class TrainableMLP:
                 raise RuntimeError("Missing key(s) in state_dict: %s" % k)
             self._set(k, 0, sd[k])
 
-    def _step_count(self, value=None):
-        c = ctypes.c_int64(0 if value is None else int(value))
-        _lib.check(_lib.load().vnf_mlp_trainer_step_count(self._h, ctypes.byref(c), 0 if value is None else 1))
-        return int(c.value)
-
-    def optimizer_state_dict(self):
-        """torch.optim.Adam.state_dict() layout (params 0..3 in state_dict order), so the reference's
-        resume_checkpoint (base_trainer.py:73-80) can load it into a torch Adam and vice versa."""
-        step = float(self._step_count())
-        state = {i: {"step": torch.tensor(step), "exp_avg": self._get(k, 1), "exp_avg_sq": self._get(k, 2)}
-                 for i, k in enumerate(PARAMS)} if step > 0 else {}
-        group = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps,
-                                 weight_decay=self.weight_decay).state_dict()["param_groups"][0]
-        group["params"] = list(range(len(PARAMS)))
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, osd):
-        g = osd["param_groups"][0]
-        self.lr = float(g["lr"])
-        if osd["state"]:
-            for i, k in enumerate(PARAMS):
-                self._set(k, 1, osd["state"][i]["exp_avg"])
-                self._set(k, 2, osd["state"][i]["exp_avg_sq"])
-            self._step_count(int(float(osd["state"][0]["step"])))
-
-
-def _check_labels(target, num_classes):
-    """torch's nll_loss raises on a label outside [0, C) (trainer/classification_trainer.py:22 F.nll_loss): so does this,
-    before any launch.  Returns the labels as an int64 host tensor."""
-    th = torch.as_tensor(target).to(dtype=torch.int64)
-    if th.numel() and (int(th.min()) < 0 or int(th.max()) >= num_classes):
-        raise IndexError("Target %d is out of bounds." % int(th.max() if int(th.max()) >= num_classes else th.min()))
-    return th
-
 
 def head_param_layout(spec):
     """(P, index of logits.weight, index of logits.bias) in `Adam(model.parameters())` of the reference module whose
@@ -251,58 +278,29 @@ def head_param_layout(spec):
     return len(params), params.index(HEAD_PARAMS[0]), params.index(HEAD_PARAMS[1])
 
 
-class TrainableHead:
-    """The `logits` layer of a frozen encoder + its Adam state, resident on the GPU (vnf_head_trainer_*): the
+class TrainableHead(_AdamTrained):
+    """The `logits` layer of a frozen encoder + its Adam state, resident on the GPU (vnf_head_trainer_create, vnf_head_train_step): the
     counterpart of TrainableMLP for iresnet100(n_classes=..., freeze_weights=True) / InceptionResnetV1(classify=True,
     freeze_weights=True).  The encoder only ever runs forward, in eval mode; the initial head is the encoder's own."""
 
     def __init__(self, encoder, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_batch=1024):
         if encoder.head_classes is None:
             raise RuntimeError("%s was built without a classification head (classify=True / n_classes)" % type(encoder).__name__)
-        self.encoder, self.num_classes, self.max_batch = encoder, int(encoder.head_classes), int(max_batch)
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
-        self.device = torch.device(encoder.device)
-        if self.device.type != "cuda":
-            raise RuntimeError("training runs on MI355X only (there is no CPU path)")
+        self.encoder, self.num_classes = encoder, int(encoder.head_classes)
+        super().__init__(encoder.device, lr, betas, eps, weight_decay, max_batch)
         self.encoder.eval()
         self.arch_name = encoder.arch_name
         self.input_size = encoder.input_size
         self.x_dtype = _X_DTYPES.get(encoder.compute_dtype, torch.float32)
         self.n_params, self._iw, self._ib = head_param_layout(encoder._spec())
         self._shapes = {HEAD_PARAMS[0]: (self.num_classes, 512), HEAD_PARAMS[1]: (self.num_classes,)}
-        self.training = True
+        self._slots, self._n_group_params = ((self._iw, HEAD_PARAMS[0]), (self._ib, HEAD_PARAMS[1])), self.n_params
         esd = encoder.state_dict()
-        lib = _lib.load()
-        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(dev):
-            _lib.check(lib.vnf_init(dev))
-            descs, n, keep = _lib.make_descs(OrderedDict((k, esd[k]) for k in HEAD_PARAMS))
-            h = ctypes.c_void_p()
-            _lib.check(lib.vnf_head_trainer_create(descs, n, self.num_classes, self.max_batch, self.betas[0], self.betas[1],
-                                                   self.eps, self.weight_decay, ctypes.byref(h)))
-            del keep
-        self._h = h
-        self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                _lib.load().vnf_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._create("vnf_head_trainer_create", OrderedDict((k, esd[k]) for k in HEAD_PARAMS), self.num_classes)
 
     def train(self, mode=True):
         """The head's mode.  The backbone stays in eval mode whatever this says: frozen means frozen."""
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def to(self, device):
-        return self
+        return super().train(mode)
 
     def features(self, x):
         """(N,3,S,S) cuda -> (N,512) fp32 cuda: what the head reads (encoders._Encoder.features)."""
@@ -318,24 +316,7 @@ class TrainableHead:
         if th.numel() != b:
             raise ValueError("%d targets for a batch of %d" % (th.numel(), b))
         x = features.to(self.device, dtype=torch.float32).contiguous()
-        t = th.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().vnf_head_train_step(
-                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()), b, self.lr, 1 if train else 0,
-                ctypes.c_void_p(self._loss.data_ptr()), ctypes.c_void_p(self._hits.data_ptr()), _lib.current_stream_ptr()))
-        return float(self._loss.item()), int(self._hits.item())
-
-    # ---- checkpoint access
-    def _get(self, name, kind):
-        a = np.empty(self._shapes[name], dtype=np.float32)
-        _lib.check(_lib.load().vnf_head_trainer_get(self._h, name.encode(), kind, a.ctypes.data, a.size))
-        return torch.from_numpy(a)
-
-    def _set(self, name, kind, value):
-        a = np.ascontiguousarray(torch.as_tensor(value).detach().cpu().float().numpy())
-        if a.shape != self._shapes[name]:
-            raise RuntimeError("size mismatch for %s: %s vs %s" % (name, a.shape, self._shapes[name]))
-        _lib.check(_lib.load().vnf_head_trainer_set(self._h, name.encode(), kind, a.ctypes.data, a.size))
+        return self._run("vnf_head_train_step", x, th.to(self.device).contiguous(), b, self.lr, 1 if train else 0)
 
     def state_dict(self):
         """The encoder's full state_dict with `logits.*` replaced by the trained values."""
@@ -349,31 +330,6 @@ class TrainableHead:
         self.encoder.load_state_dict(sd)
         for k in HEAD_PARAMS:
             self._set(k, 0, sd[k])
-
-    def _step_count(self, value=None):
-        c = ctypes.c_int64(0 if value is None else int(value))
-        _lib.check(_lib.load().vnf_head_trainer_step_count(self._h, ctypes.byref(c), 0 if value is None else 1))
-        return int(c.value)
-
-    def optimizer_state_dict(self):
-        """state_dict() of the reference's Adam(model.parameters()) after freeze_weights: every parameter of the module
-        is in the group, only the two of `logits` ever got a gradient and therefore a state entry."""
-        step = float(self._step_count())
-        state = {i: {"step": torch.tensor(step), "exp_avg": self._get(k, 1), "exp_avg_sq": self._get(k, 2)}
-                 for i, k in zip((self._iw, self._ib), HEAD_PARAMS)} if step > 0 else {}
-        group = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps,
-                                 weight_decay=self.weight_decay).state_dict()["param_groups"][0]
-        group["params"] = list(range(self.n_params))
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, osd):
-        g = osd["param_groups"][0]
-        self.lr = float(g["lr"])
-        if osd["state"]:
-            for i, k in zip((self._iw, self._ib), HEAD_PARAMS):
-                self._set(k, 1, osd["state"][i]["exp_avg"])
-                self._set(k, 2, osd["state"][i]["exp_avg_sq"])
-            self._step_count(int(float(osd["state"][self._iw]["step"])))
 
 
 class EvalModel:
@@ -514,7 +470,7 @@ class ClassificationTrainer:
         self.logger = logging.getLogger("trainer")
         self.do_val, self.val_step = tc["do_validation"], tc["validation_step"]
         self.mnt_best = float("inf") if self.mode_monitor == "min" else -float("inf")
-        self._kept = {}    # TrainableHead: features of a whole data set under the default transform, by `train`
+        self._kept = {}    # _kept_rows: the frozen encoder's output for a whole data set under the default transform, by `train`
         if tc["resume_path"] != "":
             self.resume_checkpoint(tc["resume_path"])
 
@@ -524,9 +480,7 @@ class ClassificationTrainer:
     def _images(self, ds, data, transform):
         """Rows `data` of the resident image set through `transform`, as the model's input tensor."""
         from . import augment
-        index = torch.as_tensor(data, dtype=torch.int64)
-        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
-            raise IndexError("sample index outside the data set")
+        index = _rows(ds, data)
         t = getattr(self.model, "input_size", None)
         if t is None:
             raise NotImplementedError("VNCelebDataset under ClassificationTrainer needs a model that takes images")
@@ -544,14 +498,16 @@ class ClassificationTrainer:
         name = (tf.get("name") if isinstance(tf, dict) else tf) if train else "default"
         if name != "default":
             return self.model.features(self._images(ds, data, name))
-        if train not in self._kept:
-            bs = self.model.encoder.max_batch
-            self._kept[train] = torch.cat([self.model.features(self._images(ds, torch.arange(i, min(i + bs, len(ds))), "default"))
-                                           for i in range(0, len(ds), bs)]) if len(ds) else torch.zeros((0, 512), device=self.model.device)
-        index = torch.as_tensor(data, dtype=torch.int64)
-        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(ds)):
-            raise IndexError("sample index outside the data set")
-        return self._kept[train][index.to(self._kept[train].device)]
+        return self._kept_rows(train, ds, lambda index: self.model.features(self._images(ds, index, "default")),
+                               self.model.encoder.max_batch, data)
+
+    def _kept_rows(self, key, ds, embed_fn, batch, data):
+        """Rows `data` of embed_fn (row indices -> cuda (n,512)) over all of `ds`, which is computed once, `batch` rows (the
+        encoder's max_batch) at a time, and kept under `key`."""
+        if key not in self._kept:
+            self._kept[key] = torch.cat([embed_fn(torch.arange(i, min(i + batch, len(ds)))) for i in range(0, len(ds), batch)]) \
+                if len(ds) else torch.zeros((0, 512), device=self.model.device)
+        return self._kept[key][_rows(ds, data).to(self._kept[key].device)]
 
     def _batch_input(self, data, train):
         """What the loader yields -> what the model takes: the embeddings themselves; for a VNCelebDataset (rows of the
@@ -721,27 +677,19 @@ class AugClassificationTrainer(ClassificationTrainer):
             raise NotImplementedError("transforms.resize is not built: crop the faces at the encoder's input size (DESIGN.md 8)")
         self.transform = augment.get_transform(tf["name"])
         self.val_transform = augment.get_transform("default")
-        # the encoder's own input dtype: 16-bit storage paths take 16-bit images, the others fp32
-        self.x_dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "fp16": torch.float16}.get(self.encoder.compute_dtype, torch.float32)
-        self._val_emb = None
+        self.x_dtype = _X_DTYPES.get(self.encoder.compute_dtype, torch.float32)   # the encoder's own input dtype
 
     def embed(self, dataset, index, transform):
         """Rows `index` of `dataset` through `transform` and the encoder: cuda (n,512) fp32."""
         from . import augment
         t = self.encoder.input_size
         faces = dataset.faces_device(self.model.device)
-        index = torch.as_tensor(index, dtype=torch.int64)
-        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(dataset)):
-            raise IndexError("sample index outside the data set")
+        index = _rows(dataset, index)
         params = transform.params(int(index.numel()), dataset.size, t)
         return self.encoder(augment.augment_faces_device(faces, index, params, t, dtype=self.x_dtype))
 
     def _batch_input(self, data, train):
         if train:
             return self.embed(self.train_loader.dataset, data, self.transform)
-        if self._val_emb is None:
-            ds = self.val_loader.dataset
-            bs = self.encoder.max_batch
-            self._val_emb = torch.cat([self.embed(ds, torch.arange(i, min(i + bs, len(ds))), self.val_transform)
-                                       for i in range(0, len(ds), bs)]) if len(ds) else torch.zeros((0, 512), device=self.model.device)
-        return self._val_emb[torch.as_tensor(data, dtype=torch.int64).to(self._val_emb.device)]
+        ds = self.val_loader.dataset
+        return self._kept_rows(train, ds, lambda index: self.embed(ds, index, self.val_transform), self.encoder.max_batch, data)
