@@ -3,85 +3,95 @@
 
 Same flags and files: frames are sub-sampled per second of video with -fidx (l.180-187), queued in batches of
 --n_frames, recognised with per-class thresholds (--local_thresholds JSON, or --recog_threshold for every class,
-l.127-136), logged to the tracker CSV (Time,Names,Frame_idx[,Bboxes], l.137-147,253-276; an existing tracker file is
-re-used, l.393-399) and summarised into the interval JSON (`dynamic_itv` / `fixed_itv`, l.32-107, 401-412).
+l.127-136), logged to the tracker CSV (Time,Names,Frame_idx[,Bboxes][,Emotion], l.137-147,253-276; an existing tracker
+file is re-used, l.393-399) and summarised into the interval JSON (`dynamic_itv` / `fixed_itv`, l.32-107, 401-412).
 
-The recognition itself is the resident MI355X pipeline in throughput mode (FacePipeline.submit: detection and
-embedding streams overlap, faces of consecutive batches embedded together).  Input: a directory of frames or a
-.npy array of (T,H,W,3) RGB frames with -fps (OpenCV / pafy are not installed: no container decode, no YouTube);
---recog_emotion (carried by demo_image.py only: the frame stream's multi-rank exchange does not pass emotions on) and
-seq_fd_vs_aln (outside the hot path) are refused."""
+The frames go through video.run_stream, the path demo_video.py runs on: launched under torch.distributed.run, batch b
+of the SAMPLED frames belongs to -- and is read by -- rank b % world_size only, the ranks all-gather embeddings, boxes
+and emotions per round and rank 0 writes the tracker and the statistics.  Only the frames -fidx keeps are read and
+decoded (a directory, a .npy array, a Motion-JPEG .avi; JPEG frames on the GPU unless --host_decode); frame number and
+time stay those of the input.  --recog_emotion (-emt, -emtargs, -t2i, --topk_emotions) adds every face's top-k emotion
+tags to the tracker (column Emotion, l.264-271) and to the 'emotions' field of the JSON, the mode the reference's own
+scripts run (scripts/celeb_stat_*.sh).  -sfr writes the annotated PNGs (boxes, names, emotion lines) on the host;
+-ov out.avi writes the annotated video of the sampled frames from the device (jpeg_encode.VideoEncoder: boxes, names
+and emotion lines drawn in HBM, --ov_quality, --ov_subsampling) at as many frames per second as -fidx keeps, so the
+video lasts as long as the input.  Input: a directory of frames or a .npy array of (T,H,W,3) RGB frames with -fps, or
+a Motion-JPEG .avi (OpenCV / pafy are not installed: no other container decode, no YouTube); seq_fd_vs_aln (outside
+the hot path) is refused."""
 import os
 import time
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
-from demo_image import build_models, build_parser
-from vn_celeb_face_recognition_amd.cli_utils import (append_log_to_file, draw_boxes_on_image, open_frame_source,
-                                                     write_rgb)
-from vn_celeb_face_recognition_amd.pipeline import FacePipeline, identify_names
+from demo_image import build_emotion, build_models, build_parser
+from vn_celeb_face_recognition_amd import dist as vdist
+from vn_celeb_face_recognition_amd.cli_utils import (append_log_to_file, draw_boxes_on_image, draw_emotions,
+                                                     open_frame_source, write_rgb)
+from vn_celeb_face_recognition_amd.pipeline import FacePipeline
 from vn_celeb_face_recognition_amd.statistics import (build_thresholds, convert_sec_to_max_time_quantity,
                                                       export_json_stat_dynamic_itv, export_json_stat_fixed_itv,
                                                       frame_is_sampled, read_tracker_csv, tracker_header, tracker_row)
+from vn_celeb_face_recognition_amd.video import run_stream
 
 
-def main(args, pipe, threshold, frame_idxes):
-    os.makedirs(args.output_frame, exist_ok=True)
-    with open(args.output_tracker, 'w') as f:
-        f.write('')
-    append_log_to_file(args.output_tracker, tracker_header(args.track_bbox))
-    frames_iter = open_frame_source(args.video_path)
-    fps = frames_iter.fps
+def emotion_tags(idx2etag, idx):
+    """celeb_statistic.py:264-271: per face the plain-str list of its top-k tags ([] for a frame without faces)"""
+    return [[str(idx2etag[int(i)]) for i in face] for face in idx]
+
+
+def sampled_source(args, frame_idxes):
+    """the frame source reduced to the frames -fidx keeps (celeb_statistic.py:180-187) -> (source, frames per second
+    of input it keeps)"""
+    source = open_frame_source(args.video_path)
     if args.fps_video > 0:
-        fps = args.fps_video
-    count = processed_frame = 0
+        source.fps = float(args.fps_video)
+    fps = source.fps
+    source.sample(lambda count: frame_is_sampled(count, fps, frame_idxes))
+    # count % fps takes every value below fps once per second of video (an integral rate; otherwise about once)
+    kept = len({i for i in frame_idxes if 0 <= i < fps})
+    return source, kept
+
+
+def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=None):
+    """celeb_statistic.py:150-300 on video.run_stream; identical control flow for every world size"""
+    k = args.topk_emotions if idx2etag is not None else 0
+    if rank == 0:
+        os.makedirs(args.output_frame, exist_ok=True)
+        with open(args.output_tracker, 'w') as f:
+            f.write('')
+        append_log_to_file(args.output_tracker, tracker_header(args.track_bbox, k > 0))
     start_time = time.time()
-    queue, info, inflight = [], [], []
 
-    def retire(item):
-        t, q, inf = item
-        counts, boxes, emb, amax, prob = t.result()
-        names = identify_names(amax, prob, pipe.classifier.num_classes, pipe.label2name, threshold) if len(boxes) else []
-        rows, o = [], 0
-        for idx, c in enumerate(counts):
-            nm, bx = names[o:o + c], [boxes[k] for k in range(o, o + c)]
-            o += c
-            if args.save_frame_recognized:
-                img = draw_boxes_on_image(q[idx], bx, nm) if nm else q[idx]
-                write_rgb(os.path.join(args.output_frame, 'frame_{}.png'.format(inf[idx][1])), img)
-            rows.append(tracker_row(inf[idx][0], nm, inf[idx][1], bx, q[idx].shape[:2], args.track_bbox))
-        with open(args.output_tracker, 'a') as f:
-            f.write(''.join(rows))
+    def row(tm, number, names, boxes, shape, emotions=None):
+        return tracker_row(tm, names, number, boxes, shape[:2], args.track_bbox,
+                           emotion_tags(idx2etag, emotions[0]) if emotions is not None else None)
 
-    def flush_queue():
-        nonlocal processed_frame, queue, info
-        if not queue:
-            return
-        processed_frame += len(queue)
-        if (processed_frame % args.log_step) == 0:
-            print('Processing for frame: {}, time: {}'.format(info[-1][1], convert_sec_to_max_time_quantity(info[-1][0])))
-        frames_dev, _ = pipe.detector._to_device_frames(queue)
-        inflight.append((pipe.submit(frames_dev), queue, info))
-        queue, info = [], []
-        while len(inflight) > 2:
-            retire(inflight.pop(0))
+    def on_frame(frame, number, names, boxes, emotions=None):
+        img = draw_boxes_on_image(frame, boxes, names) if names else frame
+        if names and emotions is not None:
+            img = draw_emotions(img, boxes, emotion_tags(idx2etag, emotions[0]), emotions[1])
+        write_rgb(os.path.join(args.output_frame, 'frame_{}.png'.format(number)), img)
 
-    for frame in frames_iter:
-        count += 1
-        if not frame_is_sampled(count, fps, frame_idxes):
-            continue
-        queue.append(frame)
-        info.append([count / fps, count])
-        if len(queue) == args.n_frames:
-            flush_queue()
-    flush_queue()
-    pipe.flush()
-    while inflight:
-        retire(inflight.pop(0))
+    def log(processed, inf):
+        if (processed % args.log_step) == 0:
+            print('Processing for frame: {}, time: {}'.format(inf[-1][1], convert_sec_to_max_time_quantity(inf[-1][0])))
+
+    rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
+                                 on_frame=on_frame if args.save_frame_recognized else None, log=log,
+                                 decode="host" if args.host_decode else "device", encoder=encoder, emotions=k, row=row)
+    if world > 1:
+        tot = torch.tensor([processed], device=device if device is not None else 'cuda')
+        dist.all_reduce(tot)
+        processed = int(tot.item())
+    if rank != 0:
+        return None
+    with open(args.output_tracker, 'a') as f:
+        f.write(''.join(rows[n] for n in sorted(rows)))
     processed_time = time.time() - start_time
     print('Saved tracker file in {} ...'.format(args.output_tracker))
-    print('FPS for recognition face: {}'.format(int(processed_frame / max(processed_time, 1e-9))))
+    print('FPS for recognition face: {}'.format(int(processed / max(processed_time, 1e-9))))
     return read_tracker_csv(args.output_tracker)
 
 
@@ -104,6 +114,13 @@ if __name__ == '__main__':
     p.add_argument('--youtube_video', action='store_true')
     p.add_argument('--n_frames', default=16, type=int)
     p.add_argument('-fps', '--fps_video', default=0.0, type=float, help='frame rate of a frame directory / .npy input')
+    p.add_argument('--host_decode', action='store_true',
+                   help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
+    p.add_argument('-ov', '--output_video', default='', type=str,
+                   help='annotated video of the sampled frames, encoded on the GPU (Motion-JPEG .avi)')
+    p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov (1..100)')
+    p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
+                   help='chroma subsampling of the frames of -ov')
     p.set_defaults(recog_threshold=0.7)          # celeb_statistic.py:349 (demo_image's default is 0)
     args = p.parse_args()
     if args.youtube_video:
@@ -111,22 +128,67 @@ if __name__ == '__main__':
     if args.inference_method != 'par_fd_vs_aln':
         raise SystemExit("use --inference_method par_fd_vs_aln (seq_fd_vs_aln needs the FAN landmark network, outside "
                          "the hot path and broken in the reference for list input)")
+    if args.output_video and not args.output_video.lower().endswith('.avi'):
+        raise SystemExit("-ov encodes the annotated frames on the GPU into a Motion-JPEG AVI: give it a name ending in .avi")
+    if args.output_video and not 1 <= args.ov_quality <= 100:
+        raise SystemExit("--ov_quality must be in 1..100")
+    if args.recog_emotion and not 1 <= args.topk_emotions <= 16:
+        raise SystemExit("--topk_emotions must be in 1..16 (the width of the device top-k and of the stream's exchange)")
     frame_idxes = list(args.frame_idxes)
-    if not os.path.exists(args.output_tracker):
-        print('Create tracker file {}'.format(args.output_tracker))
-        torch.cuda.set_device(0)
-        label2name_df, detection_md, emb_model, classify_model = build_models(args, 'cuda:0')
+    rank, world, local = vdist.init_from_env()
+    # one decision for every rank: the tracker file appears while rank 0 works, so a late rank must not look for it
+    create = not os.path.exists(args.output_tracker)
+    if world > 1:
+        flag = [create]
+        dist.broadcast_object_list(flag, src=0, device=torch.device('cuda', local))
+        create = flag[0]
+    tracker_df = None
+    if create:
+        if rank == 0:
+            print('Create tracker file {}'.format(args.output_tracker))
+        device = 'cuda:%d' % local
+        torch.cuda.set_device(local)
+        label2name_df, detection_md, emb_model, classify_model = build_models(args, device, allow_emotion=True)
+        idx2etag = emt_model = None
+        if args.recog_emotion:
+            idx2etag, emt_model = build_emotion(args, device)
         if args.local_thresholds != '':
             print('Using local thresholds !')
         else:
             print('Using global a threshold !')
         threshold = build_thresholds(args.local_thresholds, args.num_classes, args.recog_threshold)
         pipe = FacePipeline(detection_md, emb_model, classify_model, label2name_df, args.target_face_size, threshold,
-                            embed_batch=256)
-        tracker_df = main(args, pipe, threshold, frame_idxes)
-    else:
+                            embed_batch=256, emotion=emt_model, topk_emotions=args.topk_emotions)
+        source, kept_per_second = sampled_source(args, frame_idxes)
+        encoder = None
+        if args.output_video:
+            from vn_celeb_face_recognition_amd.jpeg_encode import VideoEncoder
+            encoder = VideoEncoder(args.output_video, float(max(kept_per_second, 1)), device, args.ov_quality,
+                                   args.ov_subsampling, rank, world, idx2tag=idx2etag)
+        try:
+            tracker_df = main(args, pipe, rank, world, source, device=device, encoder=encoder, idx2etag=idx2etag)
+        except BaseException:
+            if encoder is not None:
+                encoder.abort()                               # no half-written video, no spool file of this rank
+            raise
+        if encoder is not None:
+            try:
+                encoder.close()
+            except ValueError as e:                           # a stream without sampled frames
+                raise SystemExit("-ov: {}".format(e))
+            if world > 1:
+                dist.barrier()                                # every rank's spool file is complete
+                if rank == 0:
+                    encoder.merge()
+            if rank == 0:
+                print('Save exported video in {} ...'.format(args.output_video))
+    elif rank == 0:
         print('Re-use tracker file {}'.format(args.output_tracker))
         tracker_df = read_tracker_csv(args.output_tracker)
+    if world > 1:
+        dist.destroy_process_group()
+    if rank != 0:
+        raise SystemExit(0)
     print('Statistic mode: {}'.format(args.statistic_mode))
     if not args.track_bbox and 'Bboxes' not in tracker_df:
         raise SystemExit("the interval statistics need the Bboxes column: run with --track_bbox (the reference raises "

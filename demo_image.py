@@ -44,12 +44,13 @@ def build_parser(desc):
 
 def build_models(args, device, allow_emotion=False):
     """demo_image.py:359-376 / demo_video.py:257-275.  The emotion model is built separately (build_emotion), by the
-    CLI that carries its results: demo_image.py."""
+    CLIs that carry its results: demo_image.py and celeb_statistic.py."""
     if args.device != 'GPU':
         raise SystemExit("this build runs on MI355X only: use -dv GPU (there is no CPU path)")
     if args.recog_emotion and not allow_emotion:
-        raise SystemExit("--recog_emotion is carried by demo_image.py only: the video stream's multi-rank exchange does "
-                         "not pass emotions on yet")
+        raise SystemExit("--recog_emotion is carried by demo_image.py only among the demos: demo_video.py neither draws nor "
+                         "logs emotions.  On a frame stream use celeb_statistic.py, whose tracker, statistics and -ov "
+                         "video carry them")
     label2name_df = read_label2name(args.label2name)
     det_args = read_json(args.detection_args)
     det_args['device'] = device

@@ -44,6 +44,8 @@
  *                                    demo_video.py:25-43,149-152 (cv2.rectangle / putText on the frame, cv2.imwrite,
  *                                    cv2.VideoWriter.write: the annotated frame is drawn and transformed on the
  *                                    device, the Huffman pass and the container stay on the host)
+ *   vnf_overlay_draw_text            demo_image.py:161-171 (draw_emotions: cv2.putText per tag line) on frames in
+ *                                    device memory, from a glyph atlas
  *
  * Conventions
  *   - every function returns 0 on success or a negative VNF_E_* code and never throws;
@@ -533,6 +535,44 @@ typedef struct {
  * width outside 1..65535, a NULL frames_dev / ops_dev. */
 int vnf_overlay_draw(uint8_t* frames_dev, int b, int height, int width, const vnf_overlay_op* ops_dev, int n_ops,
                      const uint8_t* masks_dev, int64_t masks_bytes, void* stream);
+
+/* Text runs: lines that differ per face and per frame (cli_utils.draw_emotions, demo_image.py:161-171), composited on
+ * the device from a glyph atlas instead of rendered on the host. */
+#define VNF_TEXT_RUN_MAX 64   /* characters in one run */
+#define VNF_TEXT_GLYPH_MAX 64 /* a glyph's width, height and advance, and the magnitude of its offsets */
+/* One glyph: its coverage cut to the ink, w columns by h rows, row-major at coverage[offset, offset + w * h); (ox, oy)
+ * is where its top-left pixel lies relative to the pen, advance what it moves the pen by. */
+typedef struct {
+  int32_t offset, w, h, ox, oy, advance;
+} vnf_text_glyph;
+/* The atlas in device memory: this header, n_glyphs vnf_text_glyph for the characters first_char .. first_char +
+ * n_glyphs - 1, then the coverage bytes.  n_glyphs in 1..256. */
+typedef struct {
+  int32_t first_char, n_glyphs;
+} vnf_text_atlas;
+/* One ImageDraw.text((x, y), chars[first, first + length), fill=rgb) call on one frame; rgb as in vnf_overlay_op. */
+typedef struct {
+  int32_t frame, x, y;
+  uint32_t rgb;
+  int32_t first, length;
+} vnf_text_run;
+/* Paints the runs in place on frames_dev (b,height,width,3) u8, after whatever is on the frames already (call it
+ * behind vnf_overlay_draw on the same stream): the glyphs of a run sit at pen positions equal to the sum of the
+ * preceding advances, overlapping glyphs combine as dst += round(src (255 - dst) / 255), and the run's coverage is
+ * blended with vnf_overlay_draw's label formula.  With an atlas of Pillow's default font (jpeg_encode.text_atlas) this
+ * is ImageDraw.text byte for byte.  One workgroup per run, threads over the run's ink rectangle clipped to the frame.
+ *   runs_dev: device, n_runs entries in DRAW ORDER; chars_dev: device bytes; atlas_dev: device, atlas_bytes in all.
+ *   launch_ends: HOST array of n_launches ascending run counts, the last one n_runs, or NULL for one launch: runs
+ *   [launch_ends[i-1], launch_ends[i]) go into launch i.  The runs of one launch must not intersect on a frame; a run
+ *   that intersects an earlier one belongs to a later launch, which paints over it (jpeg_encode.text_runs orders them).
+ * The tables live in device memory, so the call cannot see their values: a run whose frame is outside 0..b-1, whose
+ * length is outside 1..VNF_TEXT_RUN_MAX or whose characters leave [0, chars_bytes) paints nothing; a character outside
+ * the atlas or a glyph outside VNF_TEXT_GLYPH_MAX or the atlas's bytes has no ink and does not move the pen.
+ * Nothing allocated, no synchronisation.  b == 0 or n_runs == 0: no-op.  VNF_E_INVALID: a negative count, height or
+ * width outside 1..65535, a NULL or misaligned pointer, launch_ends not ascending or not ending at n_runs. */
+int vnf_overlay_draw_text(uint8_t* frames_dev, int b, int height, int width, const vnf_text_run* runs_dev, int n_runs,
+                          const int32_t* launch_ends, int n_launches, const uint8_t* chars_dev, int64_t chars_bytes,
+                          const void* atlas_dev, int64_t atlas_bytes, void* stream);
 
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile

@@ -117,6 +117,7 @@ SIGNATURES = {
     "vnf_jpeg_encode_frames": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
     "vnf_jpeg_entropy_encode": (_I, [_P, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
+    "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }
 
 

@@ -274,6 +274,216 @@ def draw_boxes_device(frames_dev, boxes, names, stream=None):
     return frames_dev
 
 
+# text runs -------------------------------------------------------------------------------------------------------------
+# The emotion lines ('<tag> - <percent>%', cli_utils.draw_emotions) differ per face and per frame: rendering each with
+# Pillow would put the font renderer on the batch's critical path.  They are composited on the device from an atlas of
+# the default font's glyphs instead (vnf_overlay_draw_text); a line the atlas cannot express is rendered by
+# `_label_mask` and goes through the LABEL path, so the picture is Pillow's either way.
+
+RUN_DTYPE = np.dtype([("frame", "<i4"), ("x", "<i4"), ("y", "<i4"), ("rgb", "<u4"), ("first", "<i4"), ("length", "<i4")])  # vnf_text_run
+GLYPH_DTYPE = np.dtype([("offset", "<i4"), ("w", "<i4"), ("h", "<i4"), ("ox", "<i4"), ("oy", "<i4"), ("advance", "<i4")])  # vnf_text_glyph
+TEXT_RUN_MAX = 64                               # VNF_TEXT_RUN_MAX
+TEXT_GLYPH_MAX = 64                             # VNF_TEXT_GLYPH_MAX
+ATLAS_FIRST, ATLAS_LAST = 32, 126               # printable ASCII
+LABEL_PEN = 16                                  # where a fallback line's pen sits inside its rendered tile (pixels)
+
+_atlas = False                                  # False: not built yet; None: this Pillow's default font has no atlas
+_atlas_dev = {}
+
+
+def text_atlas():
+    """The default font's glyphs for printable ASCII, built once per process: {'glyphs': GLYPH_DTYPE array,
+    'coverage': u8 array, 'bytes': the vnf_text_atlas image of both}, or None when a string's picture is not the sum of
+    its glyphs' -- the font is no FreeType face laid out by Layout.BASIC, an advance is not an integer, or a glyph is
+    larger than the kernel takes.  Each glyph is what ImageDraw.text paints for the character alone, cut to its ink."""
+    global _atlas
+    if _atlas is not False:
+        return _atlas
+    from PIL import Image, ImageDraw, ImageFont
+    font = ImageDraw.Draw(Image.new("L", (1, 1))).getfont()
+    _atlas = None
+    if getattr(font, "layout_engine", None) != ImageFont.Layout.BASIC or not hasattr(font, "getlength"):
+        return None
+    pad = TEXT_GLYPH_MAX
+    glyphs, cov, at = np.zeros((ATLAS_LAST - ATLAS_FIRST + 1,), GLYPH_DTYPE), [], 0
+    for c in range(ATLAS_FIRST, ATLAS_LAST + 1):
+        adv = float(font.getlength(chr(c)))
+        if adv != int(adv) or not 0 <= adv <= TEXT_GLYPH_MAX:
+            return None
+        im = Image.new("L", (3 * pad, 3 * pad), 0)
+        ImageDraw.Draw(im).text((pad, pad), chr(c), fill=255, font=font)
+        a = np.asarray(im)
+        ys, xs = np.nonzero(a)
+        g = glyphs[c - ATLAS_FIRST]
+        g["advance"] = int(adv)
+        if ys.size == 0:
+            continue
+        y0, y1, x0, x1 = int(ys.min()), int(ys.max()) + 1, int(xs.min()), int(xs.max()) + 1
+        if x0 == 0 or y0 == 0 or x1 == 3 * pad or y1 == 3 * pad or x1 - x0 > TEXT_GLYPH_MAX or y1 - y0 > TEXT_GLYPH_MAX:
+            return None                          # ink up to the canvas's edge: the glyph may be larger than it
+        g["offset"], g["w"], g["h"], g["ox"], g["oy"] = at, x1 - x0, y1 - y0, x0 - pad, y0 - pad
+        cov.append(np.ascontiguousarray(a[y0:y1, x0:x1]).reshape(-1))
+        at += cov[-1].size
+    coverage = np.concatenate(cov) if cov else np.zeros((0,), np.uint8)
+    head = np.array([ATLAS_FIRST, glyphs.shape[0]], "<i4")
+    _atlas = {"glyphs": glyphs, "coverage": coverage,
+              "bytes": np.concatenate([head.view(np.uint8), glyphs.view(np.uint8), coverage]),
+              # what text_runs needs per line, in forms the bytes methods and sum() take
+              "charset": bytes(range(ATLAS_FIRST, ATLAS_LAST + 1)),
+              "blank": bytes(ATLAS_FIRST + i for i, g in enumerate(glyphs) if not g["w"]),
+              "advance": [0] * ATLAS_FIRST + [int(a) for a in glyphs["advance"]] + [0] * (255 - ATLAS_LAST)}
+    ink = glyphs[glyphs["w"] > 0]
+    # a box every glyph's ink fits when the pen is at 0: columns [left, advance + right), rows [top, bottom)
+    _atlas["extent"] = (int(ink["ox"].min()), int((ink["ox"] + ink["w"] - ink["advance"]).max()), int(ink["oy"].min()),
+                        int((ink["oy"] + ink["h"]).max())) if ink.size else (0, 0, 0, 0)
+    return _atlas
+
+
+def text_atlas_device(device):
+    """the atlas's bytes on `device`, uploaded once per process and device"""
+    import torch
+    key = str(torch.device(device))
+    if key not in _atlas_dev:
+        _atlas_dev[key] = torch.from_numpy(text_atlas()["bytes"]).to(device)
+    return _atlas_dev[key]
+
+
+def _run_box(atlas, text, x, y):
+    """a rectangle (x0, y0, x1, y1), half open, that holds the ink of the run `text` (bytes inside the atlas) anchored
+    at (x, y) -- the pen's travel widened by the font's largest overhangs, the font's rows --, or None for no ink"""
+    if not text.strip(atlas["blank"]):
+        return None
+    left, right, top, bottom = atlas["extent"]
+    return x + min(left, 0), y + top, x + sum(map(atlas["advance"].__getitem__, text)) + max(right, 0), y + bottom
+
+
+def emotion_lines(boxes, tags, probs):
+    """cli_utils.draw_emotions's text calls for a batch: boxes per frame; tags / probs per frame and face -> a list of
+    (frame, x, y, string) in draw order"""
+    out = []
+    for f, bx in enumerate(boxes):
+        for idx, box in enumerate(bx):
+            for i, (tag, p) in enumerate(zip(tags[f][idx], probs[f][idx])):
+                # the anchor in draw_emotions's own arithmetic (box[0] + 5 in the box's dtype, then truncated)
+                out.append((f, int(box[0] + 5), int(box[1]) + i * 16 + 4, '{} - {:.2f}%'.format(tag, p * 100)))
+    return out
+
+
+def text_runs(lines, colour=GREEN, atlas=False):
+    """The host side of vnf_overlay_draw_text: consecutive ImageDraw.text((x, y), s, fill=colour) calls with integer
+    anchors, as tables.  lines: (frame, x, y, string) in draw order.
+    -> (runs: RUN_DTYPE array, chars: u8 array, launch_ends: int32 array, label_ops: OP_DTYPE array, masks: u8 array).
+    The runs are ordered by launch, draw order inside one: a run whose rectangle (`_run_box`, which holds its ink)
+    intersects an earlier run's on the same frame sits in a later launch than it (in practice there is one launch).
+    A frame with a line the atlas cannot express -- a character outside it, more than TEXT_RUN_MAX characters, or no
+    atlas at all -- has ALL its lines as LABEL ops (rendered by `_label_mask`, for vnf_overlay_draw, behind the boxes
+    and names), so that the draw order inside a frame never crosses the two paths."""
+    atlas = text_atlas() if atlas is False else atlas
+    rgb = (int(colour[0]) & 255) | (int(colour[1]) & 255) << 8 | (int(colour[2]) & 255) << 16
+    coded, by_label = [], set()
+    for f, x, y, s in lines:
+        b = s.encode("ascii", "replace") if s.isascii() else None
+        ok = atlas is not None and b is not None and len(b) <= TEXT_RUN_MAX and not b.translate(None, atlas["charset"])
+        if not ok:
+            by_label.add(int(f))
+        coded.append(b if ok else None)
+    runs, chars, levels, placed = [], bytearray(), [], {}
+    ops, masks, mat = [], [], 0
+    for (f, x, y, s), text in zip(lines, coded):
+        f, x, y = int(f), int(max(-_COORD, min(_COORD, x))), int(max(-_COORD, min(_COORD, y)))
+        if f in by_label:
+            # the pen sits LABEL_PEN pixels inside the tile: `_label_mask` cuts ink left of or above the tile's origin,
+            # and glyphs such as 's' or ')' start a pixel left of the pen
+            m, ox, oy = _label_mask(s, float(LABEL_PEN), float(LABEL_PEN))
+            if m is not None:
+                ops.append((LABEL, f, x + ox - LABEL_PEN, y + oy - LABEL_PEN, m.shape[1], m.shape[0], mat, rgb))
+                masks.append(m.reshape(-1))
+                mat += m.size
+            continue
+        box = _run_box(atlas, text, x, y)
+        if box is None:
+            continue
+        level = 0
+        for (x0, y0, x1, y1), lv in placed.get(f, ()):
+            if lv >= level and box[0] < x1 and x0 < box[2] and box[1] < y1 and y0 < box[3]:
+                level = lv + 1
+        placed.setdefault(f, []).append((box, level))
+        runs.append((f, x, y, rgb, len(chars), len(text)))
+        levels.append(level)
+        chars += text
+    runs = np.array(runs, dtype=RUN_DTYPE) if runs else np.zeros((0,), RUN_DTYPE)
+    levels = np.asarray(levels, np.int64)
+    order = np.argsort(levels, kind="stable")
+    ends = np.cumsum(np.bincount(levels)).astype(np.int32) if levels.size else np.zeros((0,), np.int32)
+    return (runs[order], np.frombuffer(bytes(chars), np.uint8), ends,
+            np.array(ops, dtype=OP_DTYPE) if ops else np.zeros((0,), OP_DTYPE),
+            np.concatenate(masks) if masks else np.zeros((0,), np.uint8))
+
+
+def overlay_draw_text(frames_dev, runs_dev, chars_dev, launch_ends=None, atlas_dev=None, stream_ptr=None):
+    """vnf_overlay_draw_text on torch tensors: frames_dev (b,H,W,3) u8 cuda, contiguous, painted in place; runs_dev:
+    the bytes of a RUN_DTYPE table on the device; chars_dev: u8 cuda; launch_ends: host int32 array (None: one launch);
+    atlas_dev: default text_atlas_device(frames_dev.device)."""
+    if not (frames_dev.is_cuda and runs_dev.is_cuda and chars_dev.is_cuda):
+        raise RuntimeError("jpeg_encode.overlay_draw_text needs cuda tensors (there is no CPU path)")
+    if frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or not frames_dev.is_contiguous():
+        raise ValueError("overlay_draw_text: frames_dev must be a contiguous (b,H,W,3) u8 tensor")
+    if atlas_dev is None:
+        if text_atlas() is None:
+            raise RuntimeError("overlay_draw_text: this Pillow's default font has no glyph atlas (text_runs sends every "
+                               "line through the LABEL path then)")
+        atlas_dev = text_atlas_device(frames_dev.device)
+    b, h, w = (int(s) for s in frames_dev.shape[:3])
+    n_runs = runs_dev.numel() * runs_dev.element_size() // RUN_DTYPE.itemsize
+    ends = None if launch_ends is None else np.ascontiguousarray(launch_ends, dtype=np.int32)
+    _lib.check(_lib.load().vnf_overlay_draw_text(
+        frames_dev.data_ptr(), b, h, w, runs_dev.data_ptr(), int(n_runs), ends.ctypes.data if ends is not None else None,
+        int(ends.size) if ends is not None else 0, chars_dev.data_ptr() if chars_dev.numel() else None, int(chars_dev.numel()),
+        atlas_dev.data_ptr(), int(atlas_dev.numel()), stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+    return frames_dev
+
+
+def _upload_and_draw(frames_dev, ops, masks, runs, chars, ends, stream):
+    """one upload of every table, then vnf_overlay_draw (boxes, names, LABEL lines) and vnf_overlay_draw_text"""
+    import torch
+    if ops.shape[0] == 0 and runs.shape[0] == 0:
+        return frames_dev
+    stream = stream if stream is not None else torch.cuda.current_stream(frames_dev.device)
+    with torch.cuda.stream(stream):
+        # the tables first keeps them 4-byte aligned (both records are multiples of 4 bytes)
+        packed = np.concatenate([ops.view(np.uint8), runs.view(np.uint8), masks, chars])
+        dev = torch.from_numpy(packed).to(frames_dev.device, non_blocking=False)
+        a, b = ops.nbytes, ops.nbytes + runs.nbytes
+        sp = ctypes.c_void_p(stream.cuda_stream)
+        if ops.shape[0]:
+            overlay_draw(frames_dev, dev[:a], dev[b:b + masks.size], sp)
+        if runs.shape[0]:
+            overlay_draw_text(frames_dev, dev[a:b], dev[b + masks.size:], ends, None, sp)
+        dev.record_stream(stream)
+    return frames_dev
+
+
+def draw_emotions_device(frames_dev, boxes, tags, probs, stream=None):
+    """cli_utils.draw_emotions for every frame of a device batch, in place, on `stream` (default: the current one)"""
+    runs, chars, ends, ops, masks = text_runs(emotion_lines(boxes, tags, probs))
+    return _upload_and_draw(frames_dev, ops, masks, runs, chars, ends, stream)
+
+
+def draw_annotations_device(frames_dev, boxes, names, tags=None, probs=None, stream=None):
+    """draw_boxes_on_image, then (with tags) draw_emotions, for every frame of a device batch, in place: the
+    rectangles, the names and the lines that need the LABEL path in one vnf_overlay_draw launch, the text runs behind
+    it."""
+    ops, masks = overlay_ops(boxes, names)
+    runs, chars, ends = np.zeros((0,), RUN_DTYPE), np.zeros((0,), np.uint8), None
+    if tags is not None:
+        runs, chars, ends, ops2, masks2 = text_runs(emotion_lines(boxes, tags, probs))
+        if ops2.shape[0]:
+            ops2 = ops2.copy()
+            ops2["mask_offset"] += masks.size
+            ops, masks = np.concatenate([ops, ops2]), np.concatenate([masks, masks2])
+    return _upload_and_draw(frames_dev, ops, masks, runs, chars, ends, stream)
+
+
 # the video writer video.run_stream drives --------------------------------------------------------------------------
 
 PART_MAGIC = b"VNFMJPG1"
@@ -284,7 +494,9 @@ class VideoEncoder:
     order, to a Motion-JPEG AVI (one process) or to this rank's spool file `<path>.rank<r>.part` (several; rank 0
     merges them with `merge` once every rank has closed its own)."""
 
-    def __init__(self, path, fps, device, quality=92, sampling="4:2:0", rank=0, world=1):
+    def __init__(self, path, fps, device, quality=92, sampling="4:2:0", rank=0, world=1, idx2tag=None):
+        """idx2tag: the emotion tag table (index -> tag) for write_batch(emotions=...) called with class indices, as
+        video.run_stream(emotions=k) calls it; None: the tags are drawn as they are handed over."""
         import torch
         from .mjpeg_avi import MjpegAviWriter
         from .streams import side_stream
@@ -295,6 +507,7 @@ class VideoEncoder:
         self.enc = BatchEncoder(self.device, quality, sampling)
         self.stream = side_stream(self.device, ENCODE_STREAM_ROLE)
         self.frames = 0
+        self.idx2tag = idx2tag
         if self.world == 1:
             self._avi, self._part = MjpegAviWriter(self.path, self.fps), None
         else:
@@ -305,15 +518,21 @@ class VideoEncoder:
     def part_path(path, rank):
         return "%s.rank%d.part" % (path, rank)
 
-    def write_batch(self, frames_dev, numbers, boxes, names, after=None):
+    def write_batch(self, frames_dev, numbers, boxes, names, after=None, emotions=None):
         """frames_dev: the batch in HBM, drawn on IN PLACE: the caller hands it over for good -- a buffer nobody reads
         again, never a caller's own source frames (run_stream passes its upload-ring slot, or a copy) -- and its other
         readers are done once `after`, an event, has passed.  numbers: the frames' numbers (ascending); boxes / names: per frame.
+        emotions: None, or per frame (tags, probs), each with one row of top-k entries per face: drawn behind the
+        boxes and names as cli_utils.draw_emotions draws them (a tag that is an integer goes through `idx2tag`).
         -> the event behind the last kernel that reads frames_dev."""
         if after is not None:
             self.stream.wait_event(after)
         if any(len(n) for n in names):
-            draw_boxes_device(frames_dev, boxes, names, self.stream)
+            tags = probs = None
+            if emotions is not None:
+                probs = [e[1] for e in emotions]
+                tags = [[[self._tag(t) for t in face] for face in e[0]] for e in emotions]
+            draw_annotations_device(frames_dev, boxes, names, tags, probs, self.stream)
         job = self.enc.enqueue(frames_dev, self.stream)
         h, w = int(frames_dev.shape[1]), int(frames_dev.shape[2])
         for num, data in zip(numbers, self.enc.finish(job)):
@@ -324,6 +543,11 @@ class VideoEncoder:
                 self._part.write(data)
             self.frames += 1
         return job["kernels"]
+
+    def _tag(self, t):
+        if self.idx2tag is not None and isinstance(t, (int, np.integer)):
+            return self.idx2tag[int(t)]
+        return t
 
     def close(self):
         """finish this process's file.  One process: the AVI (a stream without frames is an error: there is no video to

@@ -8,7 +8,8 @@ on one GPU and on N:
     together); batches are retired two late, so the GPU always has work queued;
   * retiring round r (batches r*world .. r*world + world-1) is the ONE exchange step of the path: ONE
     fixed-size all-gather of each rank's (1 + cap, 512 + 4 + 1) fp32 block -- a header row with the face count, then
-    embedding, box, frame slot per face -- issued on a side stream behind the batch's own event.  Its result is read
+    embedding, box, frame slot per face (with `emotions=k` also the face's k emotion indices and probabilities: 2k more
+    values per row) -- issued on a side stream behind the batch's own event.  Its result is read
     on the host one round LATER (pinned D2H + event), so no rank ever blocks on a collective it has just issued; a
     batch with more than `cap` faces is completed by one exactly-sized follow-up gather that every rank derives from
     the same header rows;
@@ -42,14 +43,37 @@ class FrameSource:
     of image paths is decoded with `load`, an array is indexed) or a plain iterator (a decoder: the other ranks' frames
     are pulled and dropped).  Frame numbers start at 1 and time = number / fps, as demo_video.py:84-90 counts them.
     compressed: optional callable i -> the JPEG bytes of frame i of a random-access source, or None for a frame that is
-    no JPEG (a Motion-JPEG AVI's chunks, the .jpg files of a directory): what `rank_batches(compressed=True)` yields."""
+    no JPEG (a Motion-JPEG AVI's chunks, the .jpg files of a directory): what `rank_batches(compressed=True)` yields.
+    keep: optional predicate on the 1-based frame number (celeb_statistic.py:180-187, -fidx).  The source then yields
+    only the frames it keeps, cut into batches by their position among the kept ones; number and time stay those of
+    the original stream.  A random-access source never reads, let alone decodes, a frame it does not keep."""
 
-    def __init__(self, frames, fps, load=None, compressed=None):
+    def __init__(self, frames, fps, load=None, compressed=None, keep=None):
         self.frames, self.fps, self.load = frames, float(fps), load
         self.compressed = compressed if (compressed is not None and hasattr(frames, "__getitem__")) else None
         self.random_access = hasattr(frames, "__getitem__") and hasattr(frames, "__len__")
         self.reads = 0   # frames this rank actually fetched (tests)
-        self.total = len(frames) if self.random_access else None   # frames in the stream (iterators: known once exhausted)
+        self.total = len(frames) if self.random_access else None   # frames the source yields (iterators: known once exhausted)
+        self.keep = self._kept = None
+        if keep is not None:
+            self.sample(keep)
+
+    def sample(self, keep):
+        """yield only the frames whose 1-based number `keep` accepts (before the first batch is drawn) -> self"""
+        self.keep = keep
+        if self.random_access:
+            self._kept = [i for i in range(len(self.frames)) if keep(i + 1)]
+            self.total = len(self._kept)
+        else:
+            self._kept = []                      # filled as the stream is pulled: every rank pulls every frame
+        return self
+
+    def number_of(self, pos):
+        """the 1-based number, in the original stream, of the pos-th (0-based) frame this source yields.  A sequential
+        source learns the numbers as it is pulled, so this is defined for the frames pulled so far only.  run_stream
+        asks for the frames of a round it consumes, and a rank consumes round r only after it has drawn its own batch
+        of round r + 1 (or exhausted the stream): every batch of round r has then passed through `rank_batches`."""
+        return pos + 1 if self.keep is None else self._kept[pos] + 1
 
     def _get(self, i):
         self.reads += 1
@@ -73,19 +97,26 @@ class FrameSource:
         compressed=True: a batch whose frames are all JPEGs comes as a jpeg.CompressedBatch of their bytes, not
         decoded; every other batch as decoded frames, as without it."""
         if self.random_access:
-            total = len(self.frames)
+            total = self.total
             for b in range(rank, (total + n_frames - 1) // n_frames, world):
                 idx = range(b * n_frames, min(total, (b + 1) * n_frames))
+                if self._kept is not None:
+                    idx = self._kept[idx.start:idx.stop]
                 q = self._get_compressed(idx) if (compressed and self.compressed is not None) else None
                 yield b, q if q is not None else [self._get(i) for i in idx], [[(i + 1) / self.fps, i + 1] for i in idx]
             return
-        b, q, inf, count = 0, [], [], 0
+        b, q, inf, count, number = 0, [], [], 0, 0
         for frame in self.frames:
+            number += 1
+            if self.keep is not None:
+                if not self.keep(number):
+                    continue
+                self._kept.append(number - 1)
             count += 1
             if b % world == rank:
                 self.reads += 1
                 q.append(frame)
-                inf.append([count / self.fps, count])
+                inf.append([number / self.fps, number])
             if count % n_frames == 0:
                 if q:
                     yield b, q, inf
@@ -95,14 +126,14 @@ class FrameSource:
             yield b, q, inf
 
     def __iter__(self):
-        """every frame in order (single-process callers that sample frames themselves: celeb_statistic.py)"""
+        """every frame of the underlying stream in order, `keep` or not (callers that sample frames themselves)"""
         if self.random_access:
             return (self._get(i) for i in range(len(self.frames)))
         return iter(self.frames)
 
 
 def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
-               decode="device", encoder=None):
+               decode="device", encoder=None, emotions=0, row=None):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
 
     pipe: FacePipeline-like -- .submit(frames_dev, classify=False[, ready=event]) -> ticket with .result() ->
@@ -122,7 +153,22 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     it draws on them in place (frames without faces go through unannotated; a batch that is not a slot of the upload
     ring -- a source that hands out cuda tensors -- is copied first, the source's frames are never painted).  Like on_frame it makes every rank
     classify.  The batch's slot of the upload ring is released behind the encoder's event, not the embedding's.
+    emotions: k > 0 (at most 16, vnf_softmax_topk's limit) makes the exchange carry every face's top-k emotions: the
+    tickets then have .emo_idx / .emo_prob ((n,k), FacePipeline(emotion=...)), a row of the block is 517 + 2k fp32
+    values -- the k class indices as fp32 (exact below 2^24 classes; a pipe whose .emotion.num_classes is not refused),
+    then the k probabilities --, and on_frame, encoder.write_batch and `row` receive the keyword
+    emotions=(idx (n,k) int64, prob (n,k) fp32) per frame (write_batch: a list of them).  k is the same on every
+    rank (a CLI flag): the block's width follows from it alone.  0 (default): nothing of this, tickets need no emo_*.
+    row: the tracker line's formatter, (time, frame_number, names, boxes, frame_shape[, emotions=...]) -> str; default
+    `tracker_row`.
     Returns (rows: {frame_number: csv row}, complete on rank 0; frames processed by this rank)."""
+    k_emo = int(emotions)
+    if not 0 <= k_emo <= 16:
+        raise ValueError("run_stream: emotions must be in 0..16, got %r" % (emotions,))
+    if k_emo and int(getattr(getattr(pipe, "emotion", None), "num_classes", 0) or 0) >= 1 << 24:
+        raise ValueError("run_stream: the exchange carries emotion indices as fp32, exact below 2^24 classes only")
+    row = row if row is not None else tracker_row
+    number_of = getattr(source, "number_of", None) or (lambda pos: pos + 1)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     on_gpu = dev.type == "cuda"
     comm = uploader = None
@@ -135,10 +181,16 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     elif encoder is not None:
         raise RuntimeError("run_stream: the video encoder works on frames in device memory (there is no CPU path)")
     cap = int(cap) if cap else max(256, 16 * int(n_frames))
-    WIDTH = 517                             # 512 embedding + 4 box + 1 frame slot
+    WIDTH = 517 + 2 * k_emo                 # 512 embedding + 4 box + 1 frame slot [+ k emotion indices + k probabilities]
     classify_here = rank == 0 or on_frame is not None or encoder is not None
     rows, inflight, pending = {}, [], []    # inflight: (round, ticket or None, frames, info); pending: issued exchanges
     state = {"processed": 0, "shape": None}
+
+    def emo(ex, sel):
+        """the keyword that carries the emotions of the faces `sel` of the gathered rows' tail `ex`; nothing without k"""
+        if not k_emo:
+            return {}
+        return {"emotions": (ex[sel, 5:5 + k_emo].astype(np.int64), ex[sel, 5 + k_emo:5 + 2 * k_emo])}
 
     def to_host(x):
         if x is None or not on_gpu:
@@ -168,7 +220,14 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             if n:
                 slot = np.repeat(np.arange(len(counts)), counts).astype(np.float32)   # frame slot inside the batch
                 extra = np.concatenate([np.asarray(boxes, np.float32).reshape(n, 4), slot[:, None]], axis=1)
-                payload = torch.cat([emb.to(dev).float(), torch.from_numpy(extra).to(dev, non_blocking=True)], dim=1)
+                cols = [emb.to(dev).float(), torch.from_numpy(extra).to(dev, non_blocking=True)]
+                if k_emo:
+                    # produced on the embedding stream ahead of the ticket's event, which result() has waited for
+                    if tuple(t.emo_idx.shape) != (n, k_emo) or tuple(t.emo_prob.shape) != (n, k_emo):
+                        raise ValueError("run_stream(emotions=%d): the ticket carries emotions of shape %s" %
+                                         (k_emo, tuple(t.emo_idx.shape)))
+                    cols += [t.emo_idx.to(dev).float(), t.emo_prob.to(dev).float()]
+                payload = torch.cat(cols, dim=1)
         rec = {"rnd": rnd, "q": q, "inf": inf, "own": t is not None, "n": n, "spill": None, "hdr": None}
         if encoder is not None and t is not None:
             # the frames stay with the round: the encoder draws on them once the detector and the warp are done with
@@ -249,25 +308,29 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             nm, bx, sl = names[o:o + k], ex[:, 0:4], ex[:, 4].astype(np.int64)
             o += k
             if r == rank and rec["own"]:                      # my own frames: pixels, times and numbers are here
-                b_names, b_boxes = [], []
+                b_names, b_boxes, b_emo = [], [], []
                 for i, (tm, num) in enumerate(inf):
                     sel = np.nonzero(sl == i)[0]
-                    f_names, f_boxes = [nm[j] for j in sel], [bx[j] for j in sel]
+                    f_names, f_boxes, f_emo = [nm[j] for j in sel], [bx[j] for j in sel], emo(ex, sel)
                     b_names.append(f_names)
                     b_boxes.append(f_boxes)
+                    if k_emo:
+                        b_emo.append(f_emo["emotions"])
                     if on_frame is not None:
-                        on_frame(q[i], num, f_names, f_boxes)
+                        on_frame(q[i], num, f_names, f_boxes, **f_emo)
                     if rank == 0:
-                        rows[num] = tracker_row(tm, num, f_names, f_boxes, q[i].shape)
+                        rows[num] = row(tm, num, f_names, f_boxes, q[i].shape, **f_emo)
                 if encoder is not None:
                     frames_dev, slot, after = rec.pop("video")
-                    done = encoder.write_batch(frames_dev, [num for _, num in inf], b_boxes, b_names, after=after)
+                    done = encoder.write_batch(frames_dev, [num for _, num in inf], b_boxes, b_names, after=after,
+                                               **({"emotions": b_emo} if k_emo else {}))
                     uploader.release(slot, done)
             elif rank == 0:                                   # another rank's frames: number and time follow from the batch index
                 for i in np.unique(sl):
                     sel = np.nonzero(sl == i)[0]
-                    num = (rnd * world + r) * n_frames + int(i) + 1
-                    rows[num] = tracker_row(num / source.fps, num, [nm[j] for j in sel], [bx[j] for j in sel], state["shape"])
+                    num = number_of((rnd * world + r) * n_frames + int(i))
+                    rows[num] = row(num / source.fps, num, [nm[j] for j in sel], [bx[j] for j in sel], state["shape"],
+                                    **emo(ex, sel))
 
     def retire(item):
         pending.append(issue(item))
@@ -337,9 +400,10 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
         uploader.close()
     if rank == 0:
         # a frame without faces sent nothing through the exchange: its (empty) row follows from the frame count
-        for num in range(1, total_frames + 1):
+        none = np.zeros((0,), np.int64)
+        for num in (number_of(pos) for pos in range(total_frames)):
             if num not in rows:
-                rows[num] = tracker_row(num / source.fps, num, [], [], state["shape"] or (1, 1, 3))
+                rows[num] = row(num / source.fps, num, [], [], state["shape"] or (1, 1, 3), **emo(np.zeros((0, WIDTH - 512), np.float32), none))
     return rows, state["processed"]
 
 
