@@ -14,7 +14,8 @@ time stay those of the input.  --recog_emotion (-emt, -emtargs, -t2i, --topk_emo
 tags to the tracker (column Emotion, l.264-271) and to the 'emotions' field of the JSON, the mode the reference's own
 scripts run (scripts/celeb_stat_*.sh).  -sfr writes the annotated PNGs (boxes, names, emotion lines) on the host;
 -ov out.avi writes the annotated video of the sampled frames from the device (jpeg_encode.VideoEncoder: boxes, names
-and emotion lines drawn in HBM, --ov_quality, --ov_subsampling) at as many frames per second as -fidx keeps, so the
+and emotion lines drawn in HBM, --ov_quality, --ov_subsampling; --ov_entropy device runs the Huffman pass of the
+encoder in HIP too, the same files, default host) at as many frames per second as -fidx keeps, so the
 video lasts as long as the input.  Input: a directory of frames or a .npy array of (T,H,W,3) RGB frames with -fps, or
 a Motion-JPEG .avi (OpenCV / pafy are not installed: no other container decode, no YouTube); seq_fd_vs_aln (outside
 the hot path) is refused."""
@@ -95,7 +96,8 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
     return read_tracker_csv(args.output_tracker)
 
 
-if __name__ == '__main__':
+def make_parser():
+    """the command line of this script"""
     p = build_parser('Face recognition on a video')
     p.add_argument('-i', '--video_path', default='video.mp4', type=str)
     p.add_argument('-o', '--output_frame', default='output_frame', type=str)
@@ -121,7 +123,14 @@ if __name__ == '__main__':
     p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov (1..100)')
     p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
                    help='chroma subsampling of the frames of -ov')
+    p.add_argument('--ov_entropy', default='host', choices=['host', 'device'],
+                   help='where the Huffman pass of the frames of -ov runs: on host threads, or on the GPU (the same files)')
     p.set_defaults(recog_threshold=0.7)          # celeb_statistic.py:349 (demo_image's default is 0)
+    return p
+
+
+if __name__ == '__main__':
+    p = make_parser()
     args = p.parse_args()
     if args.youtube_video:
         raise SystemExit("--youtube_video needs pafy and network access, neither of which this build has")
@@ -164,7 +173,7 @@ if __name__ == '__main__':
         if args.output_video:
             from vn_celeb_face_recognition_amd.jpeg_encode import VideoEncoder
             encoder = VideoEncoder(args.output_video, float(max(kept_per_second, 1)), device, args.ov_quality,
-                                   args.ov_subsampling, rank, world, idx2tag=idx2etag)
+                                   args.ov_subsampling, rank, world, idx2tag=idx2etag, entropy=args.ov_entropy)
         try:
             tracker_df = main(args, pipe, rank, world, source, device=device, encoder=encoder, idx2etag=idx2etag)
         except BaseException:

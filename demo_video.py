@@ -15,7 +15,8 @@ GPU (jpeg.py: Huffman decode on host threads, IDCT / upsampling / colour in HIP)
 --host_decode keeps them on Pillow.  -ov x.avi WITHOUT -sfr never makes a PNG: boxes and names are drawn on the frames
 where they lie in HBM and the frames are JPEG-encoded there (jpeg_encode.py: overlay, colour, down-sampling, DCT and
 quantisation in HIP, the Huffman pass on host threads), the same files Pillow would write (--ov_quality,
---ov_subsampling)."""
+--ov_subsampling).  --ov_entropy device runs the Huffman pass in HIP as well (the same files; only they cross to the
+host, not the coefficients); the default is host."""
 import os
 import time
 
@@ -68,7 +69,8 @@ def main(args, pipe, rank, world, source=None, device=None, encoder=None):
         print('FPS for recognition face: {}'.format(int(processed / processed_time)))
 
 
-if __name__ == '__main__':
+def make_parser():
+    """the command line of this script"""
     p = build_parser('Face recognition on a video')
     p.add_argument('-i', '--video_path', default='video.mp4', type=str)
     p.add_argument('-o', '--output_frame', default='output_frame', type=str)
@@ -83,6 +85,13 @@ if __name__ == '__main__':
     p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov without -sfr (1..100)')
     p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
                    help='chroma subsampling of the frames of -ov without -sfr')
+    p.add_argument('--ov_entropy', default='host', choices=['host', 'device'],
+                   help='where the Huffman pass of the frames of -ov without -sfr runs: on host threads, or on the GPU (the same files)')
+    return p
+
+
+if __name__ == '__main__':
+    p = make_parser()
     args = p.parse_args()
     if args.inference_method != 'par_fd_vs_aln':
         raise SystemExit("use --inference_method par_fd_vs_aln (seq_fd_vs_aln needs the FAN landmark network, outside "
@@ -102,7 +111,8 @@ if __name__ == '__main__':
     encoder = None
     if device_video:
         from vn_celeb_face_recognition_amd.jpeg_encode import VideoEncoder
-        encoder = VideoEncoder(args.output_video, args.fps_video, device, args.ov_quality, args.ov_subsampling, rank, world)
+        encoder = VideoEncoder(args.output_video, args.fps_video, device, args.ov_quality, args.ov_subsampling, rank, world,
+                               entropy=args.ov_entropy)
     try:
         main(args, pipe, rank, world, device=device, encoder=encoder)
     except BaseException:

@@ -510,6 +510,35 @@ int vnf_jpeg_encode_frames(const uint8_t* frames_dev, int n, int width, int heig
 int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info* info, uint8_t* out, int64_t capacity,
                             int64_t* len_out);
 
+/* The same Huffman pass on the device (csrc/jpeg_huff_device.hip): a second back end that writes the same files, so that
+ * a frame's coefficients never cross to the host.  Sizes -> exclusive scan -> bit packing into a zeroed stream area ->
+ * FF count -> scan -> byte emission with stuffing; kernel boundaries are the only synchronisation between workgroups,
+ * and the result is bitwise repeatable. */
+/* The bytes SOI .. end of the SOS header of the file vnf_jpeg_entropy_encode writes for *info (623 of them; this is the
+ * code that call itself runs), into out[0, capacity); *len_out receives their count.  Host only, no HIP call.
+ * VNF_E_INVALID: a NULL pointer or an info vnf_jpeg_entropy_encode refuses; VNF_E_CAPACITY: capacity below *len_out --
+ * nothing was written outside [0, capacity). */
+int vnf_jpeg_huff_header(const vnf_jpeg_info* info, uint8_t* out, int64_t capacity, int64_t* len_out);
+/* bytes of device workspace vnf_jpeg_huff_encode_frames needs for n frames of *info with capacity_per_frame bytes of
+ * output each (the stream areas hold min(capacity_per_frame, the longest possible scan) bytes), or a negative VNF_E_*
+ * code (VNF_E_INVALID: n outside 0..65535, a negative capacity, an info vnf_jpeg_entropy_encode refuses, or a frame of
+ * 1658 * blocks >= 2^32 bits: bit offsets are 32-bit) */
+int64_t vnf_jpeg_huff_workspace_bytes(int n, const vnf_jpeg_info* info, int64_t capacity_per_frame);
+/* n frames of ONE info: coefs_dev device (n, info->coef_count) int16 as vnf_jpeg_encode_frames writes them, 16-byte
+ * aligned; header_dev: the bytes of vnf_jpeg_huff_header, on the device; out_dev: device (n, capacity_per_frame) u8;
+ * lengths_dev: device (n) int64; status_dev: device (n) int32; workspace: device, 16-byte aligned.  Frame i's file is
+ * out_dev[i * capacity_per_frame, + lengths_dev[i]) when status_dev[i] is VNF_OK; VNF_E_CAPACITY: the file does not fit
+ * and lengths_dev[i] is the length that would (the number vnf_jpeg_entropy_encode reports); VNF_E_INVALID: a
+ * coefficient outside the baseline range.  Bytes in [length, capacity) are unspecified; no byte at or past a frame's
+ * capacity is written; a frame's status never affects another frame.  Enqueued on `stream` (one memset, six launches),
+ * nothing allocated, no host synchronisation.  n == 0: no-op.
+ * Returns VNF_E_INVALID: n outside 0..65535, a NULL or misaligned pointer, an info vnf_jpeg_entropy_encode refuses,
+ * header_len other than vnf_jpeg_huff_header's; VNF_E_CAPACITY: workspace_bytes below
+ * vnf_jpeg_huff_workspace_bytes(...); VNF_E_HIP: a launch error. */
+int vnf_jpeg_huff_encode_frames(const int16_t* coefs_dev, int n, const vnf_jpeg_info* info, const uint8_t* header_dev,
+                                int64_t header_len, uint8_t* out_dev, int64_t capacity_per_frame, int64_t* lengths_dev,
+                                int32_t* status_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* frame overlay ---------------------------------------------------------------------------- */
 #define VNF_OVERLAY_RECT 0
 #define VNF_OVERLAY_LABEL 1

@@ -10,12 +10,17 @@ GPU:
   (c) what (b) is made of: the host entropy pass (per frame on one thread, and per batch across the pool) and the
       kernels' time per batch from HIP events;
   (d) the kernels' bytes (RGB in, planes out and in again, coefficients out) over their time, as a fraction of the
-      6.29 TB/s device copy rate.
+      6.29 TB/s device copy rate (DESIGN.md section 8);
+  (e) the device path with the Huffman pass on the device as well (BatchEncoder(entropy="device"),
+      csrc/jpeg_huff_device.hip) against (b), the two alternating inside one run: frames per second of both, the
+      Huffman kernels' time per batch from HIP events, the bytes per frame each copies to the host, and whether the two
+      wrote identical files.  --entropy_out writes this leg to a file of its own; --only_entropy skips (a) to (d).
 
 Input: 64 synthetic 1080p frames (synth.make_frames) with their pasted faces' rectangles as boxes, batches of 16.  Both
 paths end in the same JPEG files (checked on every frame of the warm-up pass).
 
     python tools/jpeg_encode_time.py [--frames 64] [--batch 16] [--passes 3] [--out profiles/jpeg_encode_time.txt]
+    python tools/jpeg_encode_time.py --only_entropy --entropy_out profiles/jpeg_huff_device_time.txt
 """
 import argparse
 import io
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--passes", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--entropy_out", default=None, help="where leg (e) is written")
+    ap.add_argument("--only_entropy", action="store_true", help="leg (e) alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_encode_time.py measures on the MI355X: no GPU is visible")
@@ -77,7 +84,7 @@ def main():
             if keep is not None:
                 keep.append(buf.getvalue())
 
-    def device_pass(keep=None, timings=None):
+    def device_pass(keep=None, timings=None, enc=enc):
         for k, idx in enumerate(batches):
             work[k].copy_(pristine[k])                                  # the overlay paints in place: a fresh batch every pass
             torch.cuda.synchronize()
@@ -98,11 +105,55 @@ def main():
             if tm is not None:
                 torch.cuda.synchronize()
                 timings.append({"overlay_ms": e0.elapsed_time(e1), "ops_s": t_ops, "n_ops": int(ops.shape[0]), "encode_ms": tm["kernel_events"][0].elapsed_time(tm["kernel_events"][1]),
-                                "entropy_s": enc.entropy_s, "info": job["info"]})
+                                "entropy_s": enc.entropy_s, "info": job["info"], "d2h": enc.d2h_bytes / len(idx),
+                                "huff_ms": tm["huff_events"][0].elapsed_time(tm["huff_events"][1]) if "huff_events" in tm else 0.0})
             if keep is not None:
                 keep.extend(files)
             yield dt
 
+    def entropy_leg():
+        dev_enc = jpeg_encode.BatchEncoder(DEV, QUALITY, SAMPLING, entropy="device")
+        fh, fd = [], []
+        list(device_pass(fh))                       # warm-up of both back ends, and the equality check
+        list(device_pass(fd, enc=dev_enc))
+        th, td, mh, md = [], [], [], []
+        for _ in range(args.passes):                # alternating: both see the same machine
+            th.append(sum(device_pass()))
+            td.append(sum(device_pass(enc=dev_enc)))
+        list(device_pass(timings=mh))
+        list(device_pass(timings=md, enc=dev_enc))
+        full = slice(0, max(1, len(md) - (1 if n % B else 0)))
+        info = md[0]["info"]
+        med = lambda rows, key: float(np.median([t[key] for t in rows[full]]))
+        rh, rd = n / min(th), n / min(td)
+        return [
+            "# (e) %d synthetic %dx%d annotated frames, quality %d %s (%.0f KB per frame), batches of %d, best of %d passes, the two back ends alternating"
+            % (n, info.width, info.height, QUALITY, SAMPLING, sum(len(d) for d in fd) / n / 1e3, B, args.passes),
+            "# both back ends wrote the same JPEG files for every frame: %s" % (fh == fd),
+            "(e) entropy=host    kernels, D2H of coefficients, Huffman pass on %d host threads            : %8.1f frames/s (%.2f ms per batch)"
+            % (jpeg_encode.ENTROPY_THREADS, rh, B / rh * 1e3),
+            "    entropy=device  kernels, Huffman kernels, D2H of the files                              : %8.1f frames/s (%.2f ms per batch)  = %.2f x host"
+            % (rd, B / rd * 1e3, rd / rh),
+            "    Huffman kernels (HIP events, memset + 6 launches): %.3f ms per batch of %d (%.1f us per frame); encode kernels %.3f ms"
+            % (med(md, "huff_ms"), B, med(md, "huff_ms") * 1e3 / B, med(md, "encode_ms")),
+            "    host time behind the kernels: entropy=host %.2f ms per batch (threaded Huffman pass), entropy=device %.2f ms (wait, copy of the files)"
+            % (med(mh, "entropy_s") * 1e3, med(md, "entropy_s") * 1e3),
+            "    D2H bytes per frame: entropy=host %.2f MB (coefficients), entropy=device %.2f MB (the file and its table entry)"
+            % (med(mh, "d2h") / 1e6, med(md, "d2h") / 1e6),
+        ]
+
+    def write(path, text):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write(text + "\n")
+
+    if args.only_entropy:
+        text = "\n".join(entropy_leg())
+        print(text)
+        write(args.entropy_out, text)
+        os.rmdir(tmp)
+        return
     ha, da = [], []
     host_pass(ha)                                   # warm-up of both paths, and the equality check
     list(device_pass(da))
@@ -151,10 +202,10 @@ def main():
     ]
     text = "\n".join(lines)
     print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    write(args.out, text)
+    leg_e = "\n".join(entropy_leg())
+    print(leg_e)
+    write(args.entropy_out, leg_e)
     for i in range(n):
         os.remove(os.path.join(tmp, "frame_%d.png" % (i + 1)))
     os.rmdir(tmp)

@@ -116,6 +116,10 @@ SIGNATURES = {
     "vnf_jpeg_encode_workspace_bytes": (ctypes.c_int64, [_I, _I, _I, _I]),
     "vnf_jpeg_encode_frames": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64, _P]),
     "vnf_jpeg_entropy_encode": (_I, [_P, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "vnf_jpeg_huff_header": (_I, [ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "vnf_jpeg_huff_workspace_bytes": (ctypes.c_int64, [_I, ctypes.POINTER(JpegInfo), ctypes.c_int64]),
+    "vnf_jpeg_huff_encode_frames": (_I, [_P, _I, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P,
+                                        ctypes.c_int64, _P]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }

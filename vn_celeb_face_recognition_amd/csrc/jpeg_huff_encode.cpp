@@ -7,18 +7,17 @@
 // Motion-JPEG output.  Written from the JPEG standard (ITU-T T.81: B.2 marker segments, C Huffman table generation,
 // F.1.2 encoding procedures, K.1 / K.3 the "typical" quantisation and Huffman tables) and the JFIF 1.01 APP0 layout; the
 // quality scaling of the tables is libjpeg's public rule.  No HIP call and no dependency on the rest of the library, so
-// the file also compiles into a stand-alone checker (tools/jpeg_huff_encode_check.cpp).  Every write is checked against
+// the file also compiles into the stand-alone checkers (tools/jpeg_huff_encode_check.cpp, tools/jpeg_huff_device_check.cpp).  Every write is checked against
 // `capacity`, and no state is shared between calls (thread-safe).
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/vnface.h"
+#include "jpeg_huff_tables.h"
 
 namespace {
 
-constexpr uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using namespace vnf::huff;   // zigzag order, annex K.3 tables and codes, the walk over a block
 
 // T.81 K.1: luminance, chrominance, natural order
 constexpr uint8_t kBaseQuant[2][64] = {
@@ -26,46 +25,6 @@ constexpr uint8_t kBaseQuant[2][64] = {
      18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-
-// T.81 K.3: code counts per length 1..16, then the symbols in code order
-constexpr uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-constexpr uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-constexpr uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
-constexpr uint8_t kAcVals[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
-     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
-     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
-     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
-     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
-     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
-     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
-     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
-     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
-     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
-     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
-     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
-     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa}};
-
-struct Codes {
-  uint16_t code[256];
-  uint8_t len[256];  // 0: the table has no code for this symbol
-};
-
-// T.81 annex C: counts per length -> the canonical code of every symbol
-void build_codes(Codes& c, const uint8_t counts[16], const uint8_t* syms) {
-  memset(&c, 0, sizeof(c));
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; ++l) {
-    for (int i = 0; i < counts[l - 1]; ++i, ++k, ++code) {
-      c.code[syms[k]] = (uint16_t)code;
-      c.len[syms[k]] = (uint8_t)l;
-    }
-    code <<= 1;
-  }
-}
 
 // Byte sink over out[0, cap): a byte past the end is counted, not written.
 struct Sink {
@@ -114,11 +73,6 @@ struct Sink {
     }
   }
 };
-
-inline int category(int v) {  // bits of |v|
-  const unsigned a = (unsigned)(v < 0 ? -v : v);
-  return a ? 32 - __builtin_clz(a) : 0;
-}
 
 bool geometry(int width, int height, int sampling, int* h0, int* v0, int bw[3], int bh[3], int64_t* count) {
   switch (sampling) {
@@ -176,23 +130,28 @@ extern "C" int vnf_jpeg_encode_info(int width, int height, int sampling, int qua
   return VNF_OK;
 }
 
-extern "C" int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info* info, uint8_t* out, int64_t capacity,
-                                       int64_t* len_out) {
-  if (!coefs || !info || !len_out || capacity < 0 || (!out && capacity > 0)) return VNF_E_INVALID;
-  int h0, v0, bw[3], bh[3];
+namespace {
+
+// what the Huffman pass accepts: three components, no restart interval, the geometry vnf_jpeg_encode_info gives for
+// this size and sampling, one table for both chroma components, no zero quantiser
+bool valid_info(const vnf_jpeg_info* info, int bw[3], int bh[3]) {
+  int h0, v0;
   int64_t count;
   if (info->components != 3 || info->restart_interval != 0 ||
       !geometry(info->width, info->height, info->sampling, &h0, &v0, bw, bh, &count) || count != info->coef_count)
-    return VNF_E_INVALID;
+    return false;
   for (int c = 0; c < 3; ++c)
     if (info->blocks_w[c] != bw[c] || info->blocks_h[c] != bh[c] || info->h[c] != (c ? 1 : h0) || info->v[c] != (c ? 1 : v0))
-      return VNF_E_INVALID;
+      return false;
   // two tables are written: luma's and the one both chroma components share
-  if (memcmp(info->quant[1], info->quant[2], 64) != 0) return VNF_E_INVALID;
+  if (memcmp(info->quant[1], info->quant[2], 64) != 0) return false;
   for (int i = 0; i < 64; ++i)
-    if (!info->quant[0][i] || !info->quant[1][i]) return VNF_E_INVALID;
+    if (!info->quant[0][i] || !info->quant[1][i]) return false;
+  return true;
+}
 
-  Sink s{out, capacity};
+// SOI .. the end of the SOS header
+void write_header(Sink& s, const vnf_jpeg_info* info) {
   s.be16(0xFFD8);
   static const uint8_t app0[16] = {0x00, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};  // JFIF 1.01, aspect 1:1
   s.be16(0xFFE0);
@@ -213,11 +172,6 @@ extern "C" int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info
     s.byte(c + 1);
     s.byte((info->h[c] << 4) | info->v[c]);
     s.byte(c ? 1 : 0);
-  }
-  Codes dc[2], ac[2];
-  for (int t = 0; t < 2; ++t) {
-    build_codes(dc[t], kDcBits[t], kDcVals);
-    build_codes(ac[t], kAcBits[t], kAcVals[t]);
   }
   for (int t = 0; t < 2; ++t) {  // DC 0, AC 0, DC 1, AC 1, each in a segment of its own
     s.be16(0xFFC4);
@@ -241,6 +195,29 @@ extern "C" int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info
   s.byte(0);
   s.byte(63);
   s.byte(0);
+}
+
+}  // namespace
+
+extern "C" int vnf_jpeg_huff_header(const vnf_jpeg_info* info, uint8_t* out, int64_t capacity, int64_t* len_out) {
+  if (!info || !len_out || capacity < 0 || (!out && capacity > 0)) return VNF_E_INVALID;
+  int bw[3], bh[3];
+  if (!valid_info(info, bw, bh)) return VNF_E_INVALID;
+  Sink s{out, capacity};
+  write_header(s, info);
+  *len_out = s.pos;
+  return s.pos > capacity ? VNF_E_CAPACITY : VNF_OK;
+}
+
+extern "C" int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info* info, uint8_t* out, int64_t capacity,
+                                       int64_t* len_out) {
+  if (!coefs || !info || !len_out || capacity < 0 || (!out && capacity > 0)) return VNF_E_INVALID;
+  int bw[3], bh[3];
+  if (!valid_info(info, bw, bh)) return VNF_E_INVALID;
+
+  Sink s{out, capacity};
+  write_header(s, info);
+  auto put = [&s](uint32_t v, int k) { s.bits(v, k); };
 
   int64_t plane[3] = {0, 0, 0};
   for (int c = 1; c < 3; ++c) plane[c] = plane[c - 1] + (int64_t)64 * bw[c - 1] * bh[c - 1];
@@ -249,30 +226,13 @@ extern "C" int vnf_jpeg_entropy_encode(const int16_t* coefs, const vnf_jpeg_info
   for (int y = 0; y < my; ++y) {
     for (int x = 0; x < mx; ++x) {
       for (int c = 0; c < 3; ++c) {
-        const Codes& hd = dc[c ? 1 : 0];
-        const Codes& ha = ac[c ? 1 : 0];
+        const Codes& hd = kTables.dc[c ? 1 : 0];
+        const Codes& ha = kTables.ac[c ? 1 : 0];
         for (int by = 0; by < info->v[c]; ++by) {
           for (int bx = 0; bx < info->h[c]; ++bx) {
             const int16_t* blk = coefs + plane[c] + ((int64_t)(y * info->v[c] + by) * bw[c] + (x * info->h[c] + bx)) * 64;
-            // T.81 F.1.2.1: the DC difference, its category's code, then the low bits (one's complement when negative)
-            const int diff = (int)blk[0] - pred[c];
+            if (!encode_block(blk, pred[c], hd, ha, put)) return VNF_E_INVALID;
             pred[c] = blk[0];
-            int cat = category(diff);
-            if (cat > 11) return VNF_E_INVALID;
-            s.bits(((uint32_t)hd.code[cat] << cat) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << cat) - 1u)), hd.len[cat] + cat);
-            // F.1.2.2: (run, size) symbols, ZRL for runs of 16 zeros, EOB when the rest is zero
-            int run = 0;
-            for (int k = 1; k < 64; ++k) {
-              const int v = blk[kZigzag[k]];
-              if (!v) { ++run; continue; }
-              while (run > 15) { s.bits(ha.code[0xF0], ha.len[0xF0]); run -= 16; }
-              cat = category(v);
-              if (cat > 10) return VNF_E_INVALID;
-              const int sym = (run << 4) | cat;
-              s.bits(((uint32_t)ha.code[sym] << cat) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u)), ha.len[sym] + cat);
-              run = 0;
-            }
-            if (run) s.bits(ha.code[0x00], ha.len[0x00]);
           }
         }
       }

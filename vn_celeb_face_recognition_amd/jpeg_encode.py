@@ -9,7 +9,9 @@ read it:
     masks are rendered by Pillow's own font code, so the glyphs are Pillow's);
   * colour conversion, chroma down-sampling, forward DCT and quantisation run on the MI355X (csrc/jpeg_encode.hip);
   * one D2H copy brings the coefficients (not the pixels) into pinned memory, and the serial Huffman pass
-    (csrc/jpeg_huff_encode.cpp) runs on a few host threads, one frame each (ctypes releases the GIL).
+    (csrc/jpeg_huff_encode.cpp) runs on a few host threads, one frame each (ctypes releases the GIL);
+  * or, with entropy="device", the Huffman pass runs on the MI355X as well (csrc/jpeg_huff_device.hip) and only the
+    finished files cross to the host.  It writes the same bytes; "host" is the default.
 
 The files are libjpeg's (and so Pillow's `save(format="JPEG", quality=q, subsampling=s)`) byte for byte.
 """
@@ -25,6 +27,7 @@ from . import _lib
 from .jpeg import S420, S422, S444
 
 SAMPLINGS = {"4:4:4": S444, "4:2:2": S422, "4:2:0": S420}
+ENTROPY = ("host", "device")                    # where the Huffman pass runs; both write the same files
 ENTROPY_THREADS = 8                             # fixed: the frames of a batch, never sized from the machine's CPU count
 RECT, LABEL = 0, 1                              # VNF_OVERLAY_*
 GREEN = (0, 255, 0)                             # cli_utils.draw_boxes_on_image
@@ -49,6 +52,12 @@ def sampling_code(sampling):
     if sampling in SAMPLINGS.values():
         return int(sampling)
     raise ValueError("sampling must be one of %s, got %r" % (", ".join(SAMPLINGS), sampling))
+
+
+def entropy_mode(entropy):
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be one of %s, got %r" % (", ".join(ENTROPY), entropy))
+    return entropy
 
 
 def quant_tables(quality):
@@ -84,6 +93,34 @@ def entropy_encode(coefs, info):
     raise _lib.VnfError("vnf_jpeg_entropy_encode failed (%d): a coefficient outside the baseline range or a bad info" % rc)
 
 
+def huff_header(info):
+    """the bytes SOI .. end of the SOS header of the file entropy_encode writes for `info` -> (623,) u8"""
+    out = np.zeros((1024,), np.uint8)
+    n = ctypes.c_int64()
+    _lib.check(_lib.load().vnf_jpeg_huff_header(ctypes.byref(info), out.ctypes.data, out.size, ctypes.byref(n)))
+    return out[:n.value].copy()
+
+
+def huff_workspace_bytes(n, info, capacity):
+    ws = int(_lib.load().vnf_jpeg_huff_workspace_bytes(int(n), ctypes.byref(info), int(capacity)))
+    if ws < 0:
+        _lib.check(ws)
+    return ws
+
+
+def huff_encode_frames(coefs_dev, n, info, header_dev, out_dev, capacity, lengths_dev, status_dev, workspace, stream_ptr=None):
+    """vnf_jpeg_huff_encode_frames on torch tensors: coefs_dev (n * info.coef_count) int16 cuda as encode_frames leaves
+    them; header_dev: huff_header(info) on the device; out_dev: (n * capacity) u8; lengths_dev (n) int64; status_dev
+    (n) int32; enqueues on `stream_ptr` (default: the current stream)."""
+    ts = (coefs_dev, header_dev, out_dev, lengths_dev, status_dev, workspace)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("jpeg_encode.huff_encode_frames needs cuda tensors (there is no CPU path)")
+    _lib.check(_lib.load().vnf_jpeg_huff_encode_frames(
+        coefs_dev.data_ptr(), int(n), ctypes.byref(info), header_dev.data_ptr(), int(header_dev.numel()), out_dev.data_ptr(),
+        int(capacity), lengths_dev.data_ptr(), status_dev.data_ptr(), workspace.data_ptr(),
+        workspace.numel() * workspace.element_size(), stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+
+
 def encode_frames(frames_dev, quant_dev, coefs_out, workspace, sampling, stream_ptr=None):
     """vnf_jpeg_encode_frames on torch tensors: frames_dev (n,H,W,3) u8 cuda, contiguous; enqueues on `stream_ptr`
     (default: the current stream)."""
@@ -100,23 +137,65 @@ def encode_frames(frames_dev, quant_dev, coefs_out, workspace, sampling, stream_
 
 
 class BatchEncoder:
-    """Buffers of one (device, quality, sampling): the tables on the device, and -- grown to the largest batch seen --
-    the coefficient and plane buffers and the pinned landing area of the one D2H copy."""
+    """Buffers of one (device, quality, sampling, entropy): the tables on the device, and -- grown to the largest batch
+    seen -- the coefficient and plane buffers and, with entropy="host", the pinned landing area of the one D2H copy of
+    the coefficients; with entropy="device", the Huffman workspace, the files on the device and their pinned landing
+    area (no pinned coefficient buffer, and the thread pool is not touched)."""
 
-    def __init__(self, device, quality=92, sampling="4:2:0"):
+    def __init__(self, device, quality=92, sampling="4:2:0", entropy="host"):
         import torch
+        self.entropy = entropy_mode(entropy)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("BatchEncoder needs a cuda device (there is no CPU path)")
         self.quality, self.sampling = int(quality), sampling_code(sampling)
         self.quant = torch.from_numpy(quant_tables(self.quality)).to(self.device)
         self._coefs = self._ws = self._host = None
-        self.entropy_s = 0.0                    # host wall time of the last batch's threaded entropy pass (tools)
+        self._hws = self._files = self._table = self._table_host = self._files_host = None
+        self._headers = {}                      # (width, height) -> the file header on the device
+        self.entropy_s = 0.0                    # host wall time of the last batch's entropy pass: the threaded Huffman
+        #                                         pass ("host"), or all of `finish` ("device") (tools)
+        self.d2h_bytes = 0                      # what the last batch copied to the host (tools)
+
+    def _grown(self, t, count, dtype, pinned=False):
+        import torch
+        if t is not None and t.numel() >= count:
+            return t
+        if pinned:
+            return torch.empty((count,), dtype=dtype).pin_memory()
+        return torch.empty((count,), dtype=dtype, device=self.device)
+
+    def _huff_enqueue(self, job, capacity, stream):
+        """the Huffman kernels for `job` at `capacity` bytes per frame and the copy of the (length, status) table, on
+        `stream`, which is the current one"""
+        import torch
+        n, info = job["n"], job["info"]
+        key = (int(info.width), int(info.height))
+        if key not in self._headers:
+            self._headers[key] = torch.from_numpy(huff_header(info)).to(self.device)
+        self._hws = self._grown(self._hws, huff_workspace_bytes(n, info, capacity), torch.uint8)
+        self._files = self._grown(self._files, n * capacity, torch.uint8)
+        self._table = self._grown(self._table, 2 * n, torch.int64)          # n lengths, then n int32 statuses
+        self._table_host = self._grown(self._table_host, 2 * n, torch.int64, pinned=True)
+        timed = job.get("timing") is not None and job["timing"].get("events")
+        if timed:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        huff_encode_frames(self._coefs, n, info, self._headers[key], self._files, capacity, self._table[:n],
+                           self._table[n:2 * n].view(torch.int32), self._hws, ctypes.c_void_p(stream.cuda_stream))
+        if timed:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record(stream)
+            job["timing"]["huff_events"] = (e0, e1)
+        self._table_host[:2 * n].copy_(self._table[:2 * n], non_blocking=True)
+        job["capacity"] = capacity
+        job["copied"] = stream.record_event()
 
     def enqueue(self, frames_dev, stream=None, timing=None):
-        """kernels + the D2H copy of the coefficients on `stream` (default: the current one) -> a handle for `finish`.
-        timing: optional dict; with timing["events"] set it receives 'kernel_events', two timed events around the
-        kernels."""
+        """kernels + the D2H copy of the coefficients (entropy="host") or the Huffman kernels + the D2H copy of the
+        files' lengths (entropy="device") on `stream` (default: the current one) -> a handle for `finish`.
+        timing: optional dict; with timing["events"] set it receives 'kernel_events' (and 'huff_events'), two timed
+        events around the kernels."""
         import torch
         n, h, w = (int(s) for s in frames_dev.shape[:3])
         info = encode_info(w, h, self.sampling, self.quality)
@@ -125,12 +204,13 @@ class BatchEncoder:
         if ws < 0:
             _lib.check(ws)
         stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+        job = {"n": n, "cc": cc, "info": info, "stream": stream, "timing": timing}
         with torch.cuda.stream(stream):
             if self._coefs is None or self._coefs.numel() < n * cc:
                 self._coefs = torch.empty((n * cc,), dtype=torch.int16, device=self.device)
             if self._ws is None or self._ws.numel() < ws:
                 self._ws = torch.empty((ws,), dtype=torch.uint8, device=self.device)
-            if self._host is None or self._host.numel() < n * cc:
+            if self.entropy == "host" and (self._host is None or self._host.numel() < n * cc):
                 self._host = torch.empty((n * cc,), dtype=torch.int16).pin_memory()
             if timing is not None and timing.get("events"):
                 e0 = torch.cuda.Event(enable_timing=True)
@@ -140,42 +220,88 @@ class BatchEncoder:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record(stream)
                 timing["kernel_events"] = (e0, e1)
-            kernels = stream.record_event()
-            self._host[:n * cc].copy_(self._coefs[:n * cc], non_blocking=True)
-            copied = stream.record_event()
-        return {"n": n, "cc": cc, "info": info, "kernels": kernels, "copied": copied}
+            job["kernels"] = stream.record_event()
+            if self.entropy == "host":
+                self._host[:n * cc].copy_(self._coefs[:n * cc], non_blocking=True)
+                job["copied"] = stream.record_event()
+            elif n:
+                self._huff_enqueue(job, 1024 + cc, stream)     # a byte per coefficient: entropy_encode's own first guess
+        return job
 
     def finish(self, job):
-        """wait for the copy, entropy-encode the frames on the pool -> list of JPEG files (bytes)"""
+        """wait for the copy, entropy-encode the frames on the pool -> list of JPEG files (bytes); entropy="device":
+        wait for the lengths, copy exactly that many bytes of every file to pinned memory, one synchronise"""
         import time
+        if self.entropy == "device":
+            t0 = time.perf_counter()
+            out = self._finish_device(job)
+            self.entropy_s = time.perf_counter() - t0
+            return out
         job["copied"].synchronize()
         n, cc, info = job["n"], job["cc"], job["info"]
         host = self._host.numpy()[:n * cc].reshape(n, cc)
+        self.d2h_bytes = 2 * n * cc
         t0 = time.perf_counter()
         one = lambda i: entropy_encode(host[i], info)
         out = list(_entropy_pool().map(one, range(n))) if n > 1 else [one(0)]
         self.entropy_s = time.perf_counter() - t0
         return out
 
+    def _finish_device(self, job):
+        import torch
+        n, stream = job["n"], job["stream"]
+        if n == 0:
+            return []
+        self.d2h_bytes = 0
+        for attempt in range(2):
+            job["copied"].synchronize()
+            self.d2h_bytes += 16 * n
+            table = self._table_host.numpy()
+            lengths = [int(v) for v in table[:n]]
+            status = [int(v) for v in table[n:2 * n].view(np.int32)[:n]]
+            bad = [st for st in status if st not in (0, -4)]
+            if bad or (attempt and any(status)):
+                raise _lib.VnfError("vnf_jpeg_huff_encode_frames failed (%d): a coefficient outside the baseline range or "
+                                    "a bad info" % (bad[0] if bad else -4))
+            if not any(status):
+                break
+            with torch.cuda.stream(stream):                  # VNF_E_CAPACITY reports the size that fits: once more, for
+                self._huff_enqueue(job, max(lengths), stream)  # the batch, from the coefficients still in _coefs
+        cap, total = job["capacity"], sum(lengths)
+        with torch.cuda.stream(stream):
+            self._files_host = self._grown(self._files_host, total, torch.uint8, pinned=True)
+            at = 0
+            for i, ln in enumerate(lengths):
+                self._files_host[at:at + ln].copy_(self._files[i * cap:i * cap + ln], non_blocking=True)
+                at += ln
+        stream.synchronize()
+        self.d2h_bytes += total
+        host, out, at = self._files_host.numpy(), [], 0
+        for ln in lengths:
+            out.append(host[at:at + ln].tobytes())
+            at += ln
+        return out
+
     def encode(self, frames_dev, stream=None):
         return self.finish(self.enqueue(frames_dev, stream))
 
 
-# one BatchEncoder per (device, quality, sampling) a caller of encode_batch_device has used, kept for the life of the
+# one BatchEncoder per (device, quality, sampling, entropy) a caller of encode_batch_device has used, kept for the life of the
 # process: each holds the device coefficient / plane buffers and the pinned landing area of its largest batch (about
 # 9.4 MB + 6.3 MB pinned per 1080p 4:2:0 frame).  A caller that cycles through settings or wants the memory back owns
 # a BatchEncoder itself and drops it.
 _encoders = {}
 
 
-def encode_batch_device(frames_dev, quality=92, sampling="4:2:0", stream=None):
+def encode_batch_device(frames_dev, quality=92, sampling="4:2:0", stream=None, entropy="host"):
     """frames_dev: (n,H,W,3) u8 cuda tensor -> a list of n JPEG files (bytes), the ones Pillow writes for these pixels
     with save(format="JPEG", quality=quality, subsampling=sampling).  stream: a torch stream, or an object with a
-    `.stream` (upload.FrameUploader); default: the current stream.  Synchronises with the host (one D2H copy)."""
+    `.stream` (upload.FrameUploader); default: the current stream.  entropy: "host" (the Huffman pass on host threads)
+    or "device" (in HIP; the same files).  Synchronises with the host (one D2H copy, or one per file)."""
     stream = getattr(stream, "stream", stream)
-    key = (str(frames_dev.device), int(quality), sampling_code(sampling))
+    key = (str(frames_dev.device), int(quality), sampling_code(sampling), entropy_mode(entropy))
     if key not in _encoders:
-        _encoders[key] = BatchEncoder(frames_dev.device, quality, sampling)
+        _encoders[key] = BatchEncoder(frames_dev.device, quality, sampling, entropy)
     return _encoders[key].encode(frames_dev, stream)
 
 
@@ -494,17 +620,18 @@ class VideoEncoder:
     order, to a Motion-JPEG AVI (one process) or to this rank's spool file `<path>.rank<r>.part` (several; rank 0
     merges them with `merge` once every rank has closed its own)."""
 
-    def __init__(self, path, fps, device, quality=92, sampling="4:2:0", rank=0, world=1, idx2tag=None):
-        """idx2tag: the emotion tag table (index -> tag) for write_batch(emotions=...) called with class indices, as
+    def __init__(self, path, fps, device, quality=92, sampling="4:2:0", rank=0, world=1, idx2tag=None, entropy="host"):
+        """entropy: where the Huffman pass runs, "host" or "device" (BatchEncoder).  idx2tag: the emotion tag table (index -> tag) for write_batch(emotions=...) called with class indices, as
         video.run_stream(emotions=k) calls it; None: the tags are drawn as they are handed over."""
         import torch
         from .mjpeg_avi import MjpegAviWriter
         from .streams import side_stream
+        entropy_mode(entropy)
         if not str(path).lower().endswith(".avi"):
             raise ValueError("the device encoder writes a Motion-JPEG AVI: give the video a name ending in .avi, got %r" % (path,))
         self.path, self.fps, self.rank, self.world = str(path), float(fps), int(rank), int(world)
         self.device = torch.device(device)
-        self.enc = BatchEncoder(self.device, quality, sampling)
+        self.enc = BatchEncoder(self.device, quality, sampling, entropy)
         self.stream = side_stream(self.device, ENCODE_STREAM_ROLE)
         self.frames = 0
         self.idx2tag = idx2tag
