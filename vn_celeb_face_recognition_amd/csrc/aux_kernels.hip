@@ -2,6 +2,7 @@
 // All are coalesced streaming kernels (16-byte accesses along the NHWC channel axis).
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 #include "kernels.h"
 #include "storage_unit.h"
 
@@ -202,9 +203,177 @@ __global__ void __launch_bounds__(256) stem_conv1a_mfma_kernel(const TI* __restr
   }
 }
 
+// The MFMA form fed from LDS-staged input rows.  Above, every lane gathers its 7 taps with 7 two-byte global loads per
+// 16-pixel group: ~700 k divergent wave-level gathers per 256 images, every input element pulled 2.2 times, and a wave
+// waits for its 28 loads before its 56 MFMAs.  Here a band is R = 4 output rows of one image, one row per wave: the
+// 3 x 9 input rows it touches are contiguous per channel, so they arrive with coalesced 16-byte loads and sit in LDS
+// as raw TI elements, [c][row][160] (8.6 KB for 2-byte crops, 17.3 KB for fp32 crops).  Workgroups are persistent
+// (4 per CU, 5 bands each at 256 images) and the LDS is two such buffers: the next band's loads are issued before the
+// current band's MFMAs and written to the other buffer after them, one barrier per band.
+// A group is 16 consecutive pixels of the wave's row (5 per row, the last with 15): lane (pixel, g) reads its 7 taps
+// from LDS -- the 16 pixels of a tap hit 16 different banks (2-byte crops; every other bank for fp32), kw neighbours
+// share a dword, kh neighbours sit 80 dwords on.  With the row fixed per wave and the group and buffer unrolled, every
+// tap address is one per-lane register (set once per kernel) plus an immediate: besides the MFMAs a group costs its 7
+// conversions and the epilogue, which is what lets the vector issue of four waves fit under the MFMA pipe (with the
+// addresses computed per group, 6 vector instructions per MFMA, the two added up: 46 us of which 18 us MFMA).
+// MFMAs of 3 (then 2) groups are interleaved k-step by k-step, so no accumulator is needed within its 40-cycle latency.
+// The arithmetic is the kernel above's, operand for operand: wa[ct][t] with k = 4t + g as A, bias as the initial
+// accumulator, the padding slot k = 27 reading tap 0 against a zero weight, the same ReLU / conversion / lane-row swap /
+// 16-byte store -- so the tensor is bit-identical.  Needs x 16-byte aligned (row and channel starts then are too); the
+// launcher falls back to the gather form otherwise.
+struct Stem1aRows { static constexpr int R = 4, NB = (79 + R - 1) / R; };   // output rows per band, bands per image
+
+template <typename TI, typename TO>
+__global__ void __launch_bounds__(256) stem_conv1a_rows_kernel(const TI* __restrict__ x, TO* __restrict__ y, int ldy, int n,
+                                                               const float* __restrict__ wt) {
+  constexpr int S = 160, SO = 79, NPX = SO * SO, R = Stem1aRows::R, NB = Stem1aRows::NB, ES = (int)sizeof(TI);
+  static_assert(R == 4, "one output row per wave");
+  constexpr int RI = 2 * R + 1, CS = RI * S;             // input rows of a full band; LDS channel stride in elements
+  constexpr int RC = S * ES / 16, CSC = CS * ES / 16;    // 16-byte chunks per input row / per LDS channel
+  constexpr int NLD = (3 * RI * RC + 255) / 256;         // chunks per thread
+  // a buffer and 16 bytes: lane 15 of a row's last group (pixel 79, not stored) reads up to one element past the rows
+  constexpr int BUFB = 3 * CS * ES + 16;
+  typedef unsigned u4 __attribute__((ext_vector_type(4)));
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) char sm[2 * BUFB];
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nbands = n * NB;
+  u4 v[NLD];
+  // band b = (image, rows oy0 .. oy0 + rows): its 2 rows + 1 input rows are contiguous per channel (cpc chunks), and
+  // 2 oy0 + 2 rows <= 158, so every staged row is in the image
+  auto fetch = [&](int b) {
+    const int img = b / NB, oy0 = (b - img * NB) * R;
+    const int cpc = (2 * min(R, SO - oy0) + 1) * RC;
+    const u4* src = reinterpret_cast<const u4*>(x + (size_t)img * 3 * S * S + (size_t)(2 * oy0) * S);
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int q = min(tid + j * 256, 3 * cpc - 1);       // past the end: the last chunk again, not stored
+      const int c = (q >= cpc) + (q >= 2 * cpc);
+      v[j] = src[c * (S * S * ES / 16) + q - c * cpc];
+    }
+  };
+  auto stash = [&](int b, int buf) {
+    const int oy0 = (b % NB) * R;
+    const int cpc = (2 * min(R, SO - oy0) + 1) * RC;
+#pragma unroll
+    for (int j = 0; j < NLD; ++j) {
+      const int q = tid + j * 256;
+      const int c = (q >= cpc) + (q >= 2 * cpc);
+      if (q < 3 * cpc) reinterpret_cast<u4*>(sm + buf * BUFB)[c * CSC + q - c * cpc] = v[j];
+    }
+  };
+  int band = blockIdx.x;
+  if (band >= nbands) return;
+  float wa[2][7], bias[2][4];
+  int la[7];   // byte offset in a buffer of tap k = 4t + g of this lane's pixel in the wave's row, group 0
+#pragma unroll
+  for (int t = 0; t < 7; ++t) {
+    const int k = 4 * t + g;
+    wa[0][t] = k < 27 ? wt[k * 32 + col] : 0.f;
+    wa[1][t] = k < 27 ? wt[k * 32 + 16 + col] : 0.f;
+    la[t] = (2 * wave * S + 2 * col + (k < 27 ? (k / 9) * CS + ((k % 9) / 3) * S + k % 3 : 0)) * ES;
+  }
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bias[ct][e] = wt[27 * 32 + 16 * ct + 4 * g + e];
+  const int cst = (g & 1) * 16 + (g >> 1) * 8;   // the 8 channels this lane stores after the swap
+  fetch(band);
+  stash(band, 0);
+  // nothing of the prologue is pending inside the band loop: the compiler would otherwise drain the vector-memory
+  // counter in front of the MFMAs (which read wa) and with it the next band's loads
+  __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
+
+  // groups J0 .. J0 + NJ of the wave's row, from buffer BUF
+  auto groups = [&](auto buf_c, auto j0_c, auto nj_c, unsigned row0) {
+    constexpr int BUF = decltype(buf_c)::value, J0 = decltype(j0_c)::value, NJ = decltype(nj_c)::value;
+    float xb[NJ][7];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int t = 0; t < 7; ++t)
+        xb[j][t] = to_f(*reinterpret_cast<const TI*>(sm + la[t] + (BUF * BUFB + (J0 + j) * 32 * ES)));
+    f4 a0[NJ], a1[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      a0[j] = f4{bias[0][0], bias[0][1], bias[0][2], bias[0][3]};
+      a1[j] = f4{bias[1][0], bias[1][1], bias[1][2], bias[1][3]};
+    }
+#pragma unroll
+    for (int t = 0; t < 7; ++t)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        a0[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][t], xb[j][t], a0[j], 0, 0, 0);
+        a1[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][t], xb[j][t], a1[j], 0, 0, 0);
+      }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const unsigned i = row0 + (J0 + j) * 16 + col;
+      const bool ok = (J0 + j + 1) * 16 <= SO || col < SO - (J0 + j) * 16;
+      if constexpr (__is_same(TO, pf16)) {
+        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+        h4 h0, l0, h1, l1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const sf16 s0(fmaxf(a0[j][e], 0.f)), s1(fmaxf(a1[j][e], 0.f));
+          h0[e] = s0.hi; l0[e] = s0.lo;
+          h1[e] = s1.hi; l1[e] = s1.lo;
+        }
+        const uint2 ph0 = __builtin_bit_cast(uint2, h0), ph1 = __builtin_bit_cast(uint2, h1);
+        const uint2 pl0 = __builtin_bit_cast(uint2, l0), pl1 = __builtin_bit_cast(uint2, l1);
+        const auto hx = __builtin_amdgcn_permlane16_swap(ph0.x, ph1.x, false, false);
+        const auto hy = __builtin_amdgcn_permlane16_swap(ph0.y, ph1.y, false, false);
+        const auto lx = __builtin_amdgcn_permlane16_swap(pl0.x, pl1.x, false, false);
+        const auto ly = __builtin_amdgcn_permlane16_swap(pl0.y, pl1.y, false, false);
+        if (ok) {
+          char* d = reinterpret_cast<char*>(y) + ((size_t)i * ldy + cst) * 4;
+          *reinterpret_cast<uint4*>(d) = uint4{hx[0], hy[0], hx[1], hy[1]};
+          *reinterpret_cast<uint4*>(d + 16) = uint4{lx[0], ly[0], lx[1], ly[1]};
+        }
+      } else {
+        typedef TO t4 __attribute__((ext_vector_type(4)));
+        t4 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o0[e] = (TO)fmaxf(a0[j][e], 0.f); o1[e] = (TO)fmaxf(a1[j][e], 0.f); }
+        const uint2 p0 = __builtin_bit_cast(uint2, o0), p1 = __builtin_bit_cast(uint2, o1);
+        const auto sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
+        const auto sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
+        if (ok) *reinterpret_cast<uint4*>(y + (size_t)i * ldy + cst) = uint4{sx[0], sy[0], sx[1], sy[1]};
+      }
+    }
+  };
+  // one band out of buffer BUF; false when it was this workgroup's last
+  auto one_band = [&](auto buf_c) {
+    constexpr int BUF = decltype(buf_c)::value;
+    const int next = band + gridDim.x;
+    if (next < nbands) fetch(next);            // in flight under this band's MFMAs
+    // this band's rows are visible; every wave is past its reads of the other buffer (the band before)
+    __syncthreads();
+    const int img = band / NB, oy0 = (band - img * NB) * R;
+    if (wave < min(R, SO - oy0)) {             // the image's last band has 3 rows
+      const unsigned row0 = (unsigned)img * NPX + (unsigned)((oy0 + wave) * SO);
+      groups(buf_c, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{}, row0);
+      groups(buf_c, std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{}, row0);
+    }
+    if (next < nbands) stash(next, BUF ^ 1);   // visible after the next band's barrier
+    band = next;
+    return next < nbands;
+  };
+  while (one_band(std::integral_constant<int, 0>{}) && one_band(std::integral_constant<int, 1>{})) {}
+}
+
+// mode (VNF_STEM1A_MFMA): 2 = MFMA from LDS-staged rows, 1 = MFMA with per-lane gathers, 0 = VALU
 template <typename TI>
-static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, int n, const float* wt, bool mfma, hipStream_t s) {
-  if (mfma && n > 0 && (dtype == BF16 || dtype == F16 || dtype == F16P)) {
+static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, int n, const float* wt, int mode, hipStream_t s) {
+  if (mode >= 2 && n > 0 && (dtype == BF16 || dtype == F16 || dtype == F16P) && ((uintptr_t)x & 15) == 0) {
+    const int blocks = std::min(n * Stem1aRows::NB, 1024);   // 4 workgroups per CU walk the bands (5 each at 256 images)
+    if (dtype == BF16) hipLaunchKernelGGL((stem_conv1a_rows_kernel<TI, __bf16>), dim3(blocks), dim3(256), 0, s, (const TI*)x, (__bf16*)y, ldy, n, wt);
+    else if (dtype == F16) hipLaunchKernelGGL((stem_conv1a_rows_kernel<TI, _Float16>), dim3(blocks), dim3(256), 0, s, (const TI*)x, (_Float16*)y, ldy, n, wt);
+    else hipLaunchKernelGGL((stem_conv1a_rows_kernel<TI, pf16>), dim3(blocks), dim3(256), 0, s, (const TI*)x, (pf16*)y, ldy, n, wt);
+    return hipGetLastError();
+  }
+  if (mode != 0 && n > 0 && (dtype == BF16 || dtype == F16 || dtype == F16P)) {
     const unsigned ngroups = ((unsigned)n * 79 * 79 + 15) / 16;
     const int blocks = (int)((ngroups + 15) / 16 < 2048 ? (ngroups + 15) / 16 : 2048);   // 4 waves x 4 groups per block round
     if (dtype == BF16) hipLaunchKernelGGL((stem_conv1a_mfma_kernel<TI, __bf16>), dim3(blocks), dim3(256), 0, s, (const TI*)x, (__bf16*)y, ldy, n, wt);
@@ -225,12 +394,12 @@ static hipError_t stem_dispatch_out(const void* x, void* y, int ldy, int dtype, 
   return hipGetLastError();
 }
 
-hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, bool mfma,
+hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, int mode,
                               hipStream_t s) {
   switch (x_dtype) {
-    case F32: return stem_dispatch_out<float>(x, y, ldy, dtype, n, wt, mfma, s);
-    case BF16: return stem_dispatch_out<__bf16>(x, y, ldy, dtype, n, wt, mfma, s);
-    case F16: return stem_dispatch_out<_Float16>(x, y, ldy, dtype, n, wt, mfma, s);
+    case F32: return stem_dispatch_out<float>(x, y, ldy, dtype, n, wt, mode, s);
+    case BF16: return stem_dispatch_out<__bf16>(x, y, ldy, dtype, n, wt, mode, s);
+    case F16: return stem_dispatch_out<_Float16>(x, y, ldy, dtype, n, wt, mode, s);
   }
   return hipErrorInvalidValue;
 }

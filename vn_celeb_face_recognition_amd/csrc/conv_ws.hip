@@ -598,6 +598,14 @@ static constexpr WsCfg kWs[] = {
     // small tiles for the 3x3-pixel tail (M = 9 rows per image): persistent, so their 6-28 K tiles per output tile run
     // back to back instead of each paying a pipeline fill and an epilogue
     {64, 64, 2, 2, 4, 4},   {64, 128, 2, 2, 4, 4},  {32, 64, 2, 2, 6, 4},   {32, 128, 2, 2, 4, 4},  {64, 64, 2, 2, 8, 4},
+    // 224 rows beside BN = 192 (last, so every older id keeps its number): the tile height is capped by LDS, three
+    // stages of (BM + BN) x 128 B plus the gather table within 160 KiB, and 3 x 416 x 128 + 12 x 128 = 161,280 B still
+    // fits conv2d_4a's K = 720 (ws_cfg_ok refuses it past 32 K tiles: K = 2304).  A K tile moves 53,248 B through the ~28 B/clk
+    // LDS-DMA path for 1.4 x the FLOPs of the 160 x 192 tile's 45,056 B: 15.6 % fewer bytes per FLOP on the path that
+    // bounds the layer, and its 331,776 pixels are 1,482 tiles = 5.79 rounds of 256 CUs instead of 2,074 = 8.10.
+    // TN = 6 per wave is even, so the persistent form exists (236 VGPRs, no scratch); 7 x 3 > 8: no RES form.  The
+    // one-tile and planar forms spill (256 VGPRs + ~300 B/lane of scratch): correct, slow, never the tuner's choice.
+    {224, 192, 2, 2, 3, 4},
 };
 constexpr int kNumWs = (int)(sizeof(kWs) / sizeof(kWs[0]));
 

@@ -288,7 +288,7 @@ int Encoder::run_range(const void* x, int i0, int i1, int x_dtype, float* out, h
           }
           case Op::STEM1:
             VNF_HIP(launch_stem_conv1a((const char*)x + n0 * x_image, x_dtype, at(op.dst, n0), bufs[op.dst].C, dtype, nn, stem_wt,
-                                       env.stem1a_mfma != 0, s));
+                                       env.stem1a_mfma, s));
             break;
           case Op::MAXPOOL:
             VNF_HIP(launch_maxpool(at(op.src, n0), ib->C, at(op.dst, n0, op.dst_coff), bufs[op.dst].C, dtype, nn, ib->H, ib->W, ib->C,

@@ -169,7 +169,7 @@ struct Tap { int buf, coff, C; };   // buf -2: columns [coff, coff + C) of emb_r
 // Every switch an encoder takes from the environment (VNF_<FIELD NAME>; INTEGRATION.md has the table), read once, when
 // the Encoder is constructed.  Plans, fused stacks, the autotuner and the launchers take their values from here.
 struct EncoderEnv {
-  int fuse = 31, direct_stem = 1, stem1a_mfma = 1, retina_fuse = 3, ws_persist = 1;
+  int fuse = 31, direct_stem = 1, stem1a_mfma = 2, retina_fuse = 3, ws_persist = 1;
   int stem_chunk = 0, ir100_chunk1 = 0, ir100_chunk2 = 0;   // sub-batch of the leading op groups (<= 0: the plan's default)
   int autotune = 1, force_cfg = -2, tune_lanes = 0, autotune_log = 0;
   bool tune_final = true;   // 0: no finalists pass

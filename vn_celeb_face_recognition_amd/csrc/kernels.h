@@ -65,9 +65,10 @@ bool conv_cfg_tile(int cfg, ConvTile& t);
 hipError_t launch_pack_input(const void* x, int x_dtype, void* out, int dtype, int n, int hw, hipStream_t s);
 
 // IRv1 stem: NCHW (n,3,160,160) of x_dtype -> conv2d_1a (3x3 s2, folded BN, ReLU) NHWC (n,79,79,32) of dtype;
-// wt = fp32 [27][32] folded weights (k = (c*3+kh)*3+kw) followed by 32 biases; mfma: the 16-bit / planar outputs on the
-// f32 MFMA (VNF_STEM1A_MFMA, default) instead of the VALU kernel, bitwise the same result
-hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, bool mfma,
+// wt = fp32 [27][32] folded weights (k = (c*3+kh)*3+kw) followed by 32 biases; mode (VNF_STEM1A_MFMA): the 16-bit / planar
+// outputs on the f32 MFMA, 2 (default) fed from LDS-staged input rows (x 16-byte aligned; else as 1), 1 with per-lane
+// gathers, 0 the VALU kernel -- bitwise the same result in all three
+hipError_t launch_stem_conv1a(const void* x, int x_dtype, void* y, int ldy, int dtype, int n, const float* wt, int mode,
                               hipStream_t s);
 
 // K x K stride-2 max pool, NHWC slice -> NHWC slice; padding and the overhang of a ceil-mode window compare as -inf.
