@@ -9,7 +9,8 @@ file is re-used, l.393-399) and summarised into the interval JSON (`dynamic_itv`
 The frames go through video.run_stream, the path demo_video.py runs on: launched under torch.distributed.run, batch b
 of the SAMPLED frames belongs to -- and is read by -- rank b % world_size only, the ranks all-gather embeddings, boxes
 and emotions per round and rank 0 writes the tracker and the statistics.  Only the frames -fidx keeps are read and
-decoded (a directory, a .npy array, a Motion-JPEG .avi; JPEG frames on the GPU unless --host_decode); frame number and
+decoded (a directory, a .npy array, a Motion-JPEG .avi; JPEG frames on the GPU unless --host_decode, their Huffman decode there too with
+--decode_entropy device); frame number and
 time stay those of the input.  --recog_emotion (-emt, -emtargs, -t2i, --topk_emotions) adds every face's top-k emotion
 tags to the tracker (column Emotion, l.264-271) and to the 'emotions' field of the JSON, the mode the reference's own
 scripts run (scripts/celeb_stat_*.sh).  -sfr writes the annotated PNGs (boxes, names, emotion lines) on the host;
@@ -81,7 +82,8 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
 
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
                                  on_frame=on_frame if args.save_frame_recognized else None, log=log,
-                                 decode="host" if args.host_decode else "device", encoder=encoder, emotions=k, row=row)
+                                 decode="host" if args.host_decode else "device", encoder=encoder, emotions=k, row=row,
+                                 decode_entropy=args.decode_entropy)
     if world > 1:
         tot = torch.tensor([processed], device=device if device is not None else 'cuda')
         dist.all_reduce(tot)
@@ -118,6 +120,9 @@ def make_parser():
     p.add_argument('-fps', '--fps_video', default=0.0, type=float, help='frame rate of a frame directory / .npy input')
     p.add_argument('--host_decode', action='store_true',
                    help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
+    p.add_argument('--decode_entropy', default='host', choices=['host', 'device'],
+                   help='where the Huffman decode of JPEG frames decoded on the GPU runs: on host threads, or on the GPU too '
+                        '(the compressed frames are uploaded as they are; the same pixels); ignored with --host_decode')
     p.add_argument('-ov', '--output_video', default='', type=str,
                    help='annotated video of the sampled frames, encoded on the GPU (Motion-JPEG .avi)')
     p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov (1..100)')

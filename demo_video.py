@@ -12,7 +12,8 @@ PNG-encodes every frame).  Input: a directory of frames, a
 (T,H,W,3) RGB frames, a Motion-JPEG .avi, or any video file when OpenCV is installed; -ov exports the annotated frames
 as a video (MP4V with OpenCV, Motion-JPEG .avi without).  JPEG frames (a Motion-JPEG .avi, .jpg files) are decoded on the
 GPU (jpeg.py: Huffman decode on host threads, IDCT / upsampling / colour in HIP), bit-exact to the host decoder;
---host_decode keeps them on Pillow.  -ov x.avi WITHOUT -sfr never makes a PNG: boxes and names are drawn on the frames
+--host_decode keeps them on Pillow; --decode_entropy device moves the Huffman decode into HIP as well (the compressed frames
+are uploaded as they are; the same pixels; default host).  -ov x.avi WITHOUT -sfr never makes a PNG: boxes and names are drawn on the frames
 where they lie in HBM and the frames are JPEG-encoded there (jpeg_encode.py: overlay, colour, down-sampling, DCT and
 quantisation in HIP, the Huffman pass on host threads), the same files Pillow would write (--ov_quality,
 --ov_subsampling).  --ov_entropy device runs the Huffman pass in HIP as well (the same files; only they cross to the
@@ -56,7 +57,8 @@ def main(args, pipe, rank, world, source=None, device=None, encoder=None):
 
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
                                  on_frame=on_frame if args.save_frame_recognized else None, log=log,
-                                 decode="host" if getattr(args, "host_decode", False) else "device", encoder=encoder)
+                                 decode="host" if getattr(args, "host_decode", False) else "device", encoder=encoder,
+                                 decode_entropy=getattr(args, "decode_entropy", "host"))
     if world > 1:
         tot = torch.tensor([processed], device=device if device is not None else 'cuda')
         dist.all_reduce(tot)
@@ -82,6 +84,9 @@ def make_parser():
     p.add_argument('--n_frames', default=16, type=int)
     p.add_argument('--host_decode', action='store_true',
                    help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
+    p.add_argument('--decode_entropy', default='host', choices=['host', 'device'],
+                   help='where the Huffman decode of JPEG frames decoded on the GPU runs: on host threads, or on the GPU too '
+                        '(the compressed frames are uploaded as they are; the same pixels); ignored with --host_decode')
     p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov without -sfr (1..100)')
     p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
                    help='chroma subsampling of the frames of -ov without -sfr')

@@ -40,6 +40,8 @@
  *   vnf_jpeg_probe / vnf_jpeg_entropy_decode / vnf_jpeg_decode_frames
  *                                    cv2.VideoCapture.read as demo_video.py:78-110 calls it (a frame of a
  *                                    Motion-JPEG stream: bitstream walk on the host, pixels on the device)
+ *   vnf_jpeg_huff_prepare / vnf_jpeg_huff_decode_frames
+ *                                   (the Huffman pass of that decoder on the device: a compressed frame goes to HBM as it is)
  *   vnf_jpeg_encode_frames / vnf_jpeg_entropy_encode / vnf_overlay_draw
  *                                    demo_video.py:25-43,149-152 (cv2.rectangle / putText on the frame, cv2.imwrite,
  *                                    cv2.VideoWriter.write: the annotated frame is drawn and transformed on the
@@ -538,6 +540,54 @@ int64_t vnf_jpeg_huff_workspace_bytes(int n, const vnf_jpeg_info* info, int64_t 
 int vnf_jpeg_huff_encode_frames(const int16_t* coefs_dev, int n, const vnf_jpeg_info* info, const uint8_t* header_dev,
                                 int64_t header_len, uint8_t* out_dev, int64_t capacity_per_frame, int64_t* lengths_dev,
                                 int32_t* status_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* JPEG video frames, Huffman-decoded on the device ------------------------------------------ */
+/* The Huffman pass of the frame DEcoder on the device (csrc/jpeg_huff_decode.hip): a second back end that writes the
+ * coefficients vnf_jpeg_entropy_decode writes, so that a compressed frame crosses to HBM as it is and nothing
+ * per-coefficient runs on the host.  The host PREPARES a frame (a memchr-speed pass: FF 00 unstuffed, the scan cut at its
+ * RSTn markers, the decode tables laid out; no symbol decoded); the device decodes every segment in subsequences of
+ * `subseq_bits` bits, one lane each, with the self-synchronising scheme of Weissenberger and Schmidt: speculate ->
+ * synchronise (fixed points inside one workgroup, launch boundaries between workgroups) -> count -> scan -> write ->
+ * DC prefix sums.  Kernel boundaries are the only synchronisation between workgroups, every loop is bounded by bit
+ * counts, and the result is bitwise repeatable. */
+/* The longest blob vnf_jpeg_huff_prepare writes for a file of len bytes whose probe gave *info (its restart interval
+ * decides the number of segments), or VNF_E_INVALID for a NULL info or a negative len.  Host only. */
+int64_t vnf_jpeg_huff_prepared_bound(int64_t len, const vnf_jpeg_info* info);
+/* Prepares the one scan of a frame vnf_jpeg_probe accepted (info: what it filled, for the same bytes) into
+ * out[0, capacity): one self-contained, position-independent blob -- a 64-byte header, the decode tables the scan's
+ * components select with each component's selectors, a table of (offset, byte length) per segment, and the
+ * entropy-coded bytes with FF 00 stuffing removed and fill bytes dropped, split at the RSTn markers (checked to come in
+ * sequence, as vnf_jpeg_entropy_decode checks them; the scan ends at the first other marker or at len) into segments
+ * that each start 16-byte aligned.  A scan without DRI is one segment.  *len_out receives the blob's length, a multiple
+ * of 16.  Wherever the blob is copied to, its first byte must be 16-byte aligned.  Host only, no HIP call, thread-safe;
+ * every read is checked against len, every write against capacity.  VNF_E_INVALID: a NULL pointer, a header
+ * vnf_jpeg_probe does not accept or an info that does not belong to these bytes, a restart interval that does not end
+ * with its RSTn; VNF_E_CAPACITY: the blob does not fit -- never a partial success (out then holds unspecified values
+ * inside [0, capacity), *len_out is untouched). */
+int vnf_jpeg_huff_prepare(const uint8_t* data, int64_t len, const vnf_jpeg_info* info, uint8_t* out, int64_t capacity,
+                          int64_t* len_out);
+/* bytes of device workspace vnf_jpeg_huff_decode_frames needs for n frames of *info's geometry whose blobs are at most
+ * max_blob_bytes long, with this subseq_bits (0: the default, 1024), or a negative VNF_E_* code (VNF_E_INVALID: n
+ * outside 0..65535, subseq_bits neither 0 nor a multiple of 32 in 32..8192, an info vnf_jpeg_probe does not fill,
+ * max_blob_bytes outside 0..2^28) */
+int64_t vnf_jpeg_huff_decode_workspace_bytes(int n, const vnf_jpeg_info* info, int64_t max_blob_bytes, int subseq_bits);
+/* n prepared frames of ONE geometry (*info: width, height, components, sampling, coef_count; restart intervals and
+ * tables are each frame's own): frame i's blob is blobs_dev[blob_offsets[i], + blob_bytes[i]) on the device, blobs_dev
+ * and every offset 16-byte aligned; blob_offsets and blob_bytes are HOST arrays of n, read before the call returns.  The
+ * kernels clamp every access by these sizes, never by a value a blob holds.  coefs_dev: device (n, coef_count) int16 in
+ * exactly the layout vnf_jpeg_entropy_decode writes and vnf_jpeg_decode_frames reads; status_dev: device (n) int32;
+ * workspace: device, 16-byte aligned.  status_dev[i] is VNF_OK and frame i's coefficients are those
+ * vnf_jpeg_entropy_decode gives, or VNF_E_INVALID (a stream that call refuses, or a blob that does not fit its size):
+ * the frame's coefficients are then unspecified, nothing outside its own coef_count was written, and the other frames
+ * are unaffected.  subseq_bits: 0 for the default (1024), else a multiple of 32 in 32..8192 -- a tuning parameter; the
+ * result does not depend on it.  Enqueued on `stream` (two memsets, nine launches and one more per 65536 lanes of the
+ * longest frame, per group of 32 frames), nothing allocated, no host synchronisation.  n == 0: no-op.
+ * Returns VNF_E_INVALID: n outside 0..65535, a NULL or misaligned pointer, a subseq_bits outside the above, an info
+ * vnf_jpeg_probe does not fill, an offset or size outside the above; VNF_E_CAPACITY: workspace_bytes below
+ * vnf_jpeg_huff_decode_workspace_bytes(n, info, max(blob_bytes), subseq_bits); VNF_E_HIP: a launch error. */
+int vnf_jpeg_huff_decode_frames(const uint8_t* blobs_dev, const int64_t* blob_offsets, const int64_t* blob_bytes, int n,
+                                const vnf_jpeg_info* info, int subseq_bits, int16_t* coefs_dev, int32_t* status_dev,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* frame overlay ---------------------------------------------------------------------------- */
 #define VNF_OVERLAY_RECT 0

@@ -120,6 +120,11 @@ SIGNATURES = {
     "vnf_jpeg_huff_workspace_bytes": (ctypes.c_int64, [_I, ctypes.POINTER(JpegInfo), ctypes.c_int64]),
     "vnf_jpeg_huff_encode_frames": (_I, [_P, _I, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P,
                                         ctypes.c_int64, _P]),
+    "vnf_jpeg_huff_prepared_bound": (ctypes.c_int64, [ctypes.c_int64, ctypes.POINTER(JpegInfo)]),
+    "vnf_jpeg_huff_prepare": (_I, [_P, ctypes.c_int64, ctypes.POINTER(JpegInfo), _P, ctypes.c_int64,
+                                  ctypes.POINTER(ctypes.c_int64)]),
+    "vnf_jpeg_huff_decode_workspace_bytes": (ctypes.c_int64, [_I, ctypes.POINTER(JpegInfo), ctypes.c_int64, _I]),
+    "vnf_jpeg_huff_decode_frames": (_I, [_P, _P, _P, _I, ctypes.POINTER(JpegInfo), _I, _P, _P, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }

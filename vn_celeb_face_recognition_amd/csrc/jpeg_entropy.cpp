@@ -4,8 +4,10 @@
 //
 // Replaces, together with those kernels, the reference's cv2.VideoCapture.read (/root/reference/demo_video.py:78-110)
 // for Motion-JPEG input.  Written from the JPEG standard (ITU-T T.81: B.2 marker segments, C Huffman table
-// generation, F.2.2 decoding procedures); no HIP call and no dependency on the rest of the library, so the file also
-// compiles into a stand-alone checker (tools/jpeg_entropy_check.cpp).  The input is a file from disk: every read is
+// generation, F.2.2 decoding procedures); no HIP call and no dependency on the rest of the library but headers, so the
+// file also compiles into stand-alone checkers (tools/jpeg_entropy_check.cpp, tools/jpeg_huff_decode_check.cpp).  For the
+// device Huffman decoder (jpeg_huff_decode.hip) the same marker walk PREPARES a frame instead of decoding it
+// (vnf_jpeg_huff_prepare, at the end of the file).  The input is a file from disk: every read is
 // checked against `len`, every write against `capacity`, and no state is shared between calls (thread-safe).
 #include <stdint.h>
 #include <string.h>
@@ -13,6 +15,7 @@
 #include <new>
 
 #include "../../include/vnface.h"
+#include "jpeg_huff_decode.h"
 
 namespace {
 
@@ -365,6 +368,133 @@ extern "C" int vnf_jpeg_entropy_decode(const uint8_t* data, int64_t len, const v
       }
       --left;
     }
+  }
+  delete P;
+  return rc;
+}
+
+// ---- the frame prepared for the device Huffman decoder (the blob of jpeg_huff_decode.h) ----------------------------------
+
+namespace {
+
+using namespace vnf::hdec;
+
+// writes into out[0, capacity) only; `ok` goes false at the first byte that does not fit
+struct BlobOut {
+  uint8_t* out;
+  int64_t capacity, at = 0;
+  bool ok = true;
+  void put(const void* src, int64_t n) {
+    if (!ok || n > capacity - at) { ok = false; return; }
+    if (n) memcpy(out + at, src, (size_t)n);
+    at += n;
+  }
+  void zeros(int64_t n) {
+    if (!ok || n > capacity - at) { ok = false; return; }
+    if (n) memset(out + at, 0, (size_t)n);
+    at += n;
+  }
+};
+
+void device_table(const Huff& h, DTable* t) {
+  memset(t, 0, sizeof(*t));
+  memcpy(t->look, h.look, sizeof(t->look));
+  for (int l = 1; l <= 17; ++l) t->maxcode[l] = h.maxcode[l];   // [0] of both is never set and never read
+  for (int l = 1; l <= 16; ++l) t->valoff[l] = h.valoff[l];
+  t->nvals = h.nvals;
+  memcpy(t->vals, h.vals, (size_t)h.nvals);
+}
+
+}  // namespace
+
+extern "C" int64_t vnf_jpeg_huff_prepared_bound(int64_t len, const vnf_jpeg_info* info) {
+  if (!info || len < 0 || info->components < 1 || info->components > 3 || info->h[0] < 1 || info->v[0] < 1 ||
+      info->restart_interval < 0)
+    return VNF_E_INVALID;
+  return prepared_bound(len, *info);
+}
+
+extern "C" int vnf_jpeg_huff_prepare(const uint8_t* data, int64_t len, const vnf_jpeg_info* info, uint8_t* out,
+                                     int64_t capacity, int64_t* len_out) {
+  if (!data || !info || !out || !len_out || len < 0 || capacity < 0) return VNF_E_INVALID;
+  Parsed* P = new (std::nothrow) Parsed;
+  if (!P) return VNF_E_INVALID;
+  int rc = parse(data, len, *P);
+  const vnf_jpeg_info& I = P->info;
+  if (rc != VNF_OK || I.width != info->width || I.height != info->height || I.components != info->components ||
+      I.sampling != info->sampling || I.coef_count != info->coef_count) {
+    delete P;
+    return VNF_E_INVALID;
+  }
+  const int64_t nseg = segments_of(I);
+  // the tables the scan's components select, each once: DC tables first
+  BlobHeader h;
+  memset(&h, 0, sizeof(h));
+  h.magic = kMagic;
+  h.nseg = (uint32_t)nseg;
+  h.restart_interval = (uint32_t)I.restart_interval;
+  h.ncomp = (uint32_t)I.components;
+  int slot_dc[4] = {-1, -1, -1, -1}, slot_ac[4] = {-1, -1, -1, -1};
+  const Huff* used[kMaxTables];
+  int nt = 0;
+  for (int c = 0; c < I.components; ++c)
+    if (slot_dc[P->td[c]] < 0) { slot_dc[P->td[c]] = nt; used[nt++] = &P->dc[P->td[c]]; }
+  for (int c = 0; c < I.components; ++c)
+    if (slot_ac[P->ta[c]] < 0) { slot_ac[P->ta[c]] = nt; used[nt++] = &P->ac[P->ta[c]]; }
+  for (int c = 0; c < I.components; ++c) {
+    h.dc_sel[c] = (uint8_t)slot_dc[P->td[c]];
+    h.ac_sel[c] = (uint8_t)slot_ac[P->ta[c]];
+  }
+  h.ntables = (uint32_t)nt;
+  h.tables_at = (uint32_t)sizeof(BlobHeader);
+  h.seg_at = h.tables_at + (uint32_t)nt * (uint32_t)sizeof(DTable);
+  const int64_t data_at = round16((int64_t)h.seg_at + nseg * (int64_t)sizeof(Seg));
+  h.data_at = (uint32_t)data_at;
+  rc = VNF_OK;
+  if (data_at + round16(len) + 16 * nseg > kMaxBlobBytes) rc = VNF_E_INVALID;   // 32-bit bit positions on the device
+  BlobOut o{out, capacity};
+  if (rc == VNF_OK) {
+    o.zeros(data_at);   // header, tables and segment table: filled in below, once they are known to fit
+    if (o.ok) {
+      DTable* t = new (std::nothrow) DTable;
+      if (!t) rc = VNF_E_INVALID;
+      for (int i = 0; i < nt && t; ++i) {
+        device_table(*used[i], t);
+        memcpy(out + h.tables_at + (int64_t)i * (int64_t)sizeof(DTable), t, sizeof(DTable));
+      }
+      delete t;
+    }
+  }
+  // the scan: runs without FF are copied as they are; FF 00 -> FF, FF FF -> a fill byte, FF xx -> a marker
+  int64_t p = P->scan;
+  for (int64_t s = 0; s < nseg && rc == VNF_OK && o.ok; ++s) {
+    const int64_t at = o.at;
+    int marker = -1;
+    while (o.ok) {
+      const uint8_t* q = p < len ? (const uint8_t*)memchr(data + p, 0xFF, (size_t)(len - p)) : nullptr;
+      const int64_t run = q ? q - (data + p) : len - p;
+      o.put(data + p, run);
+      p += run;
+      if (!q || p + 1 >= len) { p = len; break; }       // the end of the data; a lone FF there is no data
+      const int nx = data[p + 1];
+      if (nx == 0x00) { o.put(data + p, 1); p += 2; }   // a stuffed FF
+      else if (nx == 0xFF) ++p;                         // a fill byte
+      else { marker = nx; break; }
+    }
+    if (!o.ok) break;
+    const Seg sg = {(uint32_t)at, (uint32_t)(o.at - at)};
+    memcpy(out + h.seg_at + s * (int64_t)sizeof(Seg), &sg, sizeof(sg));
+    o.zeros(round16(o.at) - o.at);
+    if (s + 1 < nseg) {
+      if (marker != 0xD0 + (int)(s & 7)) rc = VNF_E_INVALID;   // a restart interval ends with RSTn in sequence
+      p += 2;
+    }
+  }
+  if (rc == VNF_OK && !o.ok) rc = VNF_E_CAPACITY;
+  if (rc == VNF_OK) {
+    h.total_bytes = (uint32_t)o.at;
+    memcpy(out, &h, sizeof(h));
+    *len_out = o.at;
   }
   delete P;
   return rc;

@@ -38,6 +38,7 @@ class FrameUploader:
         self._dnext = 0
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(threads))) if threads > 1 else None
         self._scratch = None                   # device bytes used on the copy stream only (jpeg.decode_batch_device)
+        self._status = None                    # pinned int32s a decoder's statuses come back through
         self.bytes = 0                         # uploaded so far (bench / tests)
         self.last_slot = -1                    # device slot of the last upload (for release())
 
@@ -88,6 +89,13 @@ class FrameUploader:
             with torch.cuda.stream(self.stream):
                 self._scratch = torch.empty((int(nbytes),), dtype=torch.uint8, device=self.device)
         return self._scratch
+
+    def status_buffer(self, n):
+        """`n` pinned int32s for a device -> host copy on the copy stream whose event the caller waits for before it
+        asks for the buffer again: one buffer is enough."""
+        if self._status is None or self._status.numel() < n:
+            self._status = torch.empty((max(int(n), 64),), dtype=torch.int32).pin_memory()
+        return self._status[:n]
 
     def staged(self, k, event, nbytes):
         """Pinned staging slot k was read by a copy the caller enqueued on the copy stream; `event` follows that copy."""

@@ -133,7 +133,7 @@ class FrameSource:
 
 
 def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
-               decode="device", encoder=None, emotions=0, row=None):
+               decode="device", encoder=None, emotions=0, row=None, decode_entropy="host"):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
 
     pipe: FacePipeline-like -- .submit(frames_dev, classify=False[, ready=event]) -> ticket with .result() ->
@@ -147,6 +147,8 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     decoded by jpeg.decode_batch_device: entropy decode on host threads, pixels on the upload stream; a batch it does
     not take is decoded by Pillow and uploaded, as every batch is with decode="host".  The frames are the same bytes
     either way; on_frame receives a jpeg.HostFrame (shape + pixels on demand) for a device-decoded frame.
+    decode_entropy: "host" (default) or "device" -- where the Huffman decode of such a batch runs (jpeg.ENTROPY): on
+    host threads, or in HIP behind an upload of the compressed frames as they are.  Ignored with decode="host".
     encoder: None, or a jpeg_encode.VideoEncoder-like object (GPU only) that writes the annotated video: every batch's
     DEVICE frames are then kept until the round's names are known and handed over with
     .write_batch(frames_dev, numbers, boxes, names, after=event) -> event, in frame order on the rank that owns them;
@@ -342,6 +344,8 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
         the next batch's host -> HBM copy has to be in flight before it, or copy and detection would take turns"""
         if decode not in ("device", "host"):
             raise ValueError("run_stream: decode must be 'device' or 'host', got %r" % (decode,))
+        if decode_entropy not in ("host", "device"):
+            raise ValueError("run_stream: decode_entropy must be 'host' or 'device', got %r" % (decode_entropy,))
         if uploader is not None and decode == "device" and getattr(source, "compressed", None) is not None:
             it = source.rank_batches(n_frames, rank, world, compressed=True)
         else:
@@ -354,7 +358,10 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             from .jpeg import CompressedBatch, decode_batch
             b, q, inf = item
             if isinstance(q, CompressedBatch):
-                frames_dev, ev, slot, q = decode_batch(q, dev, uploader)
+                if decode_entropy == "host":
+                    frames_dev, ev, slot, q = decode_batch(q, dev, uploader)
+                else:
+                    frames_dev, ev, slot, q = decode_batch(q, dev, uploader, entropy=decode_entropy)
                 return (b, q, inf), (frames_dev, ev, slot)
             return item, uploader.upload(q) + (uploader.last_slot,)
 
