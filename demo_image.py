@@ -57,9 +57,17 @@ def build_models(args, device, allow_emotion=False):
     detection_md = getattr(model_md, args.detection)(**det_args)
     detection_md.eval()
     emb_model = getattr(model_md, args.encoder)(**read_json(args.encoder_args)).to(device)
-    classify_model = model_md.MLPModel(args.input_dim_emb, args.num_classes)
-    load_model_classify(args.classify_model, classify_model)
-    classify_model = classify_model.to(device)
+    if args.classify_model.endswith('.npz'):   # a gallery written by enroll.py: identification by cosine, -nc is not used
+        classify_model = model_md.GalleryModel.load(args.classify_model)
+        if classify_model.input_dim != args.input_dim_emb:
+            raise SystemExit("-id {} does not match the gallery's embedding width {}".format(args.input_dim_emb,
+                                                                                            classify_model.input_dim))
+        args.num_classes = classify_model.num_classes   # what celeb_statistic.py sizes its threshold table by
+        classify_model = classify_model.to(device)
+    else:
+        classify_model = model_md.MLPModel(args.input_dim_emb, args.num_classes)
+        load_model_classify(args.classify_model, classify_model)
+        classify_model = classify_model.to(device)
     return label2name_df, detection_md, emb_model, classify_model
 
 

@@ -653,6 +653,44 @@ int vnf_overlay_draw_text(uint8_t* frames_dev, int b, int height, int width, con
                           const int32_t* launch_ends, int n_launches, const uint8_t* chars_dev, int64_t chars_bytes,
                           const void* atlas_dev, int64_t atlas_bytes, void* stream);
 
+/* Gallery identification ------------------------------------------------------------------------ */
+/* A gallery is a device matrix of unit-norm fp32 rows (G, dim) with an int32 label per row; identification is an exact
+ * cosine top-k search over it, so people are added without training.  dim: a multiple of 16 in 16..512 (else
+ * VNF_E_INVALID).  capacity_rows is only the first allocation: vnf_gallery_add grows it (amortised doubling, device to
+ * device copy).  Release with vnf_destroy. */
+int vnf_gallery_create(int dim, int64_t capacity_rows, vnf_handle* out);
+/* Appends n rows: rows_dev device (n,dim) fp32, 16-byte aligned, each stored as x / max(||x||_2, 1e-12) (F.normalize's
+ * rule); labels_dev device (n) int32, copied as they are.  Enqueued on `stream`; a call that has to grow the matrix
+ * synchronises that stream and the device once.  VNF_E_CAPACITY: more than 2^31 - 1 rows. */
+int vnf_gallery_add(vnf_handle gallery, const float* rows_dev, const int32_t* labels_dev, int64_t n, void* stream);
+int vnf_gallery_size(vnf_handle gallery, int64_t* rows);
+/* The stored (unit) rows [first, first + n) copied to rows_out_dev (n,dim) fp32, device to device on `stream`: what a
+ * gallery file keeps.  vnf_gallery_add_unit appends such rows as they are, without normalising them again, so a saved
+ * gallery comes back bit for bit. */
+int vnf_gallery_rows(vnf_handle gallery, float* rows_out_dev, int64_t first, int64_t n, void* stream);
+int vnf_gallery_add_unit(vnf_handle gallery, const float* rows_dev, const int32_t* labels_dev, int64_t n, void* stream);
+/* Enrolment of a centroid gallery: sums_inout_dev (num_classes,dim) fp32 += the normalised rows (same rule) whose label
+ * is the class, counts_inout_dev (num_classes) int32 += their number.  The rows of a class are added in row order in
+ * fp32, so the result repeats bitwise and appending later needs the sums alone.  A label outside [0, num_classes)
+ * matches no class (the table lives in device memory; the host layer checks labels before they are uploaded).  One
+ * wave per class walks every label: not a hot path. */
+int vnf_gallery_class_sums(const float* rows_dev, const int32_t* labels_dev, int64_t n, int dim, float* sums_inout_dev,
+                           int32_t* counts_inout_dev, int num_classes, void* stream);
+/* Bytes of workspace vnf_gallery_search needs for F queries, k results, a gallery of G rows and this chunk_rows (0: the
+ * library's default, which depends on F and G).  Negative VNF_E_INVALID on a bad argument. */
+int64_t vnf_gallery_search_workspace_bytes(int F, int k, int64_t G, int64_t chunk_rows);
+/* q_dev device (F,dim) fp32, 16-byte aligned, normalised by the kernel with the rule of vnf_gallery_add.
+ * score = <q^, g^> in fp32 on v_mfma_f32_16x16x4_f32 with one k order per (query, row) pair: a score's bits depend on
+ * the two vectors only, not on F, the row's position or chunk_rows.  Per query, idx_out / label_out / score_out (F,k)
+ * receive the k best rows (1 <= k <= 16) under the total order (score descending, row index ascending); -0 ties with
+ * +0, a NaN score (returned as the canonical quiet NaN) orders below every number, and the slots beyond G hold index
+ * -1, label -1, score -inf.  Stage one: a wave takes chunk_rows gallery rows against 16 queries and writes a partial
+ * top-k to the workspace; stage two merges the partial lists, exactly because the order is total.  No atomics, nothing
+ * allocated, no synchronisation.  chunk_rows is public so that a test can put a chunk boundary anywhere.  F == 0:
+ * no-op.  VNF_E_CAPACITY: workspace_bytes below vnf_gallery_search_workspace_bytes of the same arguments. */
+int vnf_gallery_search(vnf_handle gallery, const float* q_dev, int F, int k, int32_t* idx_out, int32_t* label_out,
+                       float* score_out, int64_t chunk_rows, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile
  * configurations (three kernel families, each compiled for five storage layouts).  A probe is a plan of exactly ONE

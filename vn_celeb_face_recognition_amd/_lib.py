@@ -125,6 +125,14 @@ SIGNATURES = {
                                   ctypes.POINTER(ctypes.c_int64)]),
     "vnf_jpeg_huff_decode_workspace_bytes": (ctypes.c_int64, [_I, ctypes.POINTER(JpegInfo), ctypes.c_int64, _I]),
     "vnf_jpeg_huff_decode_frames": (_I, [_P, _P, _P, _I, ctypes.POINTER(JpegInfo), _I, _P, _P, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_create": (_I, [_I, ctypes.c_int64, ctypes.POINTER(_P)]),
+    "vnf_gallery_add": (_I, [_P, _P, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_add_unit": (_I, [_P, _P, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_rows": (_I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P]),
+    "vnf_gallery_size": (_I, [_P, ctypes.POINTER(ctypes.c_int64)]),
+    "vnf_gallery_class_sums": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _I, _P]),
+    "vnf_gallery_search_workspace_bytes": (ctypes.c_int64, [_I, _I, ctypes.c_int64, ctypes.c_int64]),
+    "vnf_gallery_search": (_I, [_P, _P, _I, _I, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }

@@ -23,7 +23,7 @@ const char* last_error_cstr();   // the calling thread's last message (vnf_last_
       return ::vnf::fail(VNF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
   } while (0)
 
-enum class HandleKind { Encoder = 1, Mlp, Mtcnn, MlpTrainer, Retina, HeadTrainer, ConvProbe };
+enum class HandleKind { Encoder = 1, Mlp, Mtcnn, MlpTrainer, Retina, HeadTrainer, ConvProbe, Gallery };
 
 struct HandleBase {
   const HandleKind kind;
