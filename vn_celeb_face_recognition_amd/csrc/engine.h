@@ -142,11 +142,14 @@ struct Group { int first, last, chunk; };
 
 // A run of plan ops that fused kernels replace when the compute dtype allows it (16-bit operands): the 40 convolutions
 // of repeat_2 become one launch of block17_trunk_kernel (trunk17.hip), the 25 of repeat_1 five launches of
-// block35_kernel (block35.hip).
+// block35_kernel (block35.hip), reduce + 1x3 + 3x1 of each Block8 one launch of block8_chain_kernel (block8.hip).
 struct FusedStack {
   // Block17: persistent Block17 stack (trunk17.hip); Block35: one fused launch per Block35 (block35.hip);
-  // StemMid: conv2d_2a + conv2d_2b + maxpool_3a in one launch (stem_mid.hip)
-  enum class Kind { StemMid, Block35, Block17 } kind = Kind::Block17;
+  // StemMid: conv2d_2a + conv2d_2b + maxpool_3a in one launch (stem_mid.hip);
+  // Block8: reduce + branch1.1 + branch1.2 of one Block8 in one launch (block8.hip): conv0 = the reduce, out_buf = the
+  // 384-channel concat; the block's up-projection stays a plan op behind the stack
+  enum class Kind { StemMid, Block35, Block17, Block8 } kind = Kind::Block17;
+  std::string label;           // Block8: the profile row's label (one stack per block)
   int first = 0, last = 0;     // op range
   int in_buf = -1, out_buf = -1;
   int nblocks = 0;
@@ -169,7 +172,7 @@ struct Tap { int buf, coff, C; };   // buf -2: columns [coff, coff + C) of emb_r
 // Every switch an encoder takes from the environment (VNF_<FIELD NAME>; INTEGRATION.md has the table), read once, when
 // the Encoder is constructed.  Plans, fused stacks, the autotuner and the launchers take their values from here.
 struct EncoderEnv {
-  int fuse = 31, direct_stem = 1, stem1a_mfma = 2, retina_fuse = 3, ws_persist = 1;
+  int fuse = 95, direct_stem = 1, stem1a_mfma = 2, retina_fuse = 3, ws_persist = 1;
   int stem_chunk = 0, ir100_chunk1 = 0, ir100_chunk2 = 0;   // sub-batch of the leading op groups (<= 0: the plan's default)
   int autotune = 1, force_cfg = -2, tune_lanes = 0, autotune_log = 0;
   bool tune_final = true;   // 0: no finalists pass

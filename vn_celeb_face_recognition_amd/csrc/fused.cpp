@@ -1,6 +1,7 @@
 // Fused stacks: runs of plan ops that one kernel replaces when the compute dtype allows it (engine.h FusedStack).
 #include "engine.h"
 #include "block35.h"
+#include "block8.h"
 #include "stem_mid.h"
 #include "trunk17.h"
 
@@ -15,7 +16,7 @@ using Kind = FusedStack::Kind;
 int Encoder::prepare_fused() {
   // bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4: the five
   // Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
-  // mixed_6a.branch1.0 inside that launch
+  // mixed_6a.branch1.0 inside that launch, bit 6: reduce + 1x3 + 3x1 of every Block8 in one launch (bf16 / f16)
   const int enabled = env.fuse;
   for (FusedStack& f : fused) {
     f.active = false;
@@ -93,6 +94,41 @@ int Encoder::prepare_fused() {
       }
       continue;
     }
+    if (f.kind == Kind::Block8) {
+      if (!(enabled & 64) || dtype == F16P) continue;   // the planar split-f16 dtype keeps the three plan convolutions
+      const ConvLayer& red = convs[f.conv0];
+      const ConvLayer& c13 = convs[f.conv0 + 1];
+      const ConvLayer& c31 = convs[f.conv0 + 2];
+      auto plain = [](const ConvLayer& L, int cout, int K) {
+        return L.cout == cout && L.K == K && L.Kpad == K && L.ncls == 1 && L.res_buf < 0 && L.act == ACT_RELU && !L.out_f32 &&
+               L.sh == 1 && L.sw == 1 && L.H == 3 && L.W == 3 && L.Ho == 3 && L.Wo == 3;
+      };
+      const bool ok =
+          plain(red, 384, 1792) && plain(c13, 192, 576) && plain(c31, 192, 576) && f.last - f.first == 3 &&
+          red.KH == 1 && red.KW == 1 && red.x_buf == f.in_buf && red.x_coff == 0 && bufs[f.in_buf].C == 1792 && red.nseg == 2 &&
+          red.seg[0].c0 == 0 && red.seg[0].c1 == 192 && red.seg[0].buf == f.out_buf && red.seg[0].coff == 0 &&
+          red.seg[1].c0 == 192 && red.seg[1].c1 == 384 && red.seg[1].coff == 0 &&
+          c13.KH == 1 && c13.KW == 3 && c13.ph == 0 && c13.pw == 1 && c13.x_buf == red.seg[1].buf && c13.x_coff == 0 &&
+          c13.nseg == 1 && c13.seg[0].coff == 0 &&
+          c31.KH == 3 && c31.KW == 1 && c31.ph == 1 && c31.pw == 0 && c31.x_buf == c13.seg[0].buf && c31.x_coff == 0 &&
+          c31.nseg == 1 && c31.seg[0].buf == f.out_buf && c31.seg[0].coff == 192 && bufs[f.out_buf].C == 384;
+      if (!ok) return fail(VNF_E_INVALID, "fused Block8 chain: unexpected layer shapes");
+      Block8Pack pk;
+      pk.w[0] = red.w; pk.kpad[0] = red.Kpad;
+      pk.w[1] = c13.w; pk.kpad[1] = c13.Kpad;
+      pk.w[2] = c31.w; pk.kpad[2] = c31.Kpad;
+      f.wstream = dalloc(block8_stream_bytes());
+      f.bias = (float*)dalloc(B8_BIAS * 4);
+      if (!f.wstream || !f.bias) return VNF_E_HIP;
+      VNF_HIP(hipMemcpy(f.bias, red.bias, 384 * 4, hipMemcpyDeviceToDevice));
+      VNF_HIP(hipMemcpy(f.bias + 384, c13.bias, 192 * 4, hipMemcpyDeviceToDevice));
+      VNF_HIP(hipMemcpy(f.bias + 576, c31.bias, 192 * 4, hipMemcpyDeviceToDevice));
+      VNF_HIP(block8_repack(pk, f.wstream, 0));
+      VNF_HIP(hipDeviceSynchronize());
+      f.macs_alg = red.macs_alg + c13.macs_alg + c31.macs_alg;
+      f.active = true;
+      continue;
+    }
     if (!(enabled & 1)) continue;
     Trunk17Pack pk;
     memset(&pk, 0, sizeof pk);
@@ -144,6 +180,7 @@ bool Encoder::buf_materialised(int buf) const {
         produced |= f.ext && buf == f.ext_out_buf;
         break;
       case Kind::Block17: produced = buf == f.out_buf; break;
+      case Kind::Block8: produced = buf == f.out_buf; break;   // the concat; branch1.0 / 1x3 outputs only ever live in LDS
     }
     if (!produced) return false;
   }
@@ -212,18 +249,30 @@ int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
       err = dtype == F16P ? launch_trunk17s(ta, s) : launch_trunk17(ta, dtype, s);
       break;
     }
+    case Kind::Block8: {
+      Block8Args ba;
+      ba.x = at(f.in_buf, n0); ba.ldx = bufs[f.in_buf].C;
+      ba.y = at(f.out_buf, n0); ba.ldy = bufs[f.out_buf].C;
+      ba.n = nn;
+      ba.wstream = f.wstream; ba.bias = f.bias;
+      what = "fused Block8 chain";
+      err = launch_block8(ba, dtype, s);
+      break;
+    }
   }
   return err == hipSuccess ? VNF_OK : fail(VNF_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
 }
 
 const char* fused_label(const FusedStack& f) {
   if (f.kind == Kind::StemMid) return f.ext ? "conv2d_2a+2b+maxpool_3a+3b" : "conv2d_2a+2b+maxpool_3a";
+  if (f.kind == Kind::Block8) return f.label.c_str();
   return f.kind == Kind::Block35 ? "repeat_1 (fused blocks)" : "repeat_2 (persistent trunk)";
 }
 
 const char* fused_detail(const FusedStack& f) {
   if (f.kind == Kind::StemMid) return "rolling rows, one launch, one workgroup per image";
   if (f.kind == Kind::Block17) return "10 x Block17 in one launch, one workgroup per image";
+  if (f.kind == Kind::Block8) return "one launch, G = 3 images per workgroup, weights streamed to registers";
   if (!f.stack) return "5 x Block35, one launch per block, one workgroup per image";
   return f.ext ? "5 x Block35 + mixed_6a.branch1.0 in one launch, x in registers"
                : "5 x Block35 in one launch, x in registers, one workgroup per image";

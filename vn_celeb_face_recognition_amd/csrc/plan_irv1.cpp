@@ -172,10 +172,17 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   for (int i = 0; i < 6; ++i) {
     const std::string p = i < 5 ? "repeat_3." + std::to_string(i) : std::string("block8");
     const int X = x8[cur], Y = x8[cur == 1 ? 2 : 1];
+    FusedStack f;   // bf16 / f16: reduce + 1x3 + 3x1 as one weight-streaming launch (block8.hip); the up-projection stays
+    f.kind = FusedStack::Kind::Block8;
+    f.label = p + " chain (reduce+1x3+3x1)";
+    f.first = (int)e.ops.size(); f.conv0 = (int)e.convs.size();
+    f.in_buf = X; f.out_buf = cat8; f.nblocks = 1;
     TRY(fused1x1(p + ".reduce", {p + ".branch0", p + ".branch1.0"}, X, 1792, 192,
                  {{0, 192, cat8, 0}, {192, 384, t8a, 0}}));
     TRY(simple(p + ".branch1.1", t8a, 0, 192, 192, 192, 1, 3, 1, 0, 1, t8b, 0));
     TRY(simple(p + ".branch1.2", t8b, 0, 192, 192, 192, 3, 1, 1, 1, 0, cat8, 192));
+    f.last = (int)e.ops.size();
+    e.fused.push_back(f);
     TRY(up(p, cat8, 384, 1792, i < 5 ? 0.20f : 1.0f, X, Y, i < 5));
     cur = (cur == 1 ? 2 : 1);
     if (i == 4) e.taps["repeat_3"] = {x8[cur], 0, 1792};
