@@ -8,7 +8,7 @@ using namespace vnf;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("err %s line %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 int main() {
   const int n = 256, nb = 10;
-  const size_t xbytes = (size_t)n * 64 * 896 * 4, wbytes = trunk17s_stream_bytes(nb);
+  const size_t xbytes = (size_t)n * 64 * 896 * 4, wbytes = trunk17_stream_bytes(nb, F16P);
   std::vector<_Float16> hx(xbytes / 2), hw(wbytes / 2);
   std::mt19937 g(1);
   std::normal_distribution<float> d(0.f, 1.f);

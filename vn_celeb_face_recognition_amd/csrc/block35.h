@@ -1,7 +1,10 @@
-// Launch interface of the fused Block35 kernel (block35.hip).
+// Launch interface of the fused Block35 kernels: block35.hip (bf16 / f16, one block per launch), its planar split-f16
+// twin block35s.hip (F16P: x / y are F16P tensors, the pack's weights F16P-packed) and trunk35.hip (the whole stack).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+
+#include "kernels.h"
 
 namespace vnf {
 
@@ -13,7 +16,7 @@ constexpr int B35_WIMG_BYTES = (B35_FRAGS + 2) * 1024;
 constexpr int B35_BIAS = 448;  // fp32 per block: 96 reduce | 32 branch1.1 | 32 branch2.1 | 32 branch2.2 | 256 up
 
 struct Block35Args {
-  const void* x;      // (n, 289, ldx) 16-bit NHWC block input (residual source)
+  const void* x;      // (n, 289, ldx) NHWC block input (residual source)
   void* y;            // (n, 289, ldy) block output
   int ldx, ldy, n;
   const void* wimg;   // block35_repack output of this block (weights + biases)
@@ -26,13 +29,15 @@ struct Block35Pack {   // packed engine weights [rows][kpad] (k = (kh, kw, c)) o
   const float* bias;   // device [B35_BIAS]: the five convolutions' biases in that order
 };
 
-// planar split-f16 twin (block35s.hip): x / y are F16P tensors, the pack's weights F16P-packed; 300 fragments + 2 KiB biases
-constexpr int B35S_WIMG_BYTES = (300 + 2) * 1024;
+// the planar twin's image: every fragment as a (hi, lo) pair, then the 2 KiB of biases
+inline size_t block35_wimg_bytes(int dtype) { return dtype == F16P ? (size_t)(2 * B35_FRAGS + 2) * 1024 : (size_t)B35_WIMG_BYTES; }
+
+// dtype: BF16, F16 or F16P (anything else: hipErrorInvalidValue)
+hipError_t block35_repack(const Block35Pack& p, int dtype, void* out, hipStream_t s);
+hipError_t launch_block35(const Block35Args& a, int dtype, hipStream_t s);
+// the twin's own entry points, reached through the two above
 hipError_t block35s_repack(const Block35Pack& p, void* out, hipStream_t s);
 hipError_t launch_block35s(const Block35Args& a, hipStream_t s);
-
-hipError_t block35_repack(const Block35Pack& p, void* out, hipStream_t s);
-hipError_t launch_block35(const Block35Args& a, int dtype, hipStream_t s);
 
 // the whole repeat_1 stack in one launch, x resident in registers (trunk35.hip; bf16 / f16 plans)
 struct Block35StackArgs {

@@ -27,7 +27,7 @@
 #include <type_traits>
 
 #include "block35.h"
-#include "conv_device.h"
+#include "fused_device.h"
 
 namespace vnf {
 
@@ -49,31 +49,6 @@ static_assert(B35_LDS == 160 * 1024 && 4 * IMG_BYTES == 2 * XR_STAGE, "LDS map")
 constexpr int STG_PITCH = 272;                    // fp32 staging row: 64 channels + 16 B pad
 constexpr int STG_WAVE = 16 * STG_PITCH;          // 4352 B per wave
 
-template <typename T> struct Mma35;
-template <> struct Mma35<__bf16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-  }
-};
-template <> struct Mma35<_Float16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), c, 0, 0, 0);
-  }
-};
-
-template <typename T>
-__device__ __forceinline__ uint2 pack4_35(const f32x4_t& v) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 r = {(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-  return __builtin_bit_cast(uint2, r);
-}
-
-// byte offset of the 16-byte chunk `chunk` (0..3) of pixel row q inside a 32-channel image
-__device__ __forceinline__ int img_chunk(int q, int chunk) { return q * 64 + ((chunk ^ ((0 - (q >> 2)) & 3)) << 4); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 }  // namespace
 
 template <typename T>
@@ -83,7 +58,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 15, fgrp = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   // x and y are different tensors (the plan ping-pongs the block buffers): without __restrict__ every y store is
   // followed by a vmcnt(0) before the next x load
   const char* __restrict__ xg = (const char*)a.x + (size_t)img * NPX * a.ldx * 2;
@@ -113,11 +88,11 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
       glds16(src, lds0 + stage * XR_STAGE + id * 1024);
     }
   };
+
+  using C1 = std::integral_constant<int, 1>;
   using C3 = std::integral_constant<int, 3>;
   using C5 = std::integral_constant<int, 5>;
   using C6 = std::integral_constant<int, 6>;
-
-  using C1 = std::integral_constant<int, 1>;
   copy_lin(wimg + B35_BIASOFF, OFF_BIAS, 2, C1{});  // oldest DMA: landed whenever anything else has
   copy_lin(wimg + B35_W1, OFF_W, 48, C6{});
   issue_x(0, 0);
@@ -150,7 +125,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
       for (int j = 0; j < 6; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (i < nt) accA[j][i] = Mma35<T>::run(wf[j], xf[i], accA[j][i]);
+          if (i < nt) mma_chunk<T>(accA[j][i], wf[j], xf[i]);
     }
     if (kt < 2) {
       __syncthreads();  // every wave is done with this stage
@@ -171,7 +146,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = p < NPX ? fmaxf(v[e] + bv[e], 0.f) : 0.f;
         if (p < ROWS)
-          *reinterpret_cast<uint2*>(smem + (j >> 1) * IMG_BYTES + img_chunk(p, 2 * (j & 1) + (fgrp >> 1)) + (fgrp & 1) * 8) = pack4_35<T>(v);
+          *reinterpret_cast<uint2*>(smem + (j >> 1) * IMG_BYTES + row64_chunk(p, 2 * (j & 1) + (fgrp >> 1)) + (fgrp & 1) * 8) = pack4<T>(v);
       }
   __syncthreads();
 
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
         if (i < nt) {
           const int q = 16 * (wave + 8 * i) + frow + dy * IMW + dx;
           const bool ok = (unsigned)(py[i] + dy) < (unsigned)IMW && (unsigned)(px[i] + dx) < (unsigned)IMW;
-          xf[i] = *reinterpret_cast<const uint4*>(smem + src + (ok ? img_chunk(q, fgrp) : ZROW * 64));  // a zero row
+          xf[i] = *reinterpret_cast<const uint4*>(smem + src + (ok ? row64_chunk(q, fgrp) : ZROW * 64));  // a zero row
         }
 #pragma unroll
       for (int j = 0; j < 2; ++j) wf[j] = *reinterpret_cast<const uint4*>(smem + wb + (tap * 2 + j) * 1024 + lane * 16);
@@ -212,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (i < nt) acc[j][i] = Mma35<T>::run(wf[j], xf[i], acc[j][i]);
+          if (i < nt) mma_chunk<T>(acc[j][i], wf[j], xf[i]);
     }
     // no barrier needed before the writes: each phase writes an image nobody reads in this phase (B: 3, C: 1 -- whose
     // last readers finished before B's closing barrier -- D: 2, read last in C)
@@ -226,7 +201,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
           f32x4_t v = acc[j][i];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = p < NPX ? fmaxf(v[e] + bv[e], 0.f) : 0.f;
-          if (p < ROWS) *reinterpret_cast<uint2*>(smem + dst + img_chunk(p, 2 * j + (fgrp >> 1)) + (fgrp & 1) * 8) = pack4_35<T>(v);
+          if (p < ROWS) *reinterpret_cast<uint2*>(smem + dst + row64_chunk(p, 2 * j + (fgrp >> 1)) + (fgrp & 1) * 8) = pack4<T>(v);
         }
     if (ph == 1) wait_vm<0>();  // W4 (issued after B) and W5 have landed before the barrier that opens D / E
     __syncthreads();
@@ -242,7 +217,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
       if (i < nt) {
         const int p = 16 * (wave + 8 * i) + frow;
         const int im = ks == 0 ? 0 : ks == 1 ? 3 : 2;
-        cf[ks][i] = *reinterpret_cast<const uint4*>(smem + im * IMG_BYTES + img_chunk(p, fgrp));
+        cf[ks][i] = *reinterpret_cast<const uint4*>(smem + im * IMG_BYTES + row64_chunk(p, fgrp));
       }
   float* stg = reinterpret_cast<float*>(smem + OFF_W33 + wave * STG_WAVE);
 #pragma unroll 1
@@ -275,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
       for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-          if (i < nt) acc[jj][i] = Mma35<T>::run(wf[jj], cf[ks][i], acc[jj][i]);
+          if (i < nt) mma_chunk<T>(acc[jj][i], wf[jj], cf[ks][i]);
     }
     // One wait for all residual chunks HERE, while no y store of this group is in flight: vmcnt counts loads and stores
     // together and the compiler cannot count a load past a younger store, so a first use further down would become a
@@ -318,8 +293,8 @@ __global__ __launch_bounds__(512, 2) void block35_kernel(const Block35Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------- weight image
-// Per block: W1 | W2 | W3 | W4 | W5 in MFMA A-fragment order (lane l of fragment f holds k = k0 + 8*(l>>4) .. +7 of row
-// r0 + (l&15)):  W1: f = ks*6 + j  (r0 = 16j, k0 = 32ks)   W2..4: f = tap*2 + j  (k0 = 32 tap)   W5: f = ks*16 + j.
+// Per block: W1 | W2 | W3 | W4 | W5 in MFMA A-fragment order (fragment f = rows r0 .. + 15, k = k0 .. + 31):
+//   W1: f = ks*6 + j  (r0 = 16j, k0 = 32ks)   W2..4: f = tap*2 + j  (k0 = 32 tap)   W5: f = ks*16 + j.
 __global__ void block35_repack_kernel(Block35Pack p, uint4* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -335,11 +310,12 @@ __global__ void block35_repack_kernel(Block35Pack p, uint4* __restrict__ out) {
   if (f < 48) { conv = 0; r0 = 16 * (f % 6); k0 = 32 * (f / 6); }
   else if (f < 102) { const int c = (f - 48) / 18, q = (f - 48) % 18; conv = 1 + c; r0 = 16 * (q & 1); k0 = 32 * (q >> 1); }
   else { conv = 4; r0 = 16 * ((f - 102) & 15); k0 = 32 * ((f - 102) >> 4); }
-  const char* w = (const char*)p.w[conv];
-  out[(size_t)f * 64 + lane] = *reinterpret_cast<const uint4*>(w + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + k0 + 8 * (lane >> 4)) * 2);
+  out[(size_t)f * 64 + lane] = GatherA16::load(p.w[conv], p.kpad[conv], r0, k0, lane, 0);
 }
 
-hipError_t block35_repack(const Block35Pack& p, void* out, hipStream_t s) {
+hipError_t block35_repack(const Block35Pack& p, int dtype, void* out, hipStream_t s) {
+  if (dtype == F16P) return block35s_repack(p, out, s);   // its own kernel: the twin permutes W5's k (block35s.hip)
+  if (dtype != BF16 && dtype != F16) return hipErrorInvalidValue;
   hipLaunchKernelGGL(block35_repack_kernel, dim3((B35_FRAGS + 2 + 3) / 4), dim3(256), 0, s, p, (uint4*)out);
   return hipGetLastError();
 }
@@ -348,6 +324,7 @@ hipError_t launch_block35(const Block35Args& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (dtype == BF16) return launch_with_lds<block35_kernel<__bf16>>(a.n, 512, B35_LDS, s, a);
   if (dtype == F16) return launch_with_lds<block35_kernel<_Float16>>(a.n, 512, B35_LDS, s, a);
+  if (dtype == F16P) return launch_block35s(a, s);
   return hipErrorInvalidValue;
 }
 

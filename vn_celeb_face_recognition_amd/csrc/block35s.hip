@@ -24,7 +24,7 @@
 #include <type_traits>
 
 #include "block35.h"
-#include "conv_device.h"
+#include "fused_device.h"
 
 namespace vnf {
 
@@ -46,22 +46,7 @@ constexpr int STG_WAVE = 16 * STG_PITCH;          // 2304 B per wave
 
 // weight image of one block (1-KiB fragments, every (tile, k-step) as a (hi, lo) pair):
 //   W1: k-step major, 8 x 12 | W2, W3, W4: 36 each (tap major, 2 tiles) | W5: k-step major, 3 x 32 (16 tiles) | 2 KiB biases
-constexpr int S35_W1 = 0, S35_W2 = 96, S35_W3 = 132, S35_W4 = 168, S35_W5 = 204, S35_FRAGS = 300;
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ void split4h(const f32x4_t& v, uint2& hi, uint2& lo) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  h4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const sf16 s(v[e]);
-    h[e] = s.hi; l[e] = s.lo;
-  }
-  hi = __builtin_bit_cast(uint2, h);
-  lo = __builtin_bit_cast(uint2, l);
-}
+constexpr int S35_W1 = 0, S35_W2 = 96, S35_W3 = 132, S35_W4 = 168, S35_W5 = 204, S35_FRAGS = 2 * B35_FRAGS;
 
 }  // namespace
 
@@ -71,7 +56,7 @@ __global__ __launch_bounds__(512, 2) void block35_split_kernel(const Block35Args
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 15, fgrp = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   const char* __restrict__ xg = (const char*)a.x + (size_t)img * NPX * a.ldx * 4;
   char* __restrict__ yg = (char*)a.y + (size_t)img * NPX * a.ldy * 4;
   const char* wimg = (const char*)a.wimg;
@@ -160,8 +145,8 @@ __global__ __launch_bounds__(512, 2) void block35_split_kernel(const Block35Args
   uint4 cfh[3][3], cfl[3][3];
   auto to_frag = [&](const f32x4_t& t0, const f32x4_t& t1, uint4& fh, uint4& fl) {
     uint2 h0, l0, h1, l1;
-    split4h(t0, h0, l0);
-    split4h(t1, h1, l1);
+    split4(t0, h0, l0);
+    split4(t1, h1, l1);
     fh = uint4{h0.x, h0.y, h1.x, h1.y};
     fl = uint4{l0.x, l0.y, l1.x, l1.y};
   };
@@ -176,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void block35_split_kernel(const Block35Args
   // accumulator quad (channels 16*jt + 4*fgrp .. +3 of the 32-channel image, pixel p) -> image: hi 8 bytes, lo 64 B on
   auto to_image = [&](const f32x4_t& v, int image_off, int jt, int p) {
     uint2 hi, lo;
-    split4h(v, hi, lo);
+    split4(v, hi, lo);
     const int o = image_off + p * 128 + (((2 * jt + (fgrp >> 1)) ^ (p & 7)) << 4) + (fgrp & 1) * 8;
     *reinterpret_cast<uint2*>(smem + o) = hi;
     *reinterpret_cast<uint2*>(smem + (o ^ 64)) = lo;
@@ -223,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void block35_split_kernel(const Block35Args
         if (i < nt) {
           const int q = 16 * (wave + 8 * i) + frow + dy * IMW + dx;
           const bool ok = (unsigned)(py[i] + dy) < (unsigned)IMW && (unsigned)(px[i] + dx) < (unsigned)IMW;
-          const int o = ok ? q * 128 + ((fgrp ^ (q & 7)) << 4) : ZROW * 128;   // the zero row: all 128 bytes are zero
+          const int o = ok ? ktile_slot(q, fgrp) : ZROW * 128;   // the zero row: all 128 bytes are zero
           xh[i] = *reinterpret_cast<const uint4*>(smem + src + o);
           xl[i] = *reinterpret_cast<const uint4*>(smem + src + (o ^ 64));
         }

@@ -30,7 +30,7 @@
 // convolution from a zero accumulator in ascending 32-deep k steps with k = (kh, kw, c), then the plan's fast epilogue
 // (conv_device.h): v = acc + bias, max(v, 0), round to T -- at the same four points (t8a, t8b, both concat halves).
 #include "block8.h"
-#include "conv_device.h"
+#include "fused_device.h"
 
 namespace vnf {
 
@@ -55,17 +55,13 @@ constexpr int B8_LDS = 34 * KT_BYTES + 256;
 static_assert(B8_G * 9 <= B8_ROWS, "the group's rows fit the two pixel tiles");
 static_assert(B8_LDS <= 160 * 1024, "one workgroup's LDS");
 
+// the plan's fast epilogue on one accumulator quad: v = acc + bias, max(v, 0), round to T
 template <typename T>
 __device__ __forceinline__ uint2 bias_relu_round(const f32x4_t& acc, const f32x4_t& bias) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 o;
+  f32x4_t v;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float v = acc[e] + bias[e];
-    v = fmaxf(v, 0.f);
-    o[e] = (T)v;
-  }
-  return __builtin_bit_cast(uint2, o);
+  for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + bias[e], 0.f);
+  return pack4<T>(v);
 }
 
 }  // namespace
@@ -79,15 +75,13 @@ __global__ __launch_bounds__(B8_WAVES * 64) void block8_chain_kernel(const Block
   const int role = 1 - (int)blockIdx.y;            // the longer role's workgroups are dispatched first
   const int img0 = blockIdx.x * B8_G;
   const int nrows = 9 * min(B8_G, a.n - img0);   // valid pixel rows of this group (>= 9: the grid has no empty group)
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
 
   // ---- weight stream of this wave: fragment f at wp + f * 64 (uint4 units); the first B8_RING go out before the input
   const uint4* wp = reinterpret_cast<const uint4*>(a.wstream) +
                     (size_t)(role == 0 ? wave * B8_SLOT0 : B8_WAVES * B8_SLOT0 + wave * B8_SLOT1) * 64 + lane;
   uint4 wq[B8_RING];
-#pragma unroll
-  for (int r = 0; r < B8_RING; ++r) wq[r] = wp[r * 64];
-  wp += B8_RING * 64;
+  ring_prime(wq, wp);
   // the wave's biases, ahead of the stream: a load issued at a phase boundary would be waited for behind the whole ring
   const int cw = 16 * wave + 4 * fgrp;             // first of the lane's 4 output channels inside a 192-channel convolution
   const f32x4_t bv_red = *reinterpret_cast<const f32x4_t*>(a.bias + role * 192 + cw);
@@ -115,11 +109,10 @@ __global__ __launch_bounds__(B8_WAVES * 64) void block8_chain_kernel(const Block
   }
   __syncthreads();
 
-  // Per-lane LDS offsets inside a [k-tile][32 rows][128 B] image.  B-fragment read of pixel 16*i + frow, k step ks of
-  // K tile kt: kt * KT_BYTES + i * 2048 + (ks & 1 ? rb1 : rb0).  This wave's accumulator quad holds channels
-  // cw .. cw+3 of that pixel: (cw >> 6) K tiles + i * 2048 + wb.
-  const int rb0 = frow * 128 + ((fgrp ^ (frow & 7)) << 4), rb1 = rb0 ^ 64;
-  const int wb = (cw >> 6) * KT_BYTES + frow * 128 + ((((cw & 63) >> 3) ^ (frow & 7)) << 4) + (cw & 4) * 2;
+  // Per-lane LDS offsets inside the K-tile image (fused_device.h).  B-fragment read of pixel 16*i + frow, k step ks of
+  // K tile kt: kt * KT_BYTES + i * 2048 + (ks & 1 ? rb1 : rb0).  This wave's accumulator quad of that pixel: wb + i * 2048.
+  const int rb0 = ktile_slot(frow, fgrp), rb1 = rb0 ^ 64;
+  const int wb = (cw >> 6) * KT_BYTES + frow * 128 + ((((cw & 63) >> 3) ^ (frow & 7)) << 4) + (cw & 4) * 2;   // ktile_quad, written out (trunk17.hip)
   char* yrow = (char*)a.y + ((size_t)(img0 * 9 + frow) * a.ldy + role * 192 + cw) * 2;   // pixel tile i: + i * 16 rows
 
   // ---------------------------------------------------------------- reduce 1x1: rows role * 192 + 16 * wave .. + 15
@@ -133,8 +126,7 @@ __global__ __launch_bounds__(B8_WAVES * 64) void block8_chain_kernel(const Block
         xf[i] = *reinterpret_cast<const uint4*>(smem + OFF_X + (ks >> 1) * KT_BYTES + i * 2048 + ((ks & 1) ? rb1 : rb0));
 #pragma unroll
       for (int i = 0; i < 2; ++i) mma_chunk<T>(acc[i], wq[ks % B8_RING], xf[i]);
-      wq[ks % B8_RING] = *wp;
-      wp += 64;
+      ring_refill(wq, ks, wp);
       __builtin_amdgcn_sched_barrier(0);
     }
     const f32x4_t bv = bv_red;
@@ -177,8 +169,7 @@ __global__ __launch_bounds__(B8_WAVES * 64) void block8_chain_kernel(const Block
       const int s = B8_KS_RED + B8_KS_TAP * ph + ks;
 #pragma unroll
       for (int i = 0; i < 2; ++i) mma_chunk<T>(acc[i], wq[s % B8_RING], xf[i]);
-      wq[s % B8_RING] = *wp;
-      wp += 64;
+      ring_refill(wq, s, wp);
       __builtin_amdgcn_sched_barrier(0);
     }
     const f32x4_t bv = bv_tap[ph];
@@ -201,7 +192,6 @@ __global__ __launch_bounds__(B8_WAVES * 64) void block8_chain_kernel(const Block
 //   role 1   s 0..55    reducer rows 192 + 16w .. +15,  k = 32s .. +31
 //            s 56..73   1x3 rows 16w .. +15,            k = 32(s - 56) .. +31
 //            s 74..91   3x1 rows 16w .. +15,            k = 32(s - 74) .. +31
-// Lane l of a fragment holds the 8 k values k0 + 8*(l>>4) .. +7 of row r0 + (l&15) (the MFMA A-operand map).
 __global__ void block8_repack_kernel(Block8Pack p, uint4* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int frag = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -218,8 +208,7 @@ __global__ void block8_repack_kernel(Block8Pack p, uint4* __restrict__ out) {
     else if (s < B8_FRAGS1) { conv = 2; r0 = 16 * wave; k0 = 32 * (s - B8_KS_RED - B8_KS_TAP); }
   }
   uint4 v = {0u, 0u, 0u, 0u};
-  if (conv >= 0)
-    v = *reinterpret_cast<const uint4*>((const char*)p.w[conv] + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + k0 + 8 * (lane >> 4)) * 2);
+  if (conv >= 0) v = GatherA16::load(p.w[conv], p.kpad[conv], r0, k0, lane, 0);
   out[(size_t)frag * 64 + lane] = v;
 }
 
@@ -233,16 +222,9 @@ hipError_t block8_repack(const Block8Pack& p, void* out, hipStream_t s) {
 hipError_t launch_block8(const Block8Args& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   const dim3 grid((a.n + B8_G - 1) / B8_G, 2);
-  if (dtype == BF16) {
-    allow_dynamic_lds<block8_chain_kernel<__bf16>>(B8_LDS);
-    hipLaunchKernelGGL(block8_chain_kernel<__bf16>, grid, dim3(B8_WAVES * 64), B8_LDS, s, a);
-  } else if (dtype == F16) {
-    allow_dynamic_lds<block8_chain_kernel<_Float16>>(B8_LDS);
-    hipLaunchKernelGGL(block8_chain_kernel<_Float16>, grid, dim3(B8_WAVES * 64), B8_LDS, s, a);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  if (dtype == BF16) return launch_with_lds<block8_chain_kernel<__bf16>>(grid, B8_WAVES * 64, B8_LDS, s, a);
+  if (dtype == F16) return launch_with_lds<block8_chain_kernel<_Float16>>(grid, B8_WAVES * 64, B8_LDS, s, a);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace vnf

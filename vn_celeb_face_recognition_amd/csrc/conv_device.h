@@ -54,10 +54,14 @@ inline void allow_dynamic_lds(int bytes) {
 
 // the fused kernels: opt in to the launch's own dynamic LDS, launch, return the launch status
 template <auto Kernel, class Args>
-inline hipError_t launch_with_lds(int grid, int block, int lds, hipStream_t s, const Args& a) {
+inline hipError_t launch_with_lds(dim3 grid, int block, int lds, hipStream_t s, const Args& a) {
   allow_dynamic_lds<Kernel>(lds);
-  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, s, a);
+  hipLaunchKernelGGL(Kernel, grid, dim3(block), lds, s, a);
   return hipGetLastError();
+}
+template <auto Kernel, class Args>
+inline hipError_t launch_with_lds(int grid, int block, int lds, hipStream_t s, const Args& a) {
+  return launch_with_lds<Kernel>(dim3(grid), block, lds, s, a);
 }
 
 template <typename T>

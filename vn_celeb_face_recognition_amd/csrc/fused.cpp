@@ -11,147 +11,167 @@ namespace vnf {
 
 using Kind = FusedStack::Kind;
 
-// Fused stacks: the per-wave weight streams are gathered on the device from the packed per-convolution weights the
-// plan already uploaded (same folding, same k order), biases are concatenated per block.
+namespace {
+
+// One convolution's biases into a stack's concatenated bias array, device to device.
+hipError_t copy_bias(float* dst, const ConvLayer& L) { return hipMemcpy(dst, L.bias, (size_t)L.cout * 4, hipMemcpyDeviceToDevice); }
+
+// One function per kind: check the layer shapes the kernel is written for, gather the weight stream on the device from
+// the packed per-convolution weights the plan already uploaded (same folding, same k order), concatenate the biases.
+// Each leaves f.active set, or clear when the switch or the dtype leaves the stack to the plan.
+int prepare_stem_mid(Encoder& e, FusedStack& f) {
+  if (!(e.env.fuse & 4)) return VNF_OK;
+  const ConvLayer& c2a = e.convs[f.conv0];
+  const ConvLayer& c2b = e.convs[f.conv0 + 1];
+  if (c2a.cout != 32 || c2a.K != 288 || c2b.cout != 64 || c2b.K != 288 || c2a.ncls != 1 || c2b.ncls != 1)
+    return fail(VNF_E_INVALID, "fused stem: unexpected layer shapes");
+  bool ext_ok = false;
+  if ((e.env.fuse & 8) && f.ext_conv >= 0) {
+    const ConvLayer& c3b = e.convs[f.ext_conv];
+    ext_ok = c3b.cout == 80 && c3b.K == 64 && c3b.KH == 1 && c3b.ncls == 1 && c3b.nseg == 1 && c3b.res_buf < 0 && c3b.act == ACT_RELU &&
+             e.bufs[f.ext_out_buf].C == 80;
+  }
+  if (e.dtype == F16P && !ext_ok) return VNF_OK;   // the planar split-f16 stem kernel (stem_mids.hip) always carries conv2d_3b
+  StemMidPack pk;
+  pk.w[0] = c2a.w; pk.kpad[0] = c2a.Kpad;
+  pk.w[1] = c2b.w; pk.kpad[1] = c2b.Kpad;
+  f.wstream = e.dalloc(stem_mid_wfrag_bytes(e.dtype));
+  f.bias = (float*)e.dalloc(SM_BIAS * 4);
+  if (!f.wstream || !f.bias) return VNF_E_HIP;
+  VNF_HIP(copy_bias(f.bias, c2a));
+  VNF_HIP(copy_bias(f.bias + 32, c2b));
+  VNF_HIP(stem_mid_repack(pk, e.dtype, f.wstream, 0));
+  VNF_HIP(hipDeviceSynchronize());
+  f.macs_alg = c2a.macs_alg + c2b.macs_alg;
+  f.active = true;
+  f.ext = ext_ok;
+  if (ext_ok) f.macs_alg += e.convs[f.ext_conv].macs_alg;
+  return VNF_OK;
+}
+
+int prepare_block35(Encoder& e, FusedStack& f) {
+  if (!(e.env.fuse & 2)) return VNF_OK;
+  static const int rows[5] = {96, 32, 32, 32, 256}, ks[5] = {256, 288, 288, 288, 96}, boff[5] = {0, 96, 128, 160, 192};
+  const size_t wimg_bytes = block35_wimg_bytes(e.dtype);
+  f.wstream = e.dalloc((size_t)f.nblocks * wimg_bytes);
+  f.bias = (float*)e.dalloc((size_t)f.nblocks * B35_BIAS * 4);
+  if (!f.wstream || !f.bias) return VNF_E_HIP;
+  for (int b = 0; b < f.nblocks; ++b) {
+    Block35Pack pk;
+    float* bias = f.bias + (size_t)b * B35_BIAS;
+    pk.bias = bias;
+    for (int c = 0; c < 5; ++c) {
+      const ConvLayer& L = e.convs[f.conv0 + 5 * b + c];
+      if (L.cout != rows[c] || L.K != ks[c] || L.ncls != 1) return fail(VNF_E_INVALID, "fused Block35: unexpected layer shapes");
+      pk.w[c] = L.w;
+      pk.kpad[c] = L.Kpad;
+      VNF_HIP(copy_bias(bias + boff[c], L));
+      f.macs_alg += L.macs_alg;
+    }
+    VNF_HIP(block35_repack(pk, e.dtype, (char*)f.wstream + (size_t)b * wimg_bytes, 0));
+  }
+  VNF_HIP(hipDeviceSynchronize());
+  f.active = true;
+  f.stack = (e.env.fuse & 16) && e.dtype != F16P;
+  f.ext = false;
+  if (f.stack && (e.env.fuse & 32) && f.ext_conv >= 0) {
+    const ConvLayer& t = e.convs[f.ext_conv];
+    const ConvLayer& last_up = e.convs[f.conv0 + 5 * (f.nblocks - 1) + 4];
+    const bool ok = t.KH == 1 && t.KW == 1 && t.K == 256 && t.cout == 192 && t.ncls == 1 && t.nseg == 1 && t.res_buf < 0 &&
+                    t.act == ACT_RELU && !t.out_f32 && t.x_buf == last_up.seg[0].buf && t.x_coff == 0 &&
+                    t.seg[0].buf == f.ext_out_buf && t.seg[0].coff == 0 && e.bufs[f.ext_out_buf].C == 192;
+    if (ok) {
+      f.wtail = e.dalloc(B35_TAIL_BYTES);
+      if (!f.wtail) return VNF_E_HIP;
+      VNF_HIP(block35_tail_repack(t.w, t.Kpad, t.bias, f.wtail, 0));
+      VNF_HIP(hipDeviceSynchronize());
+      f.ext = true;
+      f.macs_alg += t.macs_alg;
+    }
+  }
+  return VNF_OK;
+}
+
+int prepare_block8(Encoder& e, FusedStack& f) {
+  if (!(e.env.fuse & 64) || e.dtype == F16P) return VNF_OK;   // the planar split-f16 dtype keeps the three plan convolutions
+  const ConvLayer& red = e.convs[f.conv0];
+  const ConvLayer& c13 = e.convs[f.conv0 + 1];
+  const ConvLayer& c31 = e.convs[f.conv0 + 2];
+  const std::vector<Buf>& bufs = e.bufs;
+  auto plain = [](const ConvLayer& L, int cout, int K) {
+    return L.cout == cout && L.K == K && L.Kpad == K && L.ncls == 1 && L.res_buf < 0 && L.act == ACT_RELU && !L.out_f32 &&
+           L.sh == 1 && L.sw == 1 && L.H == 3 && L.W == 3 && L.Ho == 3 && L.Wo == 3;
+  };
+  const bool ok =
+      plain(red, 384, 1792) && plain(c13, 192, 576) && plain(c31, 192, 576) && f.last - f.first == 3 &&
+      red.KH == 1 && red.KW == 1 && red.x_buf == f.in_buf && red.x_coff == 0 && bufs[f.in_buf].C == 1792 && red.nseg == 2 &&
+      red.seg[0].c0 == 0 && red.seg[0].c1 == 192 && red.seg[0].buf == f.out_buf && red.seg[0].coff == 0 &&
+      red.seg[1].c0 == 192 && red.seg[1].c1 == 384 && red.seg[1].coff == 0 &&
+      c13.KH == 1 && c13.KW == 3 && c13.ph == 0 && c13.pw == 1 && c13.x_buf == red.seg[1].buf && c13.x_coff == 0 &&
+      c13.nseg == 1 && c13.seg[0].coff == 0 &&
+      c31.KH == 3 && c31.KW == 1 && c31.ph == 1 && c31.pw == 0 && c31.x_buf == c13.seg[0].buf && c31.x_coff == 0 &&
+      c31.nseg == 1 && c31.seg[0].buf == f.out_buf && c31.seg[0].coff == 192 && bufs[f.out_buf].C == 384;
+  if (!ok) return fail(VNF_E_INVALID, "fused Block8 chain: unexpected layer shapes");
+  Block8Pack pk;
+  pk.w[0] = red.w; pk.kpad[0] = red.Kpad;
+  pk.w[1] = c13.w; pk.kpad[1] = c13.Kpad;
+  pk.w[2] = c31.w; pk.kpad[2] = c31.Kpad;
+  f.wstream = e.dalloc(block8_stream_bytes());
+  f.bias = (float*)e.dalloc(B8_BIAS * 4);
+  if (!f.wstream || !f.bias) return VNF_E_HIP;
+  VNF_HIP(copy_bias(f.bias, red));
+  VNF_HIP(copy_bias(f.bias + 384, c13));
+  VNF_HIP(copy_bias(f.bias + 576, c31));
+  VNF_HIP(block8_repack(pk, f.wstream, 0));
+  VNF_HIP(hipDeviceSynchronize());
+  f.macs_alg = red.macs_alg + c13.macs_alg + c31.macs_alg;
+  f.active = true;
+  return VNF_OK;
+}
+
+int prepare_block17(Encoder& e, FusedStack& f) {
+  if (!(e.env.fuse & 1)) return VNF_OK;
+  Trunk17Pack pk;
+  memset(&pk, 0, sizeof pk);
+  pk.nblocks = f.nblocks;
+  static const int rows[4] = {256, 128, 128, 896}, ks[4] = {896, 896, 896, 256}, boff[4] = {0, 256, 384, 512};
+  for (int b = 0; b < f.nblocks; ++b)
+    for (int c = 0; c < 4; ++c) {
+      const ConvLayer& L = e.convs[f.conv0 + 4 * b + c];
+      if (L.cout != rows[c] || L.K != ks[c] || L.Kpad != ks[c] || L.ncls != 1)
+        return fail(VNF_E_INVALID, "fused Block17 stack: unexpected layer shapes");
+      pk.w[b][c] = L.w;
+      pk.kpad[c] = L.Kpad;
+      f.macs_alg += L.macs_alg;
+    }
+  f.wstream = e.dalloc(trunk17_stream_bytes(f.nblocks, e.dtype));
+  f.bias = (float*)e.dalloc((size_t)f.nblocks * T17_BIAS * 4);
+  if (!f.wstream || !f.bias) return VNF_E_HIP;
+  for (int b = 0; b < f.nblocks; ++b)
+    for (int c = 0; c < 4; ++c) VNF_HIP(copy_bias(f.bias + (size_t)b * T17_BIAS + boff[c], e.convs[f.conv0 + 4 * b + c]));
+  VNF_HIP(trunk17_repack(pk, e.dtype, f.wstream, 0));
+  VNF_HIP(hipDeviceSynchronize());
+  f.active = true;
+  return VNF_OK;
+}
+
+}  // namespace
+
+// env.fuse: bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4:
+// the five Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
+// mixed_6a.branch1.0 inside that launch, bit 6: reduce + 1x3 + 3x1 of every Block8 in one launch (bf16 / f16)
 int Encoder::prepare_fused() {
-  // bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4: the five
-  // Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
-  // mixed_6a.branch1.0 inside that launch, bit 6: reduce + 1x3 + 3x1 of every Block8 in one launch (bf16 / f16)
-  const int enabled = env.fuse;
   for (FusedStack& f : fused) {
     f.active = false;
-    if (!enabled || (dtype != BF16 && dtype != F16 && dtype != F16P) || f.nblocks < 1 || f.nblocks > T17_MAX_BLOCKS) continue;
-    if (f.kind == Kind::StemMid) {
-      if (!(enabled & 4)) continue;
-      const ConvLayer& c2a = convs[f.conv0];
-      const ConvLayer& c2b = convs[f.conv0 + 1];
-      if (c2a.cout != 32 || c2a.K != 288 || c2b.cout != 64 || c2b.K != 288 || c2a.ncls != 1 || c2b.ncls != 1)
-        return fail(VNF_E_INVALID, "fused stem: unexpected layer shapes");
-      StemMidPack pk;
-      pk.w[0] = c2a.w; pk.kpad[0] = c2a.Kpad;
-      pk.w[1] = c2b.w; pk.kpad[1] = c2b.Kpad;
-      bool ext_ok = false;
-      if ((enabled & 8) && f.ext_conv >= 0) {
-        const ConvLayer& c3b = convs[f.ext_conv];
-        ext_ok = c3b.cout == 80 && c3b.K == 64 && c3b.KH == 1 && c3b.ncls == 1 && c3b.nseg == 1 && c3b.res_buf < 0 && c3b.act == ACT_RELU &&
-                 bufs[f.ext_out_buf].C == 80;
-      }
-      if (dtype == F16P && !ext_ok) continue;   // the planar split-f16 stem kernel (stem_mids.hip) always carries conv2d_3b
-      f.wstream = dalloc(dtype == F16P ? SMS_WFRAG_BYTES : SM_WFRAG_BYTES);
-      f.bias = (float*)dalloc(SM_BIAS * 4);
-      if (!f.wstream || !f.bias) return VNF_E_HIP;
-      VNF_HIP(hipMemcpy(f.bias, c2a.bias, 32 * 4, hipMemcpyDeviceToDevice));
-      VNF_HIP(hipMemcpy(f.bias + 32, c2b.bias, 64 * 4, hipMemcpyDeviceToDevice));
-      VNF_HIP(dtype == F16P ? stem_mids_repack(pk, f.wstream, 0) : stem_mid_repack(pk, f.wstream, 0));
-      VNF_HIP(hipDeviceSynchronize());
-      f.macs_alg = c2a.macs_alg + c2b.macs_alg;
-      f.active = true;
-      f.ext = ext_ok;
-      if (ext_ok) f.macs_alg += convs[f.ext_conv].macs_alg;
-      continue;
+    if (!env.fuse || (dtype != BF16 && dtype != F16 && dtype != F16P) || f.nblocks < 1 || f.nblocks > T17_MAX_BLOCKS) continue;
+    int rc = VNF_OK;
+    switch (f.kind) {
+      case Kind::StemMid: rc = prepare_stem_mid(*this, f); break;
+      case Kind::Block35: rc = prepare_block35(*this, f); break;
+      case Kind::Block17: rc = prepare_block17(*this, f); break;
+      case Kind::Block8: rc = prepare_block8(*this, f); break;
     }
-    if (f.kind == Kind::Block35) {
-      if (!(enabled & 2)) continue;
-      std::vector<float> bias((size_t)f.nblocks * B35_BIAS, 0.f);
-      static const int rows[5] = {96, 32, 32, 32, 256}, ks[5] = {256, 288, 288, 288, 96}, boff[5] = {0, 96, 128, 160, 192};
-      const size_t wimg_bytes = dtype == F16P ? B35S_WIMG_BYTES : B35_WIMG_BYTES;
-      f.wstream = dalloc((size_t)f.nblocks * wimg_bytes);
-      f.bias = (float*)dalloc(bias.size() * 4);
-      if (!f.wstream || !f.bias) return VNF_E_HIP;
-      for (int b = 0; b < f.nblocks; ++b) {
-        Block35Pack pk;
-        pk.bias = f.bias + (size_t)b * B35_BIAS;
-        for (int c = 0; c < 5; ++c) {
-          const ConvLayer& L = convs[f.conv0 + 5 * b + c];
-          if (L.cout != rows[c] || L.K != ks[c] || L.ncls != 1) return fail(VNF_E_INVALID, "fused Block35: unexpected layer shapes");
-          pk.w[c] = L.w;
-          pk.kpad[c] = L.Kpad;
-          VNF_HIP(hipMemcpy(&bias[(size_t)b * B35_BIAS + boff[c]], L.bias, (size_t)rows[c] * 4, hipMemcpyDeviceToHost));
-          f.macs_alg += L.macs_alg;
-        }
-        VNF_HIP(hipMemcpy(f.bias + (size_t)b * B35_BIAS, &bias[(size_t)b * B35_BIAS], (size_t)B35_BIAS * 4, hipMemcpyHostToDevice));
-        VNF_HIP(dtype == F16P ? block35s_repack(pk, (char*)f.wstream + (size_t)b * wimg_bytes, 0)
-                              : block35_repack(pk, (char*)f.wstream + (size_t)b * wimg_bytes, 0));
-      }
-      VNF_HIP(hipDeviceSynchronize());
-      f.active = true;
-      f.stack = (enabled & 16) && dtype != F16P;
-      f.ext = false;
-      if (f.stack && (enabled & 32) && f.ext_conv >= 0) {
-        const ConvLayer& t = convs[f.ext_conv];
-        const ConvLayer& last_up = convs[f.conv0 + 5 * (f.nblocks - 1) + 4];
-        const bool ok = t.KH == 1 && t.KW == 1 && t.K == 256 && t.cout == 192 && t.ncls == 1 && t.nseg == 1 && t.res_buf < 0 &&
-                        t.act == ACT_RELU && !t.out_f32 && t.x_buf == last_up.seg[0].buf && t.x_coff == 0 &&
-                        t.seg[0].buf == f.ext_out_buf && t.seg[0].coff == 0 && bufs[f.ext_out_buf].C == 192;
-        if (ok) {
-          f.wtail = dalloc(B35_TAIL_BYTES);
-          if (!f.wtail) return VNF_E_HIP;
-          VNF_HIP(block35_tail_repack(t.w, t.Kpad, t.bias, f.wtail, 0));
-          VNF_HIP(hipDeviceSynchronize());
-          f.ext = true;
-          f.macs_alg += t.macs_alg;
-        }
-      }
-      continue;
-    }
-    if (f.kind == Kind::Block8) {
-      if (!(enabled & 64) || dtype == F16P) continue;   // the planar split-f16 dtype keeps the three plan convolutions
-      const ConvLayer& red = convs[f.conv0];
-      const ConvLayer& c13 = convs[f.conv0 + 1];
-      const ConvLayer& c31 = convs[f.conv0 + 2];
-      auto plain = [](const ConvLayer& L, int cout, int K) {
-        return L.cout == cout && L.K == K && L.Kpad == K && L.ncls == 1 && L.res_buf < 0 && L.act == ACT_RELU && !L.out_f32 &&
-               L.sh == 1 && L.sw == 1 && L.H == 3 && L.W == 3 && L.Ho == 3 && L.Wo == 3;
-      };
-      const bool ok =
-          plain(red, 384, 1792) && plain(c13, 192, 576) && plain(c31, 192, 576) && f.last - f.first == 3 &&
-          red.KH == 1 && red.KW == 1 && red.x_buf == f.in_buf && red.x_coff == 0 && bufs[f.in_buf].C == 1792 && red.nseg == 2 &&
-          red.seg[0].c0 == 0 && red.seg[0].c1 == 192 && red.seg[0].buf == f.out_buf && red.seg[0].coff == 0 &&
-          red.seg[1].c0 == 192 && red.seg[1].c1 == 384 && red.seg[1].coff == 0 &&
-          c13.KH == 1 && c13.KW == 3 && c13.ph == 0 && c13.pw == 1 && c13.x_buf == red.seg[1].buf && c13.x_coff == 0 &&
-          c13.nseg == 1 && c13.seg[0].coff == 0 &&
-          c31.KH == 3 && c31.KW == 1 && c31.ph == 1 && c31.pw == 0 && c31.x_buf == c13.seg[0].buf && c31.x_coff == 0 &&
-          c31.nseg == 1 && c31.seg[0].buf == f.out_buf && c31.seg[0].coff == 192 && bufs[f.out_buf].C == 384;
-      if (!ok) return fail(VNF_E_INVALID, "fused Block8 chain: unexpected layer shapes");
-      Block8Pack pk;
-      pk.w[0] = red.w; pk.kpad[0] = red.Kpad;
-      pk.w[1] = c13.w; pk.kpad[1] = c13.Kpad;
-      pk.w[2] = c31.w; pk.kpad[2] = c31.Kpad;
-      f.wstream = dalloc(block8_stream_bytes());
-      f.bias = (float*)dalloc(B8_BIAS * 4);
-      if (!f.wstream || !f.bias) return VNF_E_HIP;
-      VNF_HIP(hipMemcpy(f.bias, red.bias, 384 * 4, hipMemcpyDeviceToDevice));
-      VNF_HIP(hipMemcpy(f.bias + 384, c13.bias, 192 * 4, hipMemcpyDeviceToDevice));
-      VNF_HIP(hipMemcpy(f.bias + 576, c31.bias, 192 * 4, hipMemcpyDeviceToDevice));
-      VNF_HIP(block8_repack(pk, f.wstream, 0));
-      VNF_HIP(hipDeviceSynchronize());
-      f.macs_alg = red.macs_alg + c13.macs_alg + c31.macs_alg;
-      f.active = true;
-      continue;
-    }
-    if (!(enabled & 1)) continue;
-    Trunk17Pack pk;
-    memset(&pk, 0, sizeof pk);
-    pk.nblocks = f.nblocks;
-    std::vector<float> bias((size_t)f.nblocks * T17_BIAS, 0.f);
-    static const int rows[4] = {256, 128, 128, 896}, ks[4] = {896, 896, 896, 256}, boff[4] = {0, 256, 384, 512};
-    bool ok = true;
-    for (int b = 0; b < f.nblocks && ok; ++b)
-      for (int c = 0; c < 4 && ok; ++c) {
-        const ConvLayer& L = convs[f.conv0 + 4 * b + c];
-        if (L.cout != rows[c] || L.K != ks[c] || L.Kpad != ks[c] || L.ncls != 1) { ok = false; break; }
-        pk.w[b][c] = L.w;
-        pk.kpad[c] = L.Kpad;
-        VNF_HIP(hipMemcpy(&bias[(size_t)b * T17_BIAS + boff[c]], L.bias, (size_t)rows[c] * 4, hipMemcpyDeviceToHost));
-        f.macs_alg += L.macs_alg;
-      }
-    if (!ok) return fail(VNF_E_INVALID, "fused Block17 stack: unexpected layer shapes");
-    f.wstream = dalloc(dtype == F16P ? trunk17s_stream_bytes(f.nblocks) : trunk17_stream_bytes(f.nblocks));
-    f.bias = (float*)upload(bias.data(), bias.size() * 4);
-    if (!f.wstream || !f.bias) return VNF_E_HIP;
-    VNF_HIP(dtype == F16P ? trunk17s_repack(pk, f.wstream, 0) : trunk17_repack(pk, f.wstream, 0));
-    VNF_HIP(hipDeviceSynchronize());
-    f.active = true;
+    if (rc != VNF_OK) return rc;
   }
   return VNF_OK;
 }
@@ -206,7 +226,7 @@ int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
         sa.w3b = c3b.w; sa.b3b = c3b.bias; sa.k3b_pad = c3b.Kpad;
       }
       what = "fused stem";
-      err = dtype == F16P ? launch_stem_mids(sa, s) : launch_stem_mid(sa, dtype, s);
+      err = launch_stem_mid(sa, dtype, s);
       break;
     }
     case Kind::Block35:
@@ -234,9 +254,9 @@ int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
         ba.x = at(up.res_buf, n0); ba.ldx = bufs[up.res_buf].C;
         ba.y = at(up.seg[0].buf, n0); ba.ldy = bufs[up.seg[0].buf].C;
         ba.n = nn;
-        ba.wimg = (const char*)f.wstream + (size_t)b * (dtype == F16P ? B35S_WIMG_BYTES : B35_WIMG_BYTES);
+        ba.wimg = (const char*)f.wstream + (size_t)b * block35_wimg_bytes(dtype);
         ba.zero = conv_zero_page();
-        err = dtype == F16P ? launch_block35s(ba, s) : launch_block35(ba, dtype, s);
+        err = launch_block35(ba, dtype, s);
       }
       break;
     case Kind::Block17: {
@@ -246,7 +266,7 @@ int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
       ta.n = nn; ta.nblocks = f.nblocks;
       ta.wstream = f.wstream; ta.bias = f.bias;
       what = "fused Block17 stack";
-      err = dtype == F16P ? launch_trunk17s(ta, s) : launch_trunk17(ta, dtype, s);
+      err = launch_trunk17(ta, dtype, s);
       break;
     }
     case Kind::Block8: {

@@ -29,7 +29,7 @@
 // (kh,kw,c) in order, bias added after the sum), so the result is bit-identical to it.
 #include <type_traits>
 
-#include "conv_device.h"
+#include "fused_device.h"
 #include "stamp.h"
 #include "stem_mid.h"
 
@@ -48,28 +48,6 @@ constexpr int OFF_ZROW = OFF_B2 + B2_RING * B2_ROW;   // zero row (2b's vertical
 constexpr int P_ROW = 38 * 128;                       // pooled row (conv2d_3b fusion): 38 px x 64 ch, layout of a 2b row
 constexpr int OFF_P = OFF_ZROW + A2_ROW;              // two pooled rows (written at odd steps, consumed one step later)
 constexpr int SM_LDS = OFF_P + 2 * P_ROW;
-
-template <typename T> struct MmaS;
-template <> struct MmaS<__bf16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-  }
-};
-template <> struct MmaS<_Float16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), c, 0, 0, 0);
-  }
-};
-
-// 16-byte chunk `chunk` (0..3 = 8 channels each) of pixel q inside a [px][64 B] row; XOR swizzle as block35.hip
-__device__ __forceinline__ int row_chunk(int q, int chunk) { return q * 64 + ((chunk ^ ((0 - (q >> 2)) & 3)) << 4); }
-
-template <typename T>
-__device__ __forceinline__ uint2 pack4s(const f32x4_t& v) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 r = {(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-  return __builtin_bit_cast(uint2, r);
-}
 
 // max of 8 non-negative 16-bit floats (the rows are ReLU outputs): for values >= 0 the bf16 / f16 bit patterns order
 // like 16-bit integers, so the maximum is four v_pk_max_i16 -- through fp32 converts the pooling alone cost more VALU
@@ -111,7 +89,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
   };
   const int frow = lane & 15, fgrp = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   const char* __restrict__ xg = (const char*)a.x + (size_t)img * W1A * W1A * a.ldx * 2;
   char* __restrict__ yg = (char*)a.y + (size_t)img * WP * WP * a.ldy * 2;
 
@@ -178,12 +156,12 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
   // does not change -- recomputing it per fragment cost ~10 VALU instructions per MFMA and made the kernel VALU-bound.
   int rd[3];            // read offset of pixel 16*pt0 + frow + k, k = 0..2 (2a: k = dx; 2b: k = dx + 1 with its +1 column pad)
 #pragma unroll
-  for (int k = 0; k < 3; ++k) rd[k] = row_chunk(16 * pt0 + frow + k, fgrp);
+  for (int k = 0; k < 3; ++k) rd[k] = row64_chunk(16 * pt0 + frow + k, fgrp);
   int st2a[2], st2b[2];   // store offsets of this lane's channel quad per channel tile (+ i * 1024 / (pt0 + i) * 2048)
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const int c2a = 16 * c + 4 * fgrp;                                          // 2a output channel of the quad
-    st2a[c] = row_chunk(16 * pt0 + frow + 1, c2a >> 3) + (c2a & 4) * 2;
+    st2a[c] = row64_chunk(16 * pt0 + frow + 1, c2a >> 3) + (c2a & 4) * 2;
     st2b[c] = frow * 128 + (((2 * (ct0 + c) + (fgrp >> 1)) ^ (frow & 7)) << 4) + (fgrp & 1) * 8;
   }
   // pooling: 38 px x 8 chunks of 16 B = 304 items per pooled row: one per lane of the four 2b waves (in-kernel timers:
@@ -274,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
 #pragma unroll
             for (int i = 0; i < NPT; ++i)
 #pragma unroll
-              for (int c = 0; c < 2; ++c) acc[c][i] = MmaS<T>::run(wf[c][t0 + d], x[d][i], acc[c][i]);
+              for (int c = 0; c < 2; ++c) mma_chunk<T>(acc[c][i], wf[c][t0 + d], x[d][i]);
         };
         if constexpr (IS2B) {
           mma(xa, 0);
@@ -298,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
               for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] + bias[c][e], 0.f);
               // 2b row: [px][8 chunks of 16 B], chunk index XORed with px & 7 -- unswizzled, the 16 pixels of a store
               // would sit 128 B apart on ONE bank (16-way conflict on every store of every 2b wave)
-              *reinterpret_cast<uint2*>(dst + st2b[c] + i * 2048) = pack4s<T>(v);
+              *reinterpret_cast<uint2*>(dst + st2b[c] + i * 2048) = pack4<T>(v);
             }
         } else {
           char* dst = smem + OFF_A2 + (s % A2_RING) * A2_ROW;
@@ -310,7 +288,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
               f32x4_t v = acc[c][i];
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] + bias[c][e], 0.f);
-              if (x < W2) *reinterpret_cast<uint2*>(dst + st2a[c] + i * 1024) = pack4s<T>(v);
+              if (x < W2) *reinterpret_cast<uint2*>(dst + st2a[c] + i * 1024) = pack4<T>(v);
             }
         }
         stamp(2);
@@ -331,20 +309,20 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
             f32x4_t v = acc;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] + bb[e], 0.f);
-            *reinterpret_cast<uint2*>(yg + ((size_t)(p * WP + px) * a.ldy + 16 * ct + 4 * fgrp) * 2) = pack4s<T>(v);
+            *reinterpret_cast<uint2*>(yg + ((size_t)(p * WP + px) * a.ldy + 16 * ct + 4 * fgrp) * 2) = pack4<T>(v);
           }
         };
 #pragma unroll
         for (int pt = 0; pt < 3; ++pt) {
           const uint4 x0 = bfrag(pt, 0), x1 = bfrag(pt, 1);
           f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-          acc = MmaS<T>::run(w3[0][0], x0, acc);
-          acc = MmaS<T>::run(w3[0][1], x1, acc);
+          mma_chunk<T>(acc, w3[0][0], x0);
+          mma_chunk<T>(acc, w3[0][1], x1);
           emit(wave - 4, pt, acc, b3[0]);
           if (pt == wave - 4) {       // wave-uniform: the shared fifth channel tile, this wave's pixel tile
             f32x4_t acc4 = {0.f, 0.f, 0.f, 0.f};
-            acc4 = MmaS<T>::run(w3[1][0], x0, acc4);
-            acc4 = MmaS<T>::run(w3[1][1], x1, acc4);
+            mma_chunk<T>(acc4, w3[1][0], x0);
+            mma_chunk<T>(acc4, w3[1][1], x1);
             emit(4, pt, acc4, b3[1]);
           }
         }
@@ -399,20 +377,22 @@ __global__ __launch_bounds__(512, 2) void stem_mid_kernel(const StemMidArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- weight fragments
-// 6 tiles x 9 taps of 1 KiB in MFMA A-fragment order: tiles 0,1 = conv2d_2a channels 0..31, tiles 2..5 = conv2d_2b
-// channels 0..63; lane l of fragment (tile, tap) holds k = 32*tap + 8*(l>>4) .. +7 of output channel 16*tile' + (l&15).
+// stem_mid.h has the fragment order; G gathers one fragment from the packed weights (fused_device.h): the 16-bit image
+// and the planar twin's (hi, lo) image are this one kernel.
+template <typename G>
 __global__ void stem_mid_repack_kernel(StemMidPack p, uint4* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (f >= 54) return;
-  const int tile = f / 9, tap = f % 9;
+  const int fp = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (fp >= SM_FRAGS * G::PLANES) return;
+  const int f = fp / G::PLANES, tile = f / 9, tap = f % 9;
   const int conv = tile < 2 ? 0 : 1, r0 = 16 * (tile < 2 ? tile : tile - 2);
-  const char* w = (const char*)p.w[conv];
-  out[(size_t)f * 64 + lane] = *reinterpret_cast<const uint4*>(w + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + 32 * tap + 8 * (lane >> 4)) * 2);
+  out[(size_t)fp * 64 + lane] = G::load(p.w[conv], p.kpad[conv], r0, 32 * tap, lane, fp % G::PLANES);
 }
 
-hipError_t stem_mid_repack(const StemMidPack& p, void* out, hipStream_t s) {
-  hipLaunchKernelGGL(stem_mid_repack_kernel, dim3(14), dim3(256), 0, s, p, (uint4*)out);
+hipError_t stem_mid_repack(const StemMidPack& p, int dtype, void* out, hipStream_t s) {
+  if (dtype == F16P) hipLaunchKernelGGL(stem_mid_repack_kernel<GatherA16P>, dim3(SM_FRAGS / 2), dim3(256), 0, s, p, (uint4*)out);
+  else if (dtype == BF16 || dtype == F16) hipLaunchKernelGGL(stem_mid_repack_kernel<GatherA16>, dim3((SM_FRAGS + 3) / 4), dim3(256), 0, s, p, (uint4*)out);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
@@ -440,6 +420,7 @@ hipError_t launch_stem_mid(const StemMidArgs& a, int dtype, hipStream_t s) {
 #endif
   if (dtype == BF16) return launch_with_lds<stem_mid_kernel<__bf16>>(a.n, 512, SM_LDS, s, a);
   if (dtype == F16) return launch_with_lds<stem_mid_kernel<_Float16>>(a.n, 512, SM_LDS, s, a);
+  if (dtype == F16P) return launch_stem_mids(a, s);
   return hipErrorInvalidValue;
 }
 

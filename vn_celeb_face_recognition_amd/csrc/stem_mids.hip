@@ -25,7 +25,7 @@
 //   waves 4-7: 2a, channel tile = wave & 1, pixel tiles {0,1,2} (waves 4,5) or {3,4} (waves 6,7); pooling; conv2d_3b
 #include <type_traits>
 
-#include "conv_device.h"
+#include "fused_device.h"
 #include "stem_mid.h"
 
 namespace vnf {
@@ -41,18 +41,6 @@ constexpr int OFF_IN = 0, OFF_A2 = OFF_IN + IN_RING * ROWB, OFF_VM = OFF_A2 + A2
 constexpr int SMS_LDS = OFF_P + P_ROW;
 static_assert(SMS_LDS <= 160 * 1024, "LDS map");
 
-__device__ __forceinline__ void split4q(const f32x4_t& v, uint2& hi, uint2& lo) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  h4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const sf16 s(v[e]);
-    h[e] = s.hi; l[e] = s.lo;
-  }
-  hi = __builtin_bit_cast(uint2, h);
-  lo = __builtin_bit_cast(uint2, l);
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArgs a) {
@@ -61,7 +49,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArg
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow = lane & 15, fgrp = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   const char* __restrict__ xg = (const char*)a.x + (size_t)img * W1A * W1A * a.ldx * 4;
   char* __restrict__ yg = (char*)a.y + (size_t)img * WP * WP * a.ldy * 4;
 
@@ -132,8 +120,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArg
   int rd[3];            // read offset of pixel 16*pt0 + frow + k, k = 0..2 (2a: k = dx; 2b: k = dx + 1 with its +1 column pad)
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const int px = 16 * pt0 + frow + k;
-    rd[k] = px * 128 + ((fgrp ^ (px & 7)) << 4);
+    rd[k] = ktile_slot(16 * pt0 + frow + k, fgrp);
   }
   const int c2a = 16 * (wave & 1) + 4 * fgrp;                                  // 2a output channel of this lane's quad
   const int x2a = 16 * pt0 + frow + 1;                                         // A2 column of this lane's pixel (tile 0)
@@ -221,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArg
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[i][e] + bias[e], 0.f);
             uint2 hi, lo;
-            split4q(v, hi, lo);
+            split4(v, hi, lo);
             if (x < W2) {
               *reinterpret_cast<uint2*>(dst + st2a + i * 2048) = hi;
               *reinterpret_cast<uint2*>(dst + ((st2a + i * 2048) ^ 64)) = lo;
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArg
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + bb[e], 0.f);
             uint2 hi, lo;
-            split4q(v, hi, lo);
+            split4(v, hi, lo);
             char* d = yg + (size_t)(p * WP + px) * a.ldy * 4 + (2 * ct + (fgrp >> 1)) * 32 + (fgrp & 1) * 8;
             *reinterpret_cast<uint2*>(d) = hi;
             *reinterpret_cast<uint2*>(d + 16) = lo;
@@ -322,27 +309,7 @@ __global__ __launch_bounds__(512, 2) void stem_mid_split_kernel(const StemMidArg
   }
 }
 
-// ---------------------------------------------------------------------------------------------- weight fragments
-// 6 tiles x 9 taps x (hi, lo) of 1 KiB in MFMA A-fragment order: tiles 0,1 = conv2d_2a channels 0..31, tiles 2..5 =
-// conv2d_2b channels 0..63; lane l of fragment (tile, tap, plane) holds k = 32*tap + 8*(l>>4) .. +7 of output channel
-// 16*tile' + (l&15).  Packed engine weights: K tile of 32 k values = [32 hi halves][32 lo halves].
-__global__ void stem_mids_repack_kernel(StemMidPack p, uint4* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int fp = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (fp >= 108) return;
-  const int f = fp >> 1, plane = fp & 1;
-  const int tile = f / 9, tap = f % 9;
-  const int conv = tile < 2 ? 0 : 1, r0 = 16 * (tile < 2 ? tile : tile - 2);
-  const char* w = (const char*)p.w[conv];
-  out[(size_t)fp * 64 + lane] =
-      *reinterpret_cast<const uint4*>(w + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + 32 * tap) * 4 + plane * 64 + (lane >> 4) * 16);
-}
-
-hipError_t stem_mids_repack(const StemMidPack& p, void* out, hipStream_t s) {
-  hipLaunchKernelGGL(stem_mids_repack_kernel, dim3(27), dim3(256), 0, s, p, (uint4*)out);
-  return hipGetLastError();
-}
-
+// the weight fragments: stem_mid_repack (stem_mid.hip), every (tile, tap) as a (hi, lo) pair
 hipError_t launch_stem_mids(const StemMidArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (!a.w3b || !a.b3b) return hipErrorInvalidValue;   // the split kernel always carries conv2d_3b

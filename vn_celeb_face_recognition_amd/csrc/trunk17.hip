@@ -25,7 +25,7 @@
 //
 // Numerics: 16-bit MFMA operands (bf16 or f16) with fp32 accumulation, as the unfused plan; the trunk itself is fp32
 // here (the unfused plan rounds it to 16 bits after every block), so this path is the more accurate of the two.
-#include "conv_device.h"
+#include "fused_device.h"
 #include "trunk17.h"
 
 namespace vnf {
@@ -41,33 +41,7 @@ constexpr int OFF_CATLO = 14 * KT_BYTES;           // 2 K tiles: concat channels
 constexpr int OFF_TA = 16 * KT_BYTES;              // 2 K tiles: branch1.0 output
 constexpr int OFF_ZERO = 18 * KT_BYTES;            // 256 zero bytes: out-of-image taps
 constexpr int T17_LDS = 18 * KT_BYTES + 256;
-constexpr int RING = 8;                            // weight fragments in flight per wave (divides T17_FRAGS)
-static_assert(T17_FRAGS % RING == 0, "the ring index of a step must not depend on the block");
-
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<_Float16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), c, 0, 0, 0);
-  }
-};
-
-template <typename T>
-__device__ __forceinline__ uint2 pack4(const f32x4_t& v) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 r = {(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-  return __builtin_bit_cast(uint2, r);
-}
-template <typename T>
-__device__ __forceinline__ f32x4_t unpack4(const uint2& u) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 r = __builtin_bit_cast(t4, u);
-  return f32x4_t{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
-}
+static_assert(T17_FRAGS % T17_RING == 0, "the ring index of a step must not depend on the block");
 
 }  // namespace
 
@@ -78,7 +52,7 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow_c = lane & 15, fgrp_c = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
 
   // ---- image -> LDS (the K-tile image of phase 1), by LDS-DMA: piece = 8 pixel rows x 128 B of one K tile
   {
@@ -95,13 +69,12 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
   }
   __syncthreads();
 
-  // Per-lane LDS bases.  A wave's accumulator tiles cover channels 128*j + 16*wave + 4*fgrp + (0..3) of pixel 16*i + frow:
-  // inside a [k-tile][64 rows][128 B] image that is wbase + j * 2 k-tiles + i * 2048 (the swizzle only involves
-  // row & 7 = frow & 7 and the channel bits below 128).  B-fragment reads of pixel 16*i + frow, k-step ks of k-tile kt:
+  // Per-lane LDS bases (fused_device.h).  A wave's accumulator tiles cover channels 128*j + 16*wave + 4*fgrp + (0..3) of
+  // pixel 16*i + frow: wbase + j * 2 k-tiles + i * 2048.  B-fragment reads of pixel 16*i + frow, k-step ks of k-tile kt:
   // kt * KT_BYTES + i * 2048 + rb[ks & 1].
   const int cw = 16 * wave + 4 * fgrp_c;  // channel offset inside a 128-channel group
-  const int wbase_c = (cw >> 6) * KT_BYTES + frow_c * 128 + ((((cw & 63) >> 3) ^ (frow_c & 7)) << 4) + (cw & 4) * 2;
-  const int rb0_c = frow_c * 128 + ((fgrp_c ^ (frow_c & 7)) << 4), rb1_c = rb0_c ^ 64;
+  const int wbase_c = (cw >> 6) * KT_BYTES + frow_c * 128 + ((((cw & 63) >> 3) ^ (frow_c & 7)) << 4) + (cw & 4) * 2;   // ktile_quad, written out: through the helper this kernel's address arithmetic folds differently
+  const int rb0_c = ktile_slot(frow_c, fgrp_c), rb1_c = rb0_c ^ 64;
 
   // ---- trunk registers
   f32x4_t trunk[7][4];
@@ -112,11 +85,9 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
       trunk[j][i] = unpack4<T>(*reinterpret_cast<const uint2*>(smem + OFF_XB + wbase_c + j * 2 * KT_BYTES + i * 2048));
 
   // ---- weight stream of this wave: fragment f of block b at wbase + (b * T17_FRAGS + f) * 64 + lane (uint4 units)
-  const uint4* wp = reinterpret_cast<const uint4*>(a.wstream) + (size_t)wave * ((size_t)a.nblocks * T17_FRAGS + RING) * 64 + lane;
-  uint4 wq[RING];
-#pragma unroll
-  for (int r = 0; r < RING; ++r) wq[r] = wp[r * 64];
-  wp += RING * 64;  // next fragment to fetch
+  const uint4* wp = reinterpret_cast<const uint4*>(a.wstream) + (size_t)wave * ((size_t)a.nblocks * T17_FRAGS + T17_RING) * 64 + lane;
+  uint4 wq[T17_RING];
+  ring_prime(wq, wp);
 
   for (int b = 0; b < a.nblocks; ++b) {
     const float* bias = a.bias + (size_t)b * T17_BIAS + cw;
@@ -153,9 +124,8 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
         for (int j = 0; j < 2; ++j) {
           const int s = ks * 2 + j;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) acc[j][i] = Mma<T>::run(wq[s % RING], xf[i], acc[j][i]);
-          wq[s % RING] = *wp;
-          wp += 64;
+          for (int i = 0; i < 4; ++i) mma_chunk<T>(acc[j][i], wq[s % T17_RING], xf[i]);
+          ring_refill(wq, s, wp);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep one k-step's fragments live at a time (register budget)
       }
@@ -204,9 +174,8 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
         }
         const int s = 56 + 28 * ph + ks;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = Mma<T>::run(wq[s % RING], xf[i], acc[i]);
-        wq[s % RING] = *wp;
-        wp += 64;
+        for (int i = 0; i < 4; ++i) mma_chunk<T>(acc[i], wq[s % T17_RING], xf[i]);
+        ring_refill(wq, s, wp);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -229,9 +198,8 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
       for (int j = 0; j < 7; ++j) {
         const int s = 112 + ks * 7 + j;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) trunk[j][i] = Mma<T>::run(wq[s % RING], xf[i], trunk[j][i]);
-        wq[s % RING] = *wp;
-        wp += 64;
+        for (int i = 0; i < 4; ++i) mma_chunk<T>(trunk[j][i], wq[s % T17_RING], xf[i]);
+        ring_refill(wq, s, wp);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -267,38 +235,30 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_kernel(const Trunk17Args
 }
 
 // ---------------------------------------------------------------------------------------------- weight stream
-// Fragment order of one wave within one block (must match the kernel's consumption order):
-//   reduce : for ks in 0..27, j in 0..1   rows 128j+16w .. +15,  k = 32ks .. +31      (56)
-//   1x7    : for ks in 0..27              rows 16w .. +15,       k = 32ks .. +31      (28)
-//   7x1    : for ks in 0..27              rows 16w .. +15,       k = 32ks .. +31      (28)
-//   up     : for ks in 0..7, j in 0..6    rows 128j+16w .. +15,  k = 32ks .. +31      (56)
-// Lane l of a fragment holds the 8 k values k0 + 8*(l>>4) .. +7 of row r0 + (l&15) (the MFMA A-operand map).
-__global__ void trunk17_repack_kernel(Trunk17Pack p, uint4* __restrict__ out) {
+// trunk17.h has the fragment order; G gathers one fragment from the packed weights (fused_device.h): the 16-bit stream
+// and the planar twin's (hi, lo) stream are this one kernel.
+template <typename G>
+__global__ void trunk17_repack_kernel(Trunk17Pack p, size_t per_wave, uint4* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const size_t frag = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const size_t per_wave = (size_t)p.nblocks * T17_FRAGS + RING;
   if (frag >= 8 * per_wave) return;
   const int wave = (int)(frag / per_wave);
   const size_t f = frag - (size_t)wave * per_wave;
   uint4 v = {0u, 0u, 0u, 0u};
-  if (f < (size_t)p.nblocks * T17_FRAGS) {
-    const int b = (int)(f / T17_FRAGS), s = (int)(f - (size_t)b * T17_FRAGS);
-    int conv, r0, k0;
-    if (s < 56) { conv = 0; r0 = 128 * (s & 1) + 16 * wave; k0 = 32 * (s >> 1); }
-    else if (s < 84) { conv = 1; r0 = 16 * wave; k0 = 32 * (s - 56); }
-    else if (s < 112) { conv = 2; r0 = 16 * wave; k0 = 32 * (s - 84); }
-    else { conv = 3; r0 = 128 * ((s - 112) % 7) + 16 * wave; k0 = 32 * ((s - 112) / 7); }
-    const char* w = (const char*)p.w[b][conv];
-    v = *reinterpret_cast<const uint4*>(w + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + k0 + 8 * (lane >> 4)) * 2);
+  if (f < (size_t)p.nblocks * T17_FRAGS * G::PLANES) {
+    const int b = (int)(f / (T17_FRAGS * G::PLANES)), sp = (int)(f - (size_t)b * (T17_FRAGS * G::PLANES));
+    const Trunk17Frag fr = trunk17_frag(sp / G::PLANES, wave);
+    v = G::load(p.w[b][fr.conv], p.kpad[fr.conv], fr.r0, fr.k0, lane, sp % G::PLANES);
   }
   out[frag * 64 + lane] = v;
 }
 
-size_t trunk17_stream_bytes(int nblocks) { return (size_t)8 * ((size_t)nblocks * T17_FRAGS + RING) * 1024; }
-
-hipError_t trunk17_repack(const Trunk17Pack& p, void* out, hipStream_t s) {
-  const size_t frags = (size_t)8 * ((size_t)p.nblocks * T17_FRAGS + RING);
-  hipLaunchKernelGGL(trunk17_repack_kernel, dim3((unsigned)((frags + 3) / 4)), dim3(256), 0, s, p, (uint4*)out);
+hipError_t trunk17_repack(const Trunk17Pack& p, int dtype, void* out, hipStream_t s) {
+  if (dtype != BF16 && dtype != F16 && dtype != F16P) return hipErrorInvalidValue;
+  const size_t per_wave = trunk17_wave_frags(p.nblocks, dtype);
+  const dim3 grid((unsigned)((8 * per_wave + 3) / 4));
+  if (dtype == F16P) hipLaunchKernelGGL(trunk17_repack_kernel<GatherA16P>, grid, dim3(256), 0, s, p, per_wave, (uint4*)out);
+  else hipLaunchKernelGGL(trunk17_repack_kernel<GatherA16>, grid, dim3(256), 0, s, p, per_wave, (uint4*)out);
   return hipGetLastError();
 }
 
@@ -306,6 +266,7 @@ hipError_t launch_trunk17(const Trunk17Args& a, int dtype, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   if (dtype == BF16) return launch_with_lds<block17_trunk_kernel<__bf16>>(a.n, 512, T17_LDS, s, a);
   if (dtype == F16) return launch_with_lds<block17_trunk_kernel<_Float16>>(a.n, 512, T17_LDS, s, a);
+  if (dtype == F16P) return launch_trunk17s(a, s);
   return hipErrorInvalidValue;
 }
 

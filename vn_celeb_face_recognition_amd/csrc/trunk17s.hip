@@ -21,7 +21,7 @@
 // Numerics: fp32-class (~22 significant bits per operand); the trunk is never rounded below fp32 between blocks.
 #include <type_traits>
 
-#include "conv_device.h"
+#include "fused_device.h"
 #include "trunk17.h"
 
 namespace vnf {
@@ -39,31 +39,11 @@ constexpr int OFF_TA = 12 * IMG;                   // 4 images: branch1.0 output
 constexpr int OFF_ZERO = 16 * IMG;                 // 256 zero bytes: out-of-image taps (dead space after pass 1)
 constexpr int S17_LDS = 20 * IMG;
 constexpr int S17_FRAGS = 2 * T17_FRAGS;           // 336: 112 reduce + 56 (1x7) + 56 (7x1) + 112 up
-#ifndef T17S_RING
-#define T17S_RING 8
-#endif
 #ifndef T17S_P1
 #define T17S_P1 0
 #endif
 constexpr int RING = T17S_RING;                    // fragments in flight per wave: (hi, lo) pairs
 static_assert(S17_FRAGS % RING == 0, "the ring index of a step must not depend on the block");
-
-__device__ __forceinline__ void split4(const f32x4_t& v, uint2& hi, uint2& lo) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  h4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const sf16 s(v[e]);
-    h[e] = s.hi; l[e] = s.lo;
-  }
-  hi = __builtin_bit_cast(uint2, h);
-  lo = __builtin_bit_cast(uint2, l);
-}
-__device__ __forceinline__ f32x4_t join4(const uint2& hi, const uint2& lo) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 h = __builtin_bit_cast(h4, hi), l = __builtin_bit_cast(h4, lo);
-  return f32x4_t{(float)h[0] + (float)l[0], (float)h[1] + (float)l[1], (float)h[2] + (float)l[2], (float)h[3] + (float)l[3]};
-}
 
 }  // namespace
 
@@ -73,7 +53,7 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int frow_c = lane & 15, fgrp_c = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   const char* const xsrc = (const char*)a.x + (size_t)img * S17_PX * a.ldx * 4;
 
   // image -> LDS by LDS-DMA: piece = 8 pixel rows x 128 B of one tile image; logical slot q of a row = hi (q < 4) or lo
@@ -88,13 +68,12 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-  // Per-lane LDS bases.  A wave's accumulator tiles cover channels 128*j + 16*wave + 4*fgrp + (0..3) of pixel 16*i + frow:
-  // inside the [image][64 rows][128 B] layout that is wbase + 4*j images + i * 2048 for the hi halves (8 bytes), the lo
-  // halves 64 bytes further (slot ^ 4).  B-fragment reads of pixel 16*i + frow, k-step (= image) s: s * IMG + i * 2048 +
-  // rb0 (hi) / rb1 (lo).
+  // Per-lane LDS bases (fused_device.h, the planar image).  A wave's accumulator tiles cover channels 128*j + 16*wave +
+  // 4*fgrp + (0..3) of pixel 16*i + frow: wbase + 4*j images + i * 2048 for the hi halves, the lo halves at ^ 64.
+  // B-fragment reads of pixel 16*i + frow, k-step (= image) s: s * IMG + i * 2048 + rb0 (hi) / rb1 (lo).
   const int cw = 16 * wave + 4 * fgrp_c;  // channel offset inside a 128-channel group
-  const int wbase_c = (cw >> 5) * IMG + frow_c * 128 + ((((cw & 31) >> 3) ^ (frow_c & 7)) << 4) + (cw & 4) * 2;
-  const int rb0_c = frow_c * 128 + ((fgrp_c ^ (frow_c & 7)) << 4), rb1_c = rb0_c ^ 64;
+  const int wbase_c = ktile_quad<IMG, 32>(cw, frow_c);
+  const int rb0_c = ktile_slot(frow_c, fgrp_c), rb1_c = rb0_c ^ 64;
   // every other term of an address below is a multiple of 128, so the lo plane's address is (base ^ 64) + the same terms:
   // the compiler folds those terms into the instructions' immediate offsets instead of keeping one register per address
   const int wlo_c = wbase_c ^ 64;
@@ -125,9 +104,7 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
   // ---- weight stream of this wave: fragment f of block b at (b * S17_FRAGS + f) * 64 + lane (uint4 units)
   const uint4* wp = reinterpret_cast<const uint4*>(a.wstream) + (size_t)wave * ((size_t)a.nblocks * S17_FRAGS + RING) * 64 + lane;
   uint4 wq[RING];
-#pragma unroll
-  for (int r = 0; r < RING; ++r) wq[r] = wp[r * 64];
-  wp += RING * 64;  // next fragment to fetch
+  ring_prime(wq, wp);
 
   for (int b = 0; b < a.nblocks; ++b) {
     const float* bias = a.bias + (size_t)b * T17_BIAS + cw;
@@ -174,11 +151,10 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
           for (int i = 0; i < 4; ++i) acc[j][i] = mfma_f16(wq[s % RING], xh[i], acc[j][i]);
 #pragma unroll
           for (int i = 0; i < 4; ++i) acc[j][i] = mfma_f16(wq[s % RING], xl[i], acc[j][i]);
-          wq[s % RING] = *wp;
+          ring_refill(wq, s, wp);
 #pragma unroll
           for (int i = 0; i < 4; ++i) acc[j][i] = mfma_f16(wq[(s + 1) % RING], xh[i], acc[j][i]);
-          wq[(s + 1) % RING] = wp[64];
-          wp += 128;
+          ring_refill(wq, s + 1, wp);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -292,11 +268,10 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
         for (int i = 0; i < 4; ++i) pacc[i] = mfma_f16(wq[s % RING], xh[i], pacc[i]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) pacc[i] = mfma_f16(wq[s % RING], xl[i], pacc[i]);
-        wq[s % RING] = *wp;
+        ring_refill(wq, s, wp);
 #pragma unroll
         for (int i = 0; i < 4; ++i) pacc[i] = mfma_f16(wq[(s + 1) % RING], xh[i], pacc[i]);
-        wq[(s + 1) % RING] = wp[64];
-        wp += 128;
+        ring_refill(wq, s + 1, wp);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -331,11 +306,10 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
         for (int i = 0; i < 4; ++i) trunk[j][i] = mfma_f16(wq[s % RING], xh[i], trunk[j][i]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) trunk[j][i] = mfma_f16(wq[s % RING], xl[i], trunk[j][i]);
-        wq[s % RING] = *wp;
+        ring_refill(wq, s, wp);
 #pragma unroll
         for (int i = 0; i < 4; ++i) trunk[j][i] = mfma_f16(wq[(s + 1) % RING], xh[i], trunk[j][i]);
-        wq[(s + 1) % RING] = wp[64];
-        wp += 128;
+        ring_refill(wq, s + 1, wp);
         __builtin_amdgcn_sched_barrier(0);   // the refill loads stay behind the tile that frees their registers
       }
     }
@@ -383,45 +357,7 @@ __global__ __launch_bounds__(512, 2) void block17_trunk_split_kernel(const Trunk
   }
 }
 
-// ---------------------------------------------------------------------------------------------- weight stream
-// Fragment order of one wave within one block (must match the kernel's consumption order); every (tile, k-step) is a
-// pair: the hi-plane fragment, then the lo-plane fragment
-//   reduce : for ks in 0..27, j in 0..1   rows 128j+16w .. +15,  k = 32ks .. +31      (112)
-//   1x7    : for ks in 0..27              rows 16w .. +15,       k = 32ks .. +31      (56)
-//   7x1    : for ks in 0..27              rows 16w .. +15,       k = 32ks .. +31      (56)
-//   up     : for ks in 0..7, j in 0..6    rows 128j+16w .. +15,  k = 32ks .. +31      (112)
-// Lane l of a fragment holds the 8 k values k0 + 8*(l>>4) .. +7 of row r0 + (l&15) (the MFMA A-operand map); the packed
-// engine weights keep a K tile of 32 k values as [32 hi halves][32 lo halves] (engine.cpp convert_to F16P).
-__global__ void trunk17s_repack_kernel(Trunk17Pack p, uint4* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const size_t frag = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const size_t per_wave = (size_t)p.nblocks * S17_FRAGS + RING;
-  if (frag >= 8 * per_wave) return;
-  const int wave = (int)(frag / per_wave);
-  const size_t f = frag - (size_t)wave * per_wave;
-  uint4 v = {0u, 0u, 0u, 0u};
-  if (f < (size_t)p.nblocks * S17_FRAGS) {
-    const int b = (int)(f / S17_FRAGS), sp = (int)(f - (size_t)b * S17_FRAGS);
-    const int s = sp >> 1, plane = sp & 1;
-    int conv, r0, k0;
-    if (s < 56) { conv = 0; r0 = 128 * (s & 1) + 16 * wave; k0 = 32 * (s >> 1); }
-    else if (s < 84) { conv = 1; r0 = 16 * wave; k0 = 32 * (s - 56); }
-    else if (s < 112) { conv = 2; r0 = 16 * wave; k0 = 32 * (s - 84); }
-    else { conv = 3; r0 = 128 * ((s - 112) % 7) + 16 * wave; k0 = 32 * ((s - 112) / 7); }
-    const char* w = (const char*)p.w[b][conv];
-    v = *reinterpret_cast<const uint4*>(w + ((size_t)(r0 + (lane & 15)) * p.kpad[conv] + k0) * 4 + plane * 64 + (lane >> 4) * 16);
-  }
-  out[frag * 64 + lane] = v;
-}
-
-size_t trunk17s_stream_bytes(int nblocks) { return (size_t)8 * ((size_t)nblocks * S17_FRAGS + RING) * 1024; }
-
-hipError_t trunk17s_repack(const Trunk17Pack& p, void* out, hipStream_t s) {
-  const size_t frags = (size_t)8 * ((size_t)p.nblocks * S17_FRAGS + RING);
-  hipLaunchKernelGGL(trunk17s_repack_kernel, dim3((unsigned)((frags + 3) / 4)), dim3(256), 0, s, p, (uint4*)out);
-  return hipGetLastError();
-}
-
+// the weight stream: trunk17_repack (trunk17.hip), every fragment of trunk17.h's order as a (hi, lo) pair
 hipError_t launch_trunk17s(const Trunk17Args& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   return launch_with_lds<block17_trunk_split_kernel>(a.n, 512, S17_LDS, s, a);

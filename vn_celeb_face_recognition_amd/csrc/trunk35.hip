@@ -29,7 +29,7 @@
 #include <type_traits>
 
 #include "block35.h"
-#include "conv_device.h"
+#include "fused_device.h"
 #include "stamp.h"
 
 namespace vnf {
@@ -48,31 +48,6 @@ constexpr int OFF_BIAS = OFF_W33 + 2 * W33_BYTES;  // 135168
 constexpr int T35_LDS = OFF_BIAS + 2 * 2048;       // 139264
 static_assert(2 * IMG_BYTES <= 48 * 1024, "the two images live inside the W1 region");
 
-template <typename T> struct Mma;
-template <> struct Mma<__bf16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w), __builtin_bit_cast(bf16x8_t, x), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<_Float16> {
-  static __device__ __forceinline__ f32x4_t run(const uint4& w, const uint4& x, f32x4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, w), __builtin_bit_cast(f16x8_t, x), c, 0, 0, 0);
-  }
-};
-
-template <typename T>
-__device__ __forceinline__ uint2 pack4(const f32x4_t& v) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 r = {(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-  return __builtin_bit_cast(uint2, r);
-}
-template <typename T>
-__device__ __forceinline__ f32x4_t unpack4(const uint2& u) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  const t4 r = __builtin_bit_cast(t4, u);
-  return f32x4_t{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
-}
-
 // Two neighbouring 16-channel tiles of one pixel tile in accumulator layout (lane row q holds channel quad q of each)
 // -> the MFMA B fragment of that 32-channel k-step (lane row r holds channels 8r .. 8r+7):
 //   permlane32_swap: lane rows 2,3 of t0 <-> rows 0,1 of t1;  permlane16_swap: odd rows of t0 <-> even rows of t1
@@ -83,11 +58,6 @@ __device__ __forceinline__ uint4 quads_to_frag(const uint2& t0, const uint2& t1)
   const auto by = __builtin_amdgcn_permlane16_swap(ay[0], ay[1], false, false);
   return uint4{bx[0], by[0], bx[1], by[1]};
 }
-
-__device__ __forceinline__ int img_chunk(int q, int chunk) { return q * 64 + ((chunk ^ ((0 - (q >> 2)) & 3)) << 4); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 }  // namespace
 
@@ -118,7 +88,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
   };
   const int frow = lane & 15, fgrp = lane >> 4;
   const int img = blockIdx.x;
-  const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
+  const unsigned lds0 = lds_dma_base(smem);
   const char* __restrict__ xg = (const char*)a.x + (size_t)img * NPX * a.ldx * 2;
   char* __restrict__ yg = (char*)a.y + (size_t)img * NPX * a.ldy * 2;
 
@@ -208,7 +178,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
 #pragma unroll
           for (int j = 0; j < 3; ++j)
 #pragma unroll
-            for (int i = 0; i < NT; ++i) acc[j][i] = Mma<T>::run(wf[c][j], xf[c][i], acc[j][i]);
+            for (int i = 0; i < NT; ++i) mma_chunk<T>(acc[j][i], wf[c][j], xf[c][i]);
           __builtin_amdgcn_sched_barrier(0);
         };
         fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -243,7 +213,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
           if (p < ROWS) {
 #pragma unroll
             for (int j = 2; j < 6; ++j)
-              *reinterpret_cast<uint2*>(smem + ((j >> 1) - 1) * IMG_BYTES + img_chunk(p, 2 * (j & 1) + (fgrp >> 1)) + (fgrp & 1) * 8) = qa[i][j];
+              *reinterpret_cast<uint2*>(smem + ((j >> 1) - 1) * IMG_BYTES + row64_chunk(p, 2 * (j & 1) + (fgrp >> 1)) + (fgrp & 1) * 8) = qa[i][j];
           }
         }
       stamp(4);
@@ -279,7 +249,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
           {
             const int q = 16 * (wave + 8 * i) + frow + dy * IMW + dx;
             const bool ok = (unsigned)(py[i] + dy) < (unsigned)IMW && (unsigned)(px[i] + dx) < (unsigned)IMW;
-            xf[i] = *reinterpret_cast<const uint4*>(smem + src + (ok ? img_chunk(q, fgrp) : ZROW * 64));
+            xf[i] = *reinterpret_cast<const uint4*>(smem + src + (ok ? row64_chunk(q, fgrp) : ZROW * 64));
           }
 #pragma unroll
         for (int j = 0; j < 2; ++j) wf[j] = *reinterpret_cast<const uint4*>(smem + wb + (tap * 2 + j) * 1024 + lane * 16);
@@ -287,7 +257,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int i = 0; i < NT; ++i)
-            acc[j][i] = Mma<T>::run(wf[j], xf[i], acc[j][i]);
+            mma_chunk<T>(acc[j][i], wf[j], xf[i]);
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i)
@@ -307,7 +277,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
             if (p < ROWS) {
 #pragma unroll
               for (int j = 0; j < 2; ++j)
-                *reinterpret_cast<uint2*>(smem + img_chunk(p, 2 * j + (fgrp >> 1)) + (fgrp & 1) * 8) = q[j];
+                *reinterpret_cast<uint2*>(smem + row64_chunk(p, 2 * j + (fgrp >> 1)) + (fgrp & 1) * 8) = q[j];
             }
           } else {
             cf[ph == 0 ? 1 : 2][i] = quads_to_frag(q[0], q[1]);
@@ -341,7 +311,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
         for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
           for (int i = 0; i < NT; ++i)
-            acc[jj][i] = Mma<T>::run(wf[jj], cf[ks][i], acc[jj][i]);
+            mma_chunk<T>(acc[jj][i], wf[jj], cf[ks][i]);
       }
 #pragma unroll
       for (int i = 0; i < NT; ++i)
@@ -404,7 +374,7 @@ __device__ __forceinline__ void block35_stack_body(const Block35StackArgs& a, ch
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int i = 0; i < NT; ++i) acc[j][i] = Mma<T>::run(wf[c][j], xf[c][i], acc[j][i]);
+          for (int i = 0; i < NT; ++i) mma_chunk<T>(acc[j][i], wf[c][j], xf[c][i]);
         __builtin_amdgcn_sched_barrier(0);
       };
       fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -503,7 +473,7 @@ __global__ void block35_tail_repack_kernel(const char* __restrict__ w, int kpad,
     if (lane * 4 < 192) v = reinterpret_cast<const uint4*>(bias)[lane];
   } else {
     const int ks = f / 12, j = f % 12;
-    v = *reinterpret_cast<const uint4*>(w + ((size_t)(16 * j + (lane & 15)) * kpad + 32 * ks + 8 * (lane >> 4)) * 2);
+    v = GatherA16::load(w, kpad, 16 * j, 32 * ks, lane, 0);
   }
   out[(size_t)f * 64 + lane] = v;
 }
