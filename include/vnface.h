@@ -690,6 +690,21 @@ int64_t vnf_gallery_search_workspace_bytes(int F, int k, int64_t G, int64_t chun
  * no-op.  VNF_E_CAPACITY: workspace_bytes below vnf_gallery_search_workspace_bytes of the same arguments. */
 int vnf_gallery_search(vnf_handle gallery, const float* q_dev, int F, int k, int32_t* idx_out, int32_t* label_out,
                        float* score_out, int64_t chunk_rows, void* workspace, int64_t workspace_bytes, void* stream);
+/* Gallery calibration: the label-aware search.  q_dev (F,dim) fp32 probes as for vnf_gallery_search, qlabels_dev (F)
+ * int32 their known labels, exclude_dev (F) int32 or NULL.  Per probe f, idx_out / label_out / score_out (F,2) receive
+ *   column 0, the mate:     the best row g with labels[g] == qlabels[f] and g != exclude[f];
+ *   column 1, the non-mate: the best row g with labels[g] != qlabels[f] (exclude plays no part);
+ * "best" under vnf_gallery_search's total order, an absent candidate being index -1, label -1, score -inf.  exclude ==
+ * NULL and exclude[f] == -1 exclude nothing (a gallery calibrated against itself passes each probe's own row); a probe
+ * label that no row carries is legal and has no mate.  The scores come from the code vnf_gallery_search runs: the bits
+ * of a (probe, row) score are the same in both.  Stage one keeps two keys per lane in registers (no LDS, no atomics) and
+ * writes (chunk, 2F, 1) partials; stage two is the search's merge.  F == 0: no-op.  Errors as vnf_gallery_search:
+ * VNF_E_INVALID for a null pointer, a q_dev not 16-byte or a workspace not 8-byte aligned; VNF_E_CAPACITY for
+ * workspace_bytes below vnf_gallery_mated_search_workspace_bytes of the same arguments. */
+int64_t vnf_gallery_mated_search_workspace_bytes(int F, int64_t G, int64_t chunk_rows);
+int vnf_gallery_mated_search(vnf_handle gallery, const float* q_dev, const int32_t* qlabels_dev, const int32_t* exclude_dev, int F,
+                             int32_t* idx_out, int32_t* label_out, float* score_out, int64_t chunk_rows, void* workspace,
+                             int64_t workspace_bytes, void* stream);
 
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile

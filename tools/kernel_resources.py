@@ -29,7 +29,8 @@ def main():
         if flt and flt not in d:
             continue
         v = rec[n]
-        print("%-110s vgpr %3d agpr %3d scratch %4d occ %d" % (d[:110], v.get("VGPRs", -1), v.get("AGPRs", -1), v.get("ScratchSize", -1), v.get("Occupancy", -1)))
+        print("%-110s vgpr %3d agpr %3d scratch %4d lds %5d occ %d" % (d[:110], v.get("VGPRs", -1), v.get("AGPRs", -1), v.get("ScratchSize", -1),
+                                                                        v.get("LDS Size", -1), v.get("Occupancy", -1)))
 
 
 if __name__ == "__main__":

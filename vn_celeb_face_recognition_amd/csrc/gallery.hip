@@ -24,51 +24,14 @@
 // group) pairs, query group fastest: with 64 queries or fewer each chunk is read by one workgroup.
 // Stage two (gallery_merge_kernel): a workgroup per query takes, k times, the largest key below the one it took last.
 // No atomics; every loop is bounded by k, dim / 16 or the number of chunks.
+// The handle, the key, the query-fragment load and the 32-row MFMA tile live in gallery_core.h, shared with the label-aware
+// search of gallery_mated.hip (f-16), which also launches this file's merge kernel (gallery_launch_merge).
 #include <memory>
 #include <string>
 
-#include "engine.h"
+#include "gallery_core.h"
 
 namespace vnf {
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr int GAL_MAX_KG = 32;      // dim <= 512: groups of 16 k
-constexpr int GAL_MAX_K = 16;
-constexpr float GAL_EPS = 1e-12f;   // F.normalize's eps
-constexpr int64_t GAL_MAX_ROWS = 0x7FFFFFFF;
-
-struct Gallery : HandleBase {
-  static constexpr HandleKind KIND = HandleKind::Gallery;
-  Gallery() : HandleBase(KIND) {}
-  int dim = 0;
-  int64_t rows = 0, cap = 0;
-  float* mat = nullptr;        // (cap, dim), rows [0, rows) are unit vectors
-  int32_t* labels = nullptr;   // (cap)
-  ~Gallery() override {
-    (void)hipFree(mat);
-    (void)hipFree(labels);
-  }
-};
-
-// ||x||^2 of the row a group of four lanes (lane & 15 equal, lane >> 4 = 0..3) holds: `part` is the lane's own sum, taken
-// over its elements k = 16 kg + 4 (lane >> 4) + j in ascending (kg, j) as s = s + x * x from 0; the four are combined as
-// (p0 + p1) + (p2 + p3).  Every lane of the group gets the same bits.
-static __device__ __forceinline__ float sum_of_squares(float part) {
-  part = part + __shfl_xor(part, 16);
-  return part + __shfl_xor(part, 32);
-}
-
-static __device__ __forceinline__ uint64_t gallery_key(float s, uint32_t row) {
-  const uint32_t u = __float_as_uint(s == 0.f ? 0.f : s);   // -0 ties with +0
-  const uint32_t m = (s != s) ? 1u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-  return ((uint64_t)m << 32) | (uint64_t)(0xFFFFFFFFu - row);
-}
-
-static __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int mask) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, mask), hi = __shfl_xor((uint32_t)(v >> 32), mask);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // rows [0, n) of x (n, dim) -> out, each divided by max(its norm, eps).  A wave per 16 rows.
 __global__ void __launch_bounds__(256) gallery_normalize_kernel(const float* __restrict__ x, int64_t n, int dim, float* __restrict__ out) {
@@ -147,26 +110,8 @@ __global__ void __launch_bounds__(256) gallery_search_kernel(const float* __rest
   const int qrow = qg * 16 + c;
   const bool qok = qrow < F;
 
-  // the wave's 16 queries, normalised, as B fragments
-  f32x4_t qf[KG];
-  {
-    const float* qp = q + (size_t)(qok ? qrow : 0) * dim + 4 * g;
-    float ss = 0.f;
-#pragma unroll
-    for (int kg = 0; kg < KG; ++kg) {
-      f32x4_t v = {0.f, 0.f, 0.f, 0.f};
-      if (kg < kgs) v = *reinterpret_cast<const f32x4_t*>(qp + kg * 16);
-      if (!qok) v = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      qf[kg] = v;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ss = ss + v[j] * v[j];   // + 0 past dim: the bits do not see KG
-    }
-    const float d = fmaxf(sqrtf(sum_of_squares(ss)), GAL_EPS);
-#pragma unroll
-    for (int kg = 0; kg < KG; ++kg)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) qf[kg][j] = qf[kg][j] / d;
-  }
+  f32x4_t qf[KG];   // the wave's 16 queries, normalised, as B fragments
+  gallery_load_queries<KG, EXACT>(q, qrow, qok, dim, g, kgs, qf);
 
   for (int j = 0; j < k; ++j) GAL_L(j) = 0;
   uint64_t thr = 0;   // the lane's k-th best key so far
@@ -175,23 +120,8 @@ __global__ void __launch_bounds__(256) gallery_search_kernel(const float* __rest
   const int64_t r_begin = chunk * chunk_rows;
   const int64_t r_end = (r_begin + chunk_rows < G) ? r_begin + chunk_rows : G;
   for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
-    // A fragments: lane (c, g) reads row r0 + c (and r0 + 16 + c); a row past the chunk reads the chunk's first instead
-    const int64_t ra = r0 + c, rb = r0 + 16 + c;
-    const float* pa = gal + (size_t)(ra < r_end ? ra : r_begin) * dim + 4 * g;
-    const float* pb = gal + (size_t)(rb < r_end ? rb : r_begin) * dim + 4 * g;
-    f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kg = 0; kg < KG; ++kg) {
-      if (EXACT || kg < kgs) {   // wave-uniform
-        const f32x4_t a = *reinterpret_cast<const f32x4_t*>(pa + kg * 16);
-        const f32x4_t b = *reinterpret_cast<const f32x4_t*>(pb + kg * 16);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], qf[kg][j], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(b[j], qf[kg][j], acc1, 0, 0, 0);
-        }
-      }
-    }
+    f32x4_t acc0, acc1;
+    gallery_tile<KG, EXACT>(gal, r0, r_begin, r_end, dim, c, g, kgs, qf, acc0, acc1);
     // D[row = 4 g + r][col = c]: this lane's query against rows r0 + 4 g + r and r0 + 16 + 4 g + r
     uint64_t cand[8];
     bool any = false;
@@ -278,15 +208,10 @@ __global__ void __launch_bounds__(256) gallery_merge_kernel(const uint64_t* __re
 
 static bool gallery_dim_ok(int dim) { return dim >= 16 && dim <= 16 * GAL_MAX_KG && dim % 16 == 0; }
 
-// chunk_rows == 0: about 2048 waves in flight however many queries there are, chunks of 64 rows at least (a wave's
-// start-up -- 16 queries loaded and normalised -- costs about one step), whole steps of 32 rows.
-static int64_t gallery_chunk_rows(int F, int64_t G, int64_t chunk_rows) {
-  if (chunk_rows > 0) return chunk_rows;
-  const int64_t nqg = F > 0 ? (F + 15) / 16 : 1;
-  const int64_t target = 2048 / nqg > 0 ? 2048 / nqg : 1;
-  int64_t c = (G + target - 1) / target;
-  c = (c + 31) / 32 * 32;
-  return c < 64 ? 64 : c;
+hipError_t gallery_launch_merge(const uint64_t* partial, int64_t nchunks, int F, int k, const int32_t* labels, int32_t* idx_out,
+                                int32_t* label_out, float* score_out, hipStream_t stream) {
+  hipLaunchKernelGGL(gallery_merge_kernel, dim3(F), dim3(256), 0, stream, partial, nchunks, F, k, labels, idx_out, label_out, score_out);
+  return hipGetLastError();
 }
 
 }  // namespace vnf
@@ -429,8 +354,7 @@ extern "C" int vnf_gallery_search(vnf_handle h, const float* q_dev, int F, int k
                            nqg, nwork, partial);
       VNF_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(gallery_merge_kernel, dim3(F), dim3(256), 0, s, partial, nchunks, F, k, t->labels, idx_out, label_out, score_out);
-    VNF_HIP(hipGetLastError());
+    VNF_HIP(gallery_launch_merge(partial, nchunks, F, k, t->labels, idx_out, label_out, score_out, s));
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());

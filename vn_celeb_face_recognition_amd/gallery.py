@@ -7,7 +7,9 @@ added with .add().  It offers the call everything downstream uses,
     classify(emb, want_logp=False) -> (None, amax (F,) int32, prob (F,) fp32)
 
 with `prob` the top-1 COSINE in [-1, 1] (not a probability), so identify_person, FacePipeline, video.run_stream, the
-per-class thresholds, the tracker and the overlay work unchanged; thresholds compare cosines.
+per-class thresholds, the tracker and the overlay work unchanged; thresholds compare cosines.  Where such a threshold comes
+from: mated_search(emb, labels, exclude) gives every probe of known label its best mate and non-mate (csrc/gallery_mated.hip),
+and calibration.py / calibrate.py read the threshold for a false-accept rate off those scores.
 
 mode "all": every enrolled row is searchable.  mode "centroid": one row per enrolled class, the normalised sum of the
 class's normalised rows, in ascending label order; the running sums and counts are kept (and saved), so a loaded
@@ -217,6 +219,58 @@ class GalleryModel:
                 _lib.check(lib.vnf_gallery_search(h, ctypes.c_void_p(emb[f0:].data_ptr()), nn, k, ctypes.c_void_p(idx[f0:].data_ptr()),
                                                   ctypes.c_void_p(label[f0:].data_ptr()), ctypes.c_void_p(score[f0:].data_ptr()),
                                                   self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
+        return idx, label, score
+
+    def _probe_ints(self, values, f, what, device):
+        """(f) integers (host sequence, array or tensor) -> int32 cuda tensor; a wrong length or dtype is refused."""
+        if not isinstance(values, torch.Tensor):
+            a = np.asarray(values)
+            if a.dtype.kind not in "iu" and a.size:
+                raise ValueError("%s must be integers, got %s" % (what, a.dtype))
+            values = torch.from_numpy(a.astype(np.int64))
+        t = values
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise ValueError("%s must be integers, got %s" % (what, t.dtype))
+        if t.dim() != 1 or t.shape[0] != f:
+            raise ValueError("expected %d %s, got shape %s" % (f, what, tuple(t.shape)))
+        if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+            raise ValueError("%s must fit in int32" % what)
+        return t.to(device=device, dtype=torch.int32).contiguous()
+
+    def mated_search(self, emb, labels, exclude=None):
+        """Calibration's search (vnf_gallery_mated_search): (F,input_dim) cuda probes of known `labels` (F integers) ->
+        (idx, label, score), each (F,2): column 0 the best row of the probe's own label other than row exclude[f] (the
+        mate), column 1 the best row of any other label (the non-mate), under search()'s order; an absent one is
+        -1, -1, -inf.  exclude: None, or F row indices with -1 for "none" -- a gallery searched with its own rows passes
+        arange(G)."""
+        dev = self._dev()
+        if self.size == 0:
+            raise ValueError("the gallery is empty: enrol embeddings with .add() first")
+        if emb.device.type != "cuda":
+            raise RuntimeError("embeddings must live on the gallery's cuda device")
+        if emb.dim() != 2 or emb.shape[1] != self.input_dim:
+            raise ValueError("expected (F,%d) embeddings, got %s" % (self.input_dim, tuple(emb.shape)))
+        f = emb.shape[0]
+        lab = self._probe_ints(labels, f, "labels", emb.device)
+        exc = None if exclude is None else self._probe_ints(exclude, f, "exclude", emb.device)
+        h = self._ensure()
+        emb = emb.float().contiguous()
+        idx = torch.empty((f, 2), dtype=torch.int32, device=emb.device)
+        label = torch.empty((f, 2), dtype=torch.int32, device=emb.device)
+        score = torch.empty((f, 2), dtype=torch.float32, device=emb.device)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            for f0 in range(0, f, self.max_batch):
+                nn = min(self.max_batch, f - f0)
+                nbytes = lib.vnf_gallery_mated_search_workspace_bytes(nn, self.size, self.chunk_rows)
+                if nbytes < 0:
+                    _lib.check(int(nbytes))
+                ws = torch.empty((nbytes,), dtype=torch.uint8, device=emb.device)
+                _lib.check(lib.vnf_gallery_mated_search(h, ctypes.c_void_p(emb[f0:].data_ptr()), ctypes.c_void_p(lab[f0:].data_ptr()),
+                                                        ctypes.c_void_p(exc[f0:].data_ptr()) if exc is not None else None, nn,
+                                                        ctypes.c_void_p(idx[f0:].data_ptr()), ctypes.c_void_p(label[f0:].data_ptr()),
+                                                        ctypes.c_void_p(score[f0:].data_ptr()), self.chunk_rows,
+                                                        ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
         return idx, label, score
 
     def classify(self, emb, want_logp=False):
