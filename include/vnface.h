@@ -705,6 +705,33 @@ int64_t vnf_gallery_mated_search_workspace_bytes(int F, int64_t G, int64_t chunk
 int vnf_gallery_mated_search(vnf_handle gallery, const float* q_dev, const int32_t* qlabels_dev, const int32_t* exclude_dev, int F,
                              int32_t* idx_out, int32_t* label_out, float* score_out, int64_t chunk_rows, void* workspace,
                              int64_t workspace_bytes, void* stream);
+/* Gallery clustering: DBSCAN over the gallery's own G stored rows, by an all-pairs self-join.  The result is a function
+ * of the scores alone: neither scheduling nor chunk_rows nor the order in which edges are met changes a bit of it.
+ *   score     s(i,j) = the fp32 dot of stored rows i and j on v_mfma_f32_16x16x4_f32 in the search's k order, the rows
+ *             taken AS STORED (no second normalisation), so s(i,j) and s(j,i) have the same bits.  It is therefore NOT
+ *             bit-equal to vnf_gallery_search's score of the same pair, which normalises its query once more.
+ *   neighbour N(i) = { j != i : s(i,j) >= threshold }; a NaN score is never >= threshold.  degree_out[i] = |N(i)|.
+ *   core      degree(i) + 1 >= min_samples (a row counts itself, as in scikit-learn's DBSCAN); min_samples 1 makes every
+ *             row core, which gives plain connected components.
+ *   cluster   the connected components of the core rows under s >= threshold, numbered 0, 1, ... in ascending order of
+ *             each component's smallest row index.
+ *   border    a non-core row with a core neighbour: it joins the cluster of its BEST core neighbour under
+ *             vnf_gallery_search's total order (score descending, row index ascending).  Every other row is noise, -1.
+ *   nearest   nn_idx_out[i] / nn_score_out[i]: the best OTHER row of row i under the same order, neighbour or not
+ *             (-1, -inf when G == 1; a NaN score is returned as the canonical quiet NaN).
+ * All pointers are device pointers; cluster_out, degree_out, nn_idx_out (int32) and nn_score_out (fp32) are (G) arrays,
+ * n_clusters_out one int32.  Three stages on `stream`: degrees and nearest neighbours (the search's stream with a key
+ * and a count per lane, the search's merge with k = 1, one integer atomic add per row and chunk); links (the same pairs
+ * with the same scoring code, a lock-free union-find over the core rows that hooks the larger root under the smaller by
+ * compare-and-swap, so the final root of a component is its smallest row whatever the arrival order); numbering (a scan
+ * over the roots).  No float atomics, nothing allocated, no synchronisation.  chunk_rows as for vnf_gallery_search
+ * (0: the library's default).  G == 0: a no-op that writes *n_clusters_out = 0.  VNF_E_INVALID: not a gallery handle,
+ * a NaN threshold, min_samples < 1, a null pointer, a workspace not 16-byte aligned; VNF_E_CAPACITY: workspace_bytes
+ * below vnf_gallery_cluster_workspace_bytes of the same G and chunk_rows. */
+int64_t vnf_gallery_cluster_workspace_bytes(int64_t G, int64_t chunk_rows);
+int vnf_gallery_cluster(vnf_handle gallery, float threshold, int min_samples, int32_t* cluster_out, int32_t* degree_out,
+                        int32_t* nn_idx_out, float* nn_score_out, int32_t* n_clusters_out, int64_t chunk_rows, void* workspace,
+                        int64_t workspace_bytes, void* stream);
 
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile

@@ -135,6 +135,8 @@ SIGNATURES = {
     "vnf_gallery_search": (_I, [_P, _P, _I, _I, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     "vnf_gallery_mated_search_workspace_bytes": (ctypes.c_int64, [_I, ctypes.c_int64, ctypes.c_int64]),
     "vnf_gallery_mated_search": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_cluster_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "vnf_gallery_cluster": (_I, [_P, ctypes.c_float, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }

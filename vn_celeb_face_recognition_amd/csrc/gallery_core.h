@@ -1,4 +1,4 @@
-// The device core the gallery kernels share (DESIGN.md 1 f-15, f-16): the handle, the 64-bit candidate key, the lane layout
+// The device core the gallery kernels share (DESIGN.md 1 f-15, f-16, f-17): the handle, the 64-bit candidate key, the lane layout
 // of a sum of squares, and the two pieces that decide a score's bits -- the load and normalisation of a wave's 16 queries
 // into MFMA B fragments, and one 32-row tile of the exact-f32 MFMA stream.  gallery_search_kernel (gallery.hip) and
 // gallery_mated_kernel (gallery_mated.hip) both call them, so the score of a (query, row) pair has the same bits in
@@ -69,6 +69,22 @@ static __device__ __forceinline__ void gallery_load_queries(const float* __restr
   for (int kg = 0; kg < KG; ++kg)
 #pragma unroll
     for (int j = 0; j < 4; ++j) qf[kg][j] = qf[kg][j] / d;
+}
+
+// gallery_load_queries' sibling for a self-join (gallery_cluster.hip, f-17): 16 STORED rows of the gallery as B fragments in
+// the same lane layout, as they are -- no second normalisation, so the score of (row i, row j) is the sum of the same
+// products in the same order whichever of the two is the B fragment.
+template <int KG, bool EXACT>
+static __device__ __forceinline__ void gallery_load_rows(const float* __restrict__ gal, int64_t row, bool ok, int dim, int g, int kgs,
+                                                         f32x4_t (&qf)[KG]) {
+  const float* qp = gal + (size_t)(ok ? row : 0) * dim + 4 * g;
+#pragma unroll
+  for (int kg = 0; kg < KG; ++kg) {
+    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+    if (EXACT || kg < kgs) v = *reinterpret_cast<const f32x4_t*>(qp + kg * 16);
+    if (!ok) v = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    qf[kg] = v;
+  }
 }
 
 // One step of the stream: the 16 queries against gallery rows [r0, r0 + 32) of the chunk [r_begin, r_end).  Lane (c, g)

@@ -9,7 +9,9 @@ added with .add().  It offers the call everything downstream uses,
 with `prob` the top-1 COSINE in [-1, 1] (not a probability), so identify_person, FacePipeline, video.run_stream, the
 per-class thresholds, the tracker and the overlay work unchanged; thresholds compare cosines.  Where such a threshold comes
 from: mated_search(emb, labels, exclude) gives every probe of known label its best mate and non-mate (csrc/gallery_mated.hip),
-and calibration.py / calibrate.py read the threshold for a false-accept rate off those scores.
+and calibration.py / calibrate.py read the threshold for a false-accept rate off those scores.  Where the labels come
+from, or whether they are right: cluster(threshold, min_samples) groups the gallery's own rows into identities by DBSCAN
+over their cosines (csrc/gallery_cluster.hip); clustering.py / cluster.py turn that into a label file or a report.
 
 mode "all": every enrolled row is searchable.  mode "centroid": one row per enrolled class, the normalised sum of the
 class's normalised rows, in ascending label order; the running sums and counts are kept (and saved), so a loaded
@@ -272,6 +274,41 @@ class GalleryModel:
                                                         ctypes.c_void_p(score[f0:].data_ptr()), self.chunk_rows,
                                                         ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
         return idx, label, score
+
+    def cluster(self, threshold, min_samples=2):
+        """DBSCAN over the gallery's own rows (vnf_gallery_cluster, csrc/gallery_cluster.hip): rows i != j are neighbours
+        where the fp32 dot of the stored rows is >= `threshold` (a cosine), a row is core when it has min_samples - 1
+        neighbours, clusters are the connected components of the core rows, a non-core row joins its best core neighbour's
+        cluster.  -> (cluster (G) int32, -1 for noise; degree (G) int32; nn_idx (G) int32 and nn_score (G) fp32, each row's
+        best other row; n_clusters int).  The tensors stay on the device; n_clusters is the one host read."""
+        dev = self._dev()
+        if self.size == 0:
+            raise ValueError("the gallery is empty: enrol embeddings with .add() first")
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise ValueError("threshold must be a finite cosine, got %r" % (threshold,))
+        if int(min_samples) != min_samples or int(min_samples) < 1:
+            raise ValueError("min_samples must be an integer >= 1, got %r" % (min_samples,))
+        h = self._ensure()
+        g = self.size
+        cuda = torch.device("cuda:%d" % dev)
+        cluster = torch.empty((g,), dtype=torch.int32, device=cuda)
+        degree = torch.empty((g,), dtype=torch.int32, device=cuda)
+        nn_idx = torch.empty((g,), dtype=torch.int32, device=cuda)
+        nn_score = torch.empty((g,), dtype=torch.float32, device=cuda)
+        n_clusters = torch.empty((1,), dtype=torch.int32, device=cuda)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            nbytes = lib.vnf_gallery_cluster_workspace_bytes(g, self.chunk_rows)
+            if nbytes < 0:
+                _lib.check(int(nbytes))
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=cuda)
+            _lib.check(lib.vnf_gallery_cluster(h, threshold, int(min_samples), ctypes.c_void_p(cluster.data_ptr()),
+                                               ctypes.c_void_p(degree.data_ptr()), ctypes.c_void_p(nn_idx.data_ptr()),
+                                               ctypes.c_void_p(nn_score.data_ptr()), ctypes.c_void_p(n_clusters.data_ptr()),
+                                               self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
+            n = int(n_clusters.item())
+        return cluster, degree, nn_idx, nn_score, n
 
     def classify(self, emb, want_logp=False):
         """MLPModel.classify's contract for want_logp=False: (None, top-1 label (F,) int32, its cosine (F,) fp32)."""
