@@ -222,7 +222,8 @@ def test_persistent_block17_trunk_kernel_matches_the_unfused_plan_and_the_oracle
     """repeat_2 (10 x Block17, inception_resnet_v1.py:70-95) runs as ONE persistent kernel on the 16-bit paths
     (trunk17.hip; trunk17s.hip for the planar split-f16 dtype: residual trunk in fp32 registers, intermediates in LDS).  Against the fp32 oracle's stage taps it
     must be at least as close as the unfused per-convolution plan (VNF_FUSE=0), which rounds the trunk to 16 bits after
-    every block; the two plans must agree with each other to the storage precision."""
+    every block; the two plans must agree with each other to the storage precision.
+    The bit-for-bit check of these kernels, on exact-arithmetic data, is tests/test_gpu_trunk17_exact.py."""
     from vn_celeb_face_recognition_amd.models import InceptionResnetV1
     from oracle import irv1
     x = seeded_normal((5, 3, 160, 160), 31)
