@@ -17,7 +17,10 @@ scripts run (scripts/celeb_stat_*.sh).  -sfr writes the annotated PNGs (boxes, n
 -ov out.avi writes the annotated video of the sampled frames from the device (jpeg_encode.VideoEncoder: boxes, names
 and emotion lines drawn in HBM, --ov_quality, --ov_subsampling; --ov_entropy device runs the Huffman pass of the
 encoder in HIP too, the same files, default host) at as many frames per second as -fidx keeps, so the
-video lasts as long as the input.  Input: a directory of frames or a .npy array of (T,H,W,3) RGB frames with -fps, or
+video lasts as long as the input.  --track_faces (--track_threshold, --track_iou, --track_gap; this build's, the
+reference names every face on its own) links the faces of consecutive processed frames into tracks on the GPU after the
+stream (tracking.py, csrc/gallery_tracks.hip) and writes every face under its track's name, with a last tracker column
+Track; it is refused together with -ov and -sfr, which draw the names while the frames pass.  Input: a directory of frames or a .npy array of (T,H,W,3) RGB frames with -fps, or
 a Motion-JPEG .avi (OpenCV / pafy are not installed: no other container decode, no YouTube); seq_fd_vs_aln (outside
 the hot path) is refused."""
 import os
@@ -63,12 +66,18 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
         os.makedirs(args.output_frame, exist_ok=True)
         with open(args.output_tracker, 'w') as f:
             f.write('')
-        append_log_to_file(args.output_tracker, tracker_header(args.track_bbox, k > 0))
+        append_log_to_file(args.output_tracker, tracker_header(args.track_bbox, k > 0, args.track_faces))
     start_time = time.time()
+    frames_seen, faces_seen = {}, []           # --track_faces, rank 0: what every row was made of; every face of the stream
 
-    def row(tm, number, names, boxes, shape, emotions=None):
+    def row(tm, number, names, boxes, shape, emotions=None, tracks=None):
+        if args.track_faces and tracks is None:
+            frames_seen[number] = (tm, boxes, shape, emotions)
         return tracker_row(tm, names, number, boxes, shape[:2], args.track_bbox,
-                           emotion_tags(idx2etag, emotions[0]) if emotions is not None else None)
+                           emotion_tags(idx2etag, emotions[0]) if emotions is not None else None, tracks)
+
+    def face(number, tm, box, emb):
+        faces_seen.append((number, np.array(emb, np.float32), np.array(box, np.float32)))
 
     def on_frame(frame, number, names, boxes, emotions=None):
         img = draw_boxes_on_image(frame, boxes, names) if names else frame
@@ -83,19 +92,47 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
                                  on_frame=on_frame if args.save_frame_recognized else None, log=log,
                                  decode="host" if args.host_decode else "device", encoder=encoder, emotions=k, row=row,
-                                 decode_entropy=args.decode_entropy)
+                                 decode_entropy=args.decode_entropy, faces=face if args.track_faces else None)
     if world > 1:
         tot = torch.tensor([processed], device=device if device is not None else 'cuda')
         dist.all_reduce(tot)
         processed = int(tot.item())
     if rank != 0:
         return None
+    if args.track_faces:
+        rows = track_rows(args, pipe, device, frames_seen, faces_seen, row)
     with open(args.output_tracker, 'a') as f:
         f.write(''.join(rows[n] for n in sorted(rows)))
     processed_time = time.time() - start_time
     print('Saved tracker file in {} ...'.format(args.output_tracker))
     print('FPS for recognition face: {}'.format(int(processed / max(processed_time, 1e-9))))
     return read_tracker_csv(args.output_tracker)
+
+
+def track_rows(args, pipe, device, frames_seen, faces_seen, row):
+    """--track_faces, after the stream: the faces in frame order (the order of their tracker row within a frame), linked
+    into tracks and named per track (tracking.py) -> the tracker rows again, every face under its track's name, with the
+    track ids of the row's faces for a last column."""
+    from vn_celeb_face_recognition_amd.tracking import link_tracks, name_tracks, pool_tracks
+    numbers = sorted(frames_seen)
+    ordinal = {num: p for p, num in enumerate(numbers)}      # a frame's position among the processed frames
+    order = sorted(range(len(faces_seen)), key=lambda i: faces_seen[i][0])   # stable: the stream's order inside a frame
+    emb = np.stack([faces_seen[i][1] for i in order]) if order else np.zeros((0, 512), np.float32)
+    boxes = np.stack([faces_seen[i][2] for i in order]) if order else np.zeros((0, 4), np.float32)
+    frame_ord = np.array([ordinal[faces_seen[i][0]] for i in order], np.int64)
+    res = link_tracks(emb, frame_ord, boxes, threshold=args.track_threshold, min_iou=args.track_iou, max_gap=args.track_gap,
+                      device=device)
+    names = name_tracks(pool_tracks(emb, res), pipe.classifier, pipe.label2name, pipe.threshold)
+    print('Linked {} faces into {} tracks'.format(len(order), res.n_tracks))
+    rows, o = {}, 0
+    for num in numbers:
+        tm, f_boxes, shape, emotions = frames_seen[num]
+        ids = res.track[o:o + len(f_boxes)].tolist()
+        assert (frame_ord[o:o + len(f_boxes)] == ordinal[num]).all()
+        o += len(f_boxes)
+        kw = {} if emotions is None else {"emotions": emotions}
+        rows[num] = row(tm, num, [names[t] for t in ids], f_boxes, shape, tracks=ids, **kw)
+    return rows
 
 
 def make_parser():
@@ -130,6 +167,18 @@ def make_parser():
                    help='chroma subsampling of the frames of -ov')
     p.add_argument('--ov_entropy', default='host', choices=['host', 'device'],
                    help='where the Huffman pass of the frames of -ov runs: on host threads, or on the GPU (the same files)')
+    p.add_argument('--track_faces', action='store_true',
+                   help='link the faces of consecutive processed frames into tracks on the GPU and name every face by its '
+                        'track: one name per track, decided from all of its frames; adds the column Track to the tracker')
+    p.add_argument('--track_threshold', default=None, type=float,
+                   help='cosine two faces of one track must reach: required with --track_faces, no default -- the threshold '
+                        'calibrate.py prints for the encoder in use')
+    p.add_argument('--track_iou', default=0.0, type=float,
+                   help='with --track_faces: the IoU the boxes of two linked faces must reach; 0 (default) ignores the boxes. '
+                        'The default is a convention, not a measurement')
+    p.add_argument('--track_gap', default=1, type=int,
+                   help='with --track_faces: how many processed frames a link may span (1..255); 1 (default) links adjacent '
+                        'processed frames only.  The default is a convention, not a measurement')
     p.set_defaults(recog_threshold=0.7)          # celeb_statistic.py:349 (demo_image's default is 0)
     return p
 
@@ -148,6 +197,14 @@ if __name__ == '__main__':
         raise SystemExit("--ov_quality must be in 1..100")
     if args.recog_emotion and not 1 <= args.topk_emotions <= 16:
         raise SystemExit("--topk_emotions must be in 1..16 (the width of the device top-k and of the stream's exchange)")
+    if args.track_faces:
+        if args.track_threshold is None or args.track_threshold != args.track_threshold:
+            p.error("--track_faces needs --track_threshold (a cosine: the value calibrate.py prints)")
+        if not 1 <= args.track_gap <= 255:
+            p.error("--track_gap must be in 1..255")
+        if args.output_video or args.save_frame_recognized:
+            raise SystemExit("--track_faces knows the names only after the stream: it cannot be combined with -ov or -sfr, which "
+                             "draw them while the frames pass (a second pass over the frames is not implemented)")
     frame_idxes = list(args.frame_idxes)
     rank, world, local = vdist.init_from_env()
     # one decision for every rank: the tracker file appears while rank 0 works, so a late rank must not look for it

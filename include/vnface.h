@@ -732,6 +732,47 @@ int64_t vnf_gallery_cluster_workspace_bytes(int64_t G, int64_t chunk_rows);
 int vnf_gallery_cluster(vnf_handle gallery, float threshold, int min_samples, int32_t* cluster_out, int32_t* degree_out,
                         int32_t* nn_idx_out, float* nn_score_out, int32_t* n_clusters_out, int64_t chunk_rows, void* workspace,
                         int64_t workspace_bytes, void* stream);
+/* Face tracks: the G faces of a video, stored in a gallery IN FRAME ORDER, linked across frames.  A row's int32 label is
+ * its frame ordinal f(i) -- its position among the processed frames --, non-decreasing in i; frame_first_dev is a device
+ * int32 array of n_frames + 1 entries, the rows of frame p being [frame_first[p], frame_first[p + 1]), ascending from 0 to G;
+ * boxes_dev is device (G,4) fp32 x1,y1,x2,y2, 16-byte aligned, or NULL.  The result is a function of these inputs alone:
+ * neither scheduling nor the number of waves nor the order in which pairs are met changes a bit of it.
+ *   score      s(i,j): vnf_gallery_cluster's, the fp32 dot of the two STORED rows, the same bits from either side.
+ *   candidate  j is a forward candidate of i iff 0 < f(j) - f(i) <= max_gap (with j > i, which the order of the rows
+ *              implies), s(i,j) >= threshold (a NaN score never), and, with min_iou > 0,  inter >= min_iou * union  where
+ *              iw = max(0, min(x2) - max(x1)), ih likewise, inter = iw * ih, area = (x2 - x1) * (y2 - y1),
+ *              union = area_i + area_j - inter: fp32, in this operation order, nothing contracted.  With min_iou <= 0 the
+ *              boxes are not read.  Two faces of one frame are never candidates of each other.  i is a backward
+ *              candidate of j exactly where j is a forward candidate of i.
+ *   best       next(i): the best forward candidate of i under the total order (frame distance ascending, then score
+ *              descending, then row index ascending -- the last two vnf_gallery_search's order); pred(j): the best backward
+ *              candidate of j likewise.
+ *   link       i -> j iff next(i) == j and pred(j) == i.  A row has at most one successor and one predecessor, so the
+ *              links form chains through strictly increasing frames: the tracks.
+ * Outputs, device arrays of G entries: prev_out / next_out (int32) the linked rows, -1 without one; link_score_out
+ * (fp32) the score of the link to prev, -inf at the head of a track (-0 is returned as +0); track_out (int32) the
+ * track of each row, tracks numbered 0, 1, ... in ascending order of each chain's first row; n_tracks_out one int32.
+ * The work follows the window, not G^2: a wave takes 16 rows and streams the one contiguous row range frame_first gives
+ * for the frames within max_gap of them, 32 rows a step, keeping a best forward and a best backward candidate per
+ * lane; then mutual bests, then chains to tracks: ceil(log2(n_frames)) rounds of pointer jumping, and a scan over the
+ * heads as vnf_gallery_cluster numbers its roots.
+ * No float atomics, nothing allocated, no synchronisation.  G == 0: a no-op that writes *n_tracks_out = 0 and looks at
+ * no other pointer.  VNF_E_INVALID: not a gallery handle, a NaN threshold or min_iou, max_gap outside 1..255,
+ * n_frames < 0, a null pointer (boxes_dev only with min_iou > 0), a workspace or boxes_dev not 16-byte aligned;
+ * VNF_E_CAPACITY: workspace_bytes below vnf_gallery_tracks_workspace_bytes(G).  frame_first and the labels live in
+ * device memory and are the caller's to check: tables that break the rules above give tracks that mean nothing, but no
+ * row outside [0, G) is read or written and every loop ends (the rounds are counted from n_frames). */
+int64_t vnf_gallery_tracks_workspace_bytes(int64_t G);
+int vnf_gallery_tracks(vnf_handle gallery, const int32_t* frame_first_dev, int n_frames, const float* boxes_dev, float threshold,
+                       float min_iou, int max_gap, int32_t* prev_out, int32_t* next_out, float* link_score_out, int32_t* track_out,
+                       int32_t* n_tracks_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* One pooled row per track: sums_out device (n_tracks,dim) fp32, 16-byte aligned, row k the sum of the stored rows of
+ * track k IN ROW ORDER, s = s + x from 0 in fp32 per element (it repeats bitwise and equals a sequential fp32 sum on the
+ * host); counts_out device (n_tracks) int32 their number.  prev_dev, next_dev, track_dev: vnf_gallery_tracks' outputs
+ * for this gallery.  A wave per track starts at the track's head (the row without a prev) and walks next while it leads
+ * to a later row of the gallery; a track number no head carries gets zeros and 0.  n_tracks == 0: no-op. */
+int vnf_gallery_track_sums(vnf_handle gallery, const int32_t* prev_dev, const int32_t* next_dev, const int32_t* track_dev, int n_tracks,
+                           float* sums_out, int32_t* counts_out, void* stream);
 
 /* One-convolution probe (debug / test entry) -------------------------------------------------- */
 /* Every convolution of every plan goes through one launcher that picks one of vnf_conv_probe_cfgs() tile

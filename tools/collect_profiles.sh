@@ -55,6 +55,7 @@ python tools/jpeg_huff_decode_time.py --out $OUT/jpeg_huff_decode_time.txt > $OU
 python tools/gallery_time.py --out $OUT/gallery_time.txt > $OUT/gallery_time.log 2>&1 || exit 1
 python tools/calibrate_time.py --out $OUT/calibrate_time.txt > $OUT/calibrate_time.log 2>&1 || exit 1   # the mated search beside search(k=1)
 python tools/cluster_time.py --out $OUT/cluster_time.txt > $OUT/cluster_time.log 2>&1 || exit 1   # the clustering self-join, each size in a child under its own time limit
+python tools/tracks_time.py --out $OUT/tracks_time.txt > $OUT/tracks_time.log 2>&1 || exit 1   # face tracks: the temporal join and the pooled rows
 # 4. kernel-trace summary of the same default bench command (embed legs + pipeline leg)
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/kt_bench -o b --output-format csv -- python3 $ROOT/bench.py --full --no-cpu-baseline --legs "" > $OUT/kt_bench.log 2>&1 || exit 1

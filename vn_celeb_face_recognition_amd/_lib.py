@@ -137,6 +137,9 @@ SIGNATURES = {
     "vnf_gallery_mated_search": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     "vnf_gallery_cluster_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
     "vnf_gallery_cluster": (_I, [_P, ctypes.c_float, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_tracks_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "vnf_gallery_tracks": (_I, [_P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "vnf_gallery_track_sums": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "vnf_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _P, ctypes.c_int64, _P]),
     "vnf_overlay_draw_text": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
 }

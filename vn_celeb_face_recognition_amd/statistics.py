@@ -114,17 +114,20 @@ def build_thresholds(local_thresholds, num_classes, recog_threshold, read_json=N
     return {str(i): recog_threshold for i in range(num_classes)}
 
 
-def tracker_header(track_bbox, recog_emotion=False):
+def tracker_header(track_bbox, recog_emotion=False, track_faces=False):
     cols = ['Time', 'Names', 'Frame_idx']
     if track_bbox:
         cols.append('Bboxes')
     if recog_emotion:
         cols.append('Emotion')
+    if track_faces:
+        cols.append('Track')
     return cols
 
 
-def tracker_row(time_in_video, names, frame_count, bboxes=None, frame_hw=None, track_bbox=False, emotions=None):
-    """One tracker.csv line (celeb_statistic.py:253-276): boxes scaled to [0,1] by (w,h,w,h)."""
+def tracker_row(time_in_video, names, frame_count, bboxes=None, frame_hw=None, track_bbox=False, emotions=None, tracks=None):
+    """One tracker.csv line (celeb_statistic.py:253-276): boxes scaled to [0,1] by (w,h,w,h).  tracks (--track_faces, this
+    build's): the track id of each face of the row, the last column."""
     row = [str(time_in_video), '"' + str(list(names)) + '"', str(frame_count)]
     if track_bbox and bboxes is not None:
         h, w = frame_hw
@@ -132,6 +135,8 @@ def tracker_row(time_in_video, names, frame_count, bboxes=None, frame_hw=None, t
         row.append('"' + str(scaled) + '"')
     if emotions is not None:
         row.append('"' + str(emotions) + '"')
+    if tracks is not None:
+        row.append('"' + str([int(k) for k in tracks]) + '"')
     return ','.join(row) + '\n'
 
 

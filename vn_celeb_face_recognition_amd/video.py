@@ -133,7 +133,7 @@ class FrameSource:
 
 
 def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
-               decode="device", encoder=None, emotions=0, row=None, decode_entropy="host"):
+               decode="device", encoder=None, emotions=0, row=None, decode_entropy="host", faces=None):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
 
     pipe: FacePipeline-like -- .submit(frames_dev, classify=False[, ready=event]) -> ticket with .result() ->
@@ -163,6 +163,11 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     rank (a CLI flag): the block's width follows from it alone.  0 (default): nothing of this, tickets need no emo_*.
     row: the tracker line's formatter, (time, frame_number, names, boxes, frame_shape[, emotions=...]) -> str; default
     `tracker_row`.
+    faces: None (default: nothing below happens), or a callable that rank 0 hands every face of every round, in the order
+    the tracker rows list them: faces(frame_number, time, box (4,) fp32, embedding (512,) host fp32) -- the gathered
+    embeddings as they were exchanged, for rank 0's own frames and for the other ranks' alike (tracking.py links them
+    into tracks after the stream).  It costs one more pinned read-back per round, of gathered[:, :512], on rank 0 only;
+    the collectives and the rows are the same with and without it.
     Returns (rows: {frame_number: csv row}, complete on rank 0; frames processed by this rank)."""
     k_emo = int(emotions)
     if not 0 <= k_emo <= 16:
@@ -185,6 +190,7 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
     cap = int(cap) if cap else max(256, 16 * int(n_frames))
     WIDTH = 517 + 2 * k_emo                 # 512 embedding + 4 box + 1 frame slot [+ k emotion indices + k probabilities]
     classify_here = rank == 0 or on_frame is not None or encoder is not None
+    sink = faces if rank == 0 else None
     rows, inflight, pending = {}, [], []    # inflight: (round, ticket or None, frames, info); pending: issued exchanges
     state = {"processed": 0, "shape": None}
 
@@ -258,6 +264,8 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             amax, prob = classify(gathered)
             if classify_here:
                 rec["extra"], rec["amax"], rec["prob"] = to_host(gathered[:, 512:].contiguous()), to_host(amax), to_host(prob)
+            if sink is not None:
+                rec["emb"] = to_host(gathered[:, :512].contiguous())
             if payload is not None and comm is not None:
                 payload.record_stream(comm)
             rec["event"] = comm.record_event() if comm is not None else None
@@ -278,6 +286,9 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
             parts = [[ex[r * stride: r * stride + min(c, cap if world > 1 else c)],
                       am[r * stride: r * stride + min(c, cap if world > 1 else c)],
                       pr[r * stride: r * stride + min(c, cap if world > 1 else c)]] for r, c in enumerate(counts)]
+            if sink is not None:
+                em = rec["emb"].numpy()
+                embs = [em[r * stride: r * stride + min(c, cap if world > 1 else c)] for r, c in enumerate(counts)]
         if world > 1 and max(counts) > cap:
             # rare: some rank's batch held more faces than the fixed block; every rank sees the same headers, so every
             # rank issues this same exactly-sized follow-up here
@@ -296,6 +307,9 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
                         parts[r] = [np.concatenate([parts[r][0], ex2[r * m: r * m + k]]),
                                     np.concatenate([parts[r][1], am2[r * m: r * m + k]]),
                                     np.concatenate([parts[r][2], pr2[r * m: r * m + k]])]
+                    if sink is not None:
+                        em2 = out[:, :512].cpu().numpy()
+                        embs = [np.concatenate([embs[r], em2[r * m: r * m + max(0, c - cap)]]) for r, c in enumerate(counts)]
                 elif comm is not None:
                     comm.synchronize()
         if not classify_here:
@@ -322,6 +336,9 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
                         on_frame(q[i], num, f_names, f_boxes, **f_emo)
                     if rank == 0:
                         rows[num] = row(tm, num, f_names, f_boxes, q[i].shape, **f_emo)
+                    if sink is not None:
+                        for j in sel:
+                            sink(num, tm, bx[j], embs[r][j])
                 if encoder is not None:
                     frames_dev, slot, after = rec.pop("video")
                     done = encoder.write_batch(frames_dev, [num for _, num in inf], b_boxes, b_names, after=after,
@@ -333,6 +350,9 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
                     num = number_of((rnd * world + r) * n_frames + int(i))
                     rows[num] = row(num / source.fps, num, [nm[j] for j in sel], [bx[j] for j in sel], state["shape"],
                                     **emo(ex, sel))
+                    if sink is not None:
+                        for j in sel:
+                            sink(num, num / source.fps, bx[j], embs[r][j])
 
     def retire(item):
         pending.append(issue(item))
