@@ -208,3 +208,24 @@ def test_oracle_tie_order_and_padding():
     assert worst == 0.0
     with pytest.raises(AssertionError):
         go.check_ranks(np.array([[1, 2, 3]]), np.array([[1.0, 1.0, 1.0]]), go.scores(np.array([[3.0, 0.0]]), g), 3, go.tol(2))
+
+
+@pytest.mark.parametrize("chunk_rows", [0, 32])
+@pytest.mark.parametrize("G", [0, 1, 3, 4, 5, 70, 100000])
+def test_cluster_and_tracks_workspaces_keep_their_layout(G, chunk_rows):
+    """The two carved workspaces (csrc/gallery_cluster.hip, gallery_tracks.hip, both on gallery_core.h's carver) have the
+    totals of the layouts they were first written with: (nchunks, G) 8-byte keys then seven arrays of G 32-bit entries, and
+    five such arrays, each section rounded up to 16 bytes, an array to a multiple of 4 entries; 16 bytes for an empty one."""
+    from vn_celeb_face_recognition_amd import _lib
+    lib = _lib.load()
+
+    def align16(n):
+        return (n + 15) // 16 * 16
+
+    cr = chunk_rows
+    if cr == 0:                                                  # the library's default: about 2048 waves, 64 rows at least
+        target = max(2048 // max((G + 15) // 16, 1), 1)
+        cr = max((-(-G // target) + 31) // 32 * 32, 64)
+    nchunks, padded = -(-G // cr), (G + 3) // 4 * 4
+    assert lib.vnf_gallery_cluster_workspace_bytes(G, chunk_rows) == max(align16(nchunks * G * 8) + 7 * align16(padded * 4), 16)
+    assert lib.vnf_gallery_tracks_workspace_bytes(G) == max(5 * align16(padded * 4), 16)

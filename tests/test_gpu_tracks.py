@@ -5,8 +5,9 @@ The scenes are random: identities as tight blobs (a unit centre plus noise), a f
 face of one identity in the larger frames so that candidates compete, boxes that follow the identity with a jitter and
 now and then jump.  prev, next, track and n_tracks are compared EXACTLY, which only means something when no decision sits
 within rounding of a boundary: every comparison first asserts on the CPU that the oracle's three margins exceed
-4 * gallery_oracle.tol(dim); the seeds were chosen so that they do.  link_score is held to tol(dim), the sums to the bits
-of a sequential fp32 sum of the stored rows.  Every raw call runs with guard bytes around its outputs and its workspace."""
+4 * gallery_oracle.tol(dim); the seeds were chosen so that they do.  link_score is held to tol(dim) and, on a scene of
+far-apart pairs, to the bits of vnf_gallery_cluster's score of the same pair; the sums to the bits of a sequential fp32 sum
+of the stored rows.  Every raw call runs with guard bytes around its outputs and its workspace."""
 import ctypes
 import functools
 
@@ -17,6 +18,7 @@ import torch
 import gallery_oracle as go
 import track_oracle as to
 from test_gpu_gallery import DEV, Guarded, RawGallery
+from test_gpu_gallery_cluster import cluster
 from vn_celeb_face_recognition_amd import _lib, tracking
 
 pytestmark = pytest.mark.gpu
@@ -288,3 +290,35 @@ def test_error_codes():
     torch.cuda.synchronize()
     assert int(nt.item()) == 0
     empty.close(); rg.close()
+
+
+@pytest.mark.parametrize("dim", [512, 32])
+def test_link_score_is_the_clustering_score_bit_for_bit(dim):
+    """a link's score is f-17's score of the pair, the same bits.  17 pairs of rows, pair k two noisy
+    copies of centre k of an orthonormal set, row 2k in frame 2k and row 2k + 1 in frame 2k + 1: at max_gap 1 the only
+    links are 2k -> 2k + 1, and each row's nearest other row under vnf_gallery_cluster is its mate."""
+    rng = np.random.default_rng(7)
+    centres = np.linalg.qr(rng.standard_normal((dim, dim)))[0][:17]
+    x = _unit(np.repeat(centres, 2, axis=0) + 0.15 * _unit(rng.standard_normal((34, dim))))
+    x = (x * rng.uniform(0.1, 30.0, (34, 1))).astype(np.float32)
+    f = np.arange(34)
+    s = go.scores(x, x)
+    even, odd = np.arange(0, 34, 2), np.arange(1, 34, 2)
+    within = s[even, odd]
+    cross = s.copy()
+    cross[np.arange(34), np.arange(34)] = -1.0
+    cross[even, odd] = cross[odd, even] = -1.0
+    lim = 4 * go.tol(dim)
+    assert within.min() >= 0.8 and cross.max() <= 0.2, (within.min(), cross.max())
+    assert within.min() - T > lim and T - cross.max() > lim
+    rg = _gallery(x, f)
+    got = tracks(rg, f, None, T, 0.0, 1)
+    want_next, want_prev = np.full(34, -1), np.full(34, -1)
+    want_next[even], want_prev[odd] = odd, even
+    assert np.array_equal(got["next"], want_next) and np.array_equal(got["prev"], want_prev) and got["n_tracks"] == 17
+    _, _, nn_idx, nn_score, _ = cluster(rg, T, 2)
+    assert np.array_equal(nn_idx[even], odd) and np.array_equal(nn_idx[odd], even)
+    link = got["link_score"][odd].view(np.int32)
+    assert np.array_equal(link, nn_score[even].view(np.int32)) and np.array_equal(link, nn_score[odd].view(np.int32))
+    assert (np.abs(got["link_score"][odd] - within) <= go.tol(dim)).all()
+    rg.close()

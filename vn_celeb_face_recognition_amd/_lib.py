@@ -167,6 +167,15 @@ def check(rc):
         raise VnfError("libvnface error %d: %s" % (rc, load().vnf_last_error().decode("utf-8", "replace")))
 
 
+def workspace(nbytes, device):
+    """What a vnf_*_workspace_bytes call answered -> the uint8 scratch tensor on `device`; a negative answer is the
+    library's error code and raises it."""
+    import torch
+    if nbytes < 0:
+        check(int(nbytes))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
 def make_descs(state_dict):
     """state_dict (name -> torch.Tensor | ndarray) -> (TensorDesc array, keepalive list)."""
     import torch

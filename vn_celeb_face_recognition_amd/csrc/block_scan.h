@@ -1,5 +1,6 @@
-// The one-workgroup exclusive scan the device Huffman coder and decoder share (jpeg_huff_device.hip,
-// jpeg_huff_decode.hip).  Device code only.
+// The one-workgroup exclusive scan: the device Huffman coder and decoder (jpeg_huff_device.hip, jpeg_huff_decode.hip)
+// and cluster_number_kernel (gallery_cluster.hip), which numbers the clusters of f-17 and the tracks of f-18.  Device
+// code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -6,26 +6,17 @@
 //   search  score[f][g] = <q_f / max(||q_f||, 1e-12), gallery_g>; per query the k best rows under the TOTAL order
 //           (score descending, row index ascending), a NaN score below every number, an absent row below that
 //
-// The order is total, so it is one unsigned 64-bit comparison: a candidate is the key
-//     (monotone image of the score) << 32 | (0xFFFFFFFF - row)
-// where the score's image is the usual sign-flip of its bits, 1 for a NaN and 0 for "no row" (the whole key is 0 then).
-// A larger key is a better candidate, every real candidate has a key of its own, and a merge of sorted lists is exact.
+// The order is total, so it is one unsigned 64-bit comparison (gallery_key): a larger key is a better candidate, every
+// real candidate has a key of its own, and a merge of sorted lists is exact.
 //
-// Stage one (gallery_search_kernel): a wave owns 16 queries and a chunk of gallery rows.  It keeps the normalised
-// queries as MFMA B fragments in registers (dim/16 x 4 floats, 128 VGPRs at dim 512) and streams the chunk 32 rows at a
-// time: a lane reads 16 contiguous bytes of one row (k = 16 kg + 4 (lane >> 4) + j, j = 0..3) and four MFMAs consume
-// them, MFMA j taking element j of both operands -- a fixed permutation of k inside each group of 16, the same for every
-// (query, row) pair, so a score's bits depend on the two vectors alone: not on F, not on the row's place in a tile, not
-// on the chunking.  The sum of squares of a vector is formed in the same lane layout (sum_of_squares below) by the
-// search and by add.  D[row = 4 (lane >> 4) + r][col = lane & 15]: a lane ends up with one query's scores against four
-// rows of each tile.  It keeps the top-k of ITS rows in LDS (an unordered list per lane, touched by no other lane, so
-// nothing is synchronised), entered only by candidates that beat the lane's k-th key, which take that key's slot; at the
-// end of the chunk the four lanes of a query merge their lists by k rounds of a shuffled maximum.  The waves of a workgroup take consecutive (chunk, query
-// group) pairs, query group fastest: with 64 queries or fewer each chunk is read by one workgroup.
-// Stage two (gallery_merge_kernel): a workgroup per query takes, k times, the largest key below the one it took last.
+// Stage one (gallery_search_kernel) is the stream of gallery_core.h with a top-k list per lane on top: a wave owns 16
+// queries and a chunk of gallery rows, and a lane keeps the top-k of ITS rows in LDS (an unordered list per lane, touched
+// by no other lane, so nothing is synchronised), entered only by candidates that beat the lane's k-th key, which take that
+// key's slot; at the end of the chunk the four lanes of a query merge their lists by k rounds of gallery_max4.  The sum
+// of squares of a vector is formed in the same lane layout (sum_of_squares) by the search and by add.
+// Stage two (gallery_merge_kernel, which the other users of the core launch too): a workgroup per query takes, k times,
+// the largest key below the one it took last.
 // No atomics; every loop is bounded by k, dim / 16 or the number of chunks.
-// The handle, the key, the query-fragment load and the 32-row MFMA tile live in gallery_core.h, shared with the label-aware
-// search of gallery_mated.hip (f-16), which also launches this file's merge kernel (gallery_launch_merge).
 #include <memory>
 #include <string>
 
@@ -94,42 +85,36 @@ __global__ void __launch_bounds__(64) gallery_class_sums_kernel(const float* __r
       }                                                \
   } while (0)
 
-// KG groups of 16 k are held; EXACT: dim == 16 KG, otherwise the groups at and beyond dim / 16 are skipped.
 template <int KG, bool EXACT>
 __global__ void __launch_bounds__(256) gallery_search_kernel(const float* __restrict__ gal, int64_t G, int dim, const float* __restrict__ q,
                                                              int F, int k, int64_t chunk_rows, int nqg, int64_t nwork,
                                                              uint64_t* __restrict__ partial) {
   __shared__ uint64_t lists[4 * GAL_MAX_K * 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t w = (int64_t)blockIdx.x * 4 + wave;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // GAL_L's
+  GalleryLane<int> L;
+  const int64_t w = gallery_wave();
   if (w >= nwork) return;
-  const int64_t chunk = w / nqg;
-  const int qg = (int)(w % nqg);
-  const int c = lane & 15, g = lane >> 4;
-  const int kgs = EXACT ? KG : (dim >> 4);
-  const int qrow = qg * 16 + c;
-  const bool qok = qrow < F;
+  gallery_lane_chunked<KG, EXACT>(L, w, nqg, F, dim);
 
   f32x4_t qf[KG];   // the wave's 16 queries, normalised, as B fragments
-  gallery_load_queries<KG, EXACT>(q, qrow, qok, dim, g, kgs, qf);
+  gallery_load_queries<KG, EXACT>(q, L.qrow, L.qok, dim, L.g, L.kgs, qf);
 
   for (int j = 0; j < k; ++j) GAL_L(j) = 0;
   uint64_t thr = 0;   // the lane's k-th best key so far
   int minpos = 0;
 
-  const int64_t r_begin = chunk * chunk_rows;
-  const int64_t r_end = (r_begin + chunk_rows < G) ? r_begin + chunk_rows : G;
-  for (int64_t r0 = r_begin; r0 < r_end; r0 += 32) {
+  gallery_lane_rows(L, chunk_rows, G);
+  for (int64_t r0 = L.r_begin; r0 < L.r_end; r0 += 32) {
     f32x4_t acc0, acc1;
-    gallery_tile<KG, EXACT>(gal, r0, r_begin, r_end, dim, c, g, kgs, qf, acc0, acc1);
-    // D[row = 4 g + r][col = c]: this lane's query against rows r0 + 4 g + r and r0 + 16 + 4 g + r
+    gallery_tile<KG, EXACT>(gal, r0, L.r_begin, L.r_end, dim, L.c, L.g, L.kgs, qf, acc0, acc1);
     uint64_t cand[8];
     bool any = false;
+    // gallery_for_each's walk, written out (see there)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int64_t i0 = r0 + 4 * g + r, i1 = i0 + 16;
-      cand[r] = i0 < r_end ? gallery_key(acc0[r], (uint32_t)i0) : 0;
-      cand[4 + r] = i1 < r_end ? gallery_key(acc1[r], (uint32_t)i1) : 0;
+      const int64_t i0 = r0 + 4 * L.g + r, i1 = i0 + 16;
+      cand[r] = i0 < L.r_end ? gallery_key(acc0[r], (uint32_t)i0) : 0;
+      cand[4 + r] = i1 < L.r_end ? gallery_key(acc1[r], (uint32_t)i1) : 0;
       any = any || cand[r] > thr || cand[4 + r] > thr;
     }
     if (any) {
@@ -149,12 +134,8 @@ __global__ void __launch_bounds__(256) gallery_search_kernel(const float* __rest
     uint64_t m = 0;
 #pragma unroll
     for (int j = 0; j < GAL_MAX_K; ++j) m = (e[j] < prev && e[j] > m) ? e[j] : m;
-    uint64_t o = shfl_xor_u64(m, 16);
-    m = o > m ? o : m;
-    o = shfl_xor_u64(m, 32);
-    m = o > m ? o : m;
-    prev = m;
-    if (g == 0 && qok) partial[((size_t)chunk * F + qrow) * k + r] = m;
+    prev = m = gallery_max4(m);
+    if (L.g == 0 && L.qok) partial[((size_t)L.chunk * F + L.qrow) * k + r] = m;
   }
 }
 
@@ -197,10 +178,10 @@ __global__ void __launch_bounds__(256) gallery_merge_kernel(const uint64_t* __re
         label_out[o] = -1;
         score_out[o] = __uint_as_float(0xFF800000u);
       } else {
-        const uint32_t row = 0xFFFFFFFFu - (uint32_t)best, m = (uint32_t)(best >> 32);
+        const uint32_t row = gallery_key_row(best);
         idx_out[o] = (int32_t)row;
         label_out[o] = labels[row];
-        score_out[o] = __uint_as_float(m == 1u ? 0x7FC00000u : ((m & 0x80000000u) ? (m ^ 0x80000000u) : ~m));
+        score_out[o] = gallery_key_score(best);
       }
     }
   }
@@ -320,9 +301,7 @@ extern "C" int vnf_gallery_class_sums(const float* rows_dev, const int32_t* labe
 
 extern "C" int64_t vnf_gallery_search_workspace_bytes(int F, int k, int64_t G, int64_t chunk_rows) {
   if (F < 0 || k < 1 || k > GAL_MAX_K || G < 0 || G > GAL_MAX_ROWS || chunk_rows < 0) return VNF_E_INVALID;
-  const int64_t cr = gallery_chunk_rows(F, G, chunk_rows);
-  const int64_t nchunks = (G + cr - 1) / cr;
-  const int64_t bytes = nchunks * F * k * 8;
+  const int64_t bytes = GalleryPlan(F, G, chunk_rows).nchunks * F * k * 8;
   return bytes > 0 ? bytes : 8;
 }
 
@@ -336,25 +315,20 @@ extern "C" int vnf_gallery_search(vnf_handle h, const float* q_dev, int F, int k
     if (!q_dev || !idx_out || !label_out || !score_out || !workspace || ((uintptr_t)q_dev & 15) || ((uintptr_t)workspace & 7))
       return fail(VNF_E_INVALID, "vnf_gallery_search: null or misaligned pointer");
     const int64_t G = t->rows;
-    const int64_t cr = gallery_chunk_rows(F, G, chunk_rows);
-    const int64_t nchunks = (G + cr - 1) / cr;
+    const GalleryPlan plan(F, G, chunk_rows);
     if (workspace_bytes < vnf_gallery_search_workspace_bytes(F, k, G, chunk_rows))
       return fail(VNF_E_CAPACITY, "vnf_gallery_search: workspace smaller than vnf_gallery_search_workspace_bytes");
+    if (!plan.ok) return fail(VNF_E_INVALID, "vnf_gallery_search: chunk_rows too small for this gallery");
     hipStream_t s = (hipStream_t)stream;
-    const int nqg = (F + 15) / 16;
-    const int64_t nwork = nchunks * nqg, blocks = (nwork + 3) / 4;
-    if (blocks > 0x7FFFFFFF) return fail(VNF_E_INVALID, "vnf_gallery_search: chunk_rows too small for this gallery");
     uint64_t* partial = (uint64_t*)workspace;
-    if (blocks > 0) {
-      if (t->dim == 16 * GAL_MAX_KG)
-        hipLaunchKernelGGL((gallery_search_kernel<GAL_MAX_KG, true>), dim3((unsigned)blocks), dim3(256), 0, s, t->mat, G, t->dim, q_dev, F, k, cr,
-                           nqg, nwork, partial);
-      else
-        hipLaunchKernelGGL((gallery_search_kernel<GAL_MAX_KG, false>), dim3((unsigned)blocks), dim3(256), 0, s, t->mat, G, t->dim, q_dev, F, k, cr,
-                           nqg, nwork, partial);
+    if (plan.blocks > 0) {
+      gallery_dispatch(t->dim, [&](auto exact) {
+        hipLaunchKernelGGL((gallery_search_kernel<GAL_MAX_KG, decltype(exact)::value>), dim3((unsigned)plan.blocks), dim3(256), 0, s, t->mat,
+                           G, t->dim, q_dev, F, k, plan.chunk_rows, plan.nqg, plan.nwork, partial);
+      });
       VNF_HIP(hipGetLastError());
     }
-    VNF_HIP(gallery_launch_merge(partial, nchunks, F, k, t->labels, idx_out, label_out, score_out, s));
+    VNF_HIP(gallery_launch_merge(partial, plan.nchunks, F, k, t->labels, idx_out, label_out, score_out, s));
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());

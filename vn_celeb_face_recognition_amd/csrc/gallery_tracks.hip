@@ -1,7 +1,7 @@
 // Face tracks: the faces of a video, stored as a gallery in frame order, linked across frames.
 //
-//   s(i,j)      the fp32 dot of stored rows i and j: gallery_cluster.hip's score (gallery_load_rows + gallery_tile), the
-//               same bits from either side
+//   s(i,j)      the fp32 dot of stored rows i and j: gallery_cluster.hip's score, the same bits from either side (the same
+//               gallery_load_rows and gallery_tile of gallery_core.h produce it)
 //   candidate   j is a forward candidate of i where 0 < f(j) - f(i) <= max_gap, j > i (which the order of the rows implies),
 //               s(i,j) >= t (a NaN never) and, with min_iou > 0, the boxes overlap by inter >= min_iou * union.  Every term
 //               is symmetric or antisymmetric in (i, j), so i is a backward candidate of j exactly then
@@ -10,13 +10,12 @@
 //   track       a chain, numbered by its first row
 //
 // Stage A (tracks_best_kernel): a wave owns 16 rows.  The rows are sorted by frame, so everything within max_gap frames
-// of them is ONE contiguous row range, read from frame_first; it passes 32 rows a step through gallery_tile, and a lane
-// keeps its best forward and its best backward candidate (frame distance and key) in registers.  The four lanes of a
+// of them is ONE contiguous row range, read from frame_first: the core's stream over a window in place of a chunk.  A lane
+// keeps its best forward and its best backward candidate (frame distance and key) in registers; the four lanes of a
 // row combine by shuffle and write the two candidates to the workspace.  The work follows the window, not G^2.
 // Stage B (tracks_mutual_kernel): a row keeps a candidate that names it back.
-// Stage C: gallery_cluster.hip's with another way to the roots: parent[i] = prev[i] (< i) or i, ceil(log2(n_frames))
-// rounds of pointer jumping bring every row to its head, the heads are numbered by one workgroup's exclusive scan
-// (block_scan.h), tracks written.
+// Stage C: clustering's (gallery_launch_number) with another way to the roots: parent[i] = prev[i] (< i) or i,
+// ceil(log2(n_frames)) rounds of pointer jumping bring every row to its head, tracks_flatten_kernel flags the heads.
 // vnf_gallery_track_sums: the heads enter counts[] by track, then a wave per track walks next[] and adds the stored rows
 // in row order.
 //
@@ -26,7 +25,6 @@
 // larger row or stops.
 #include <string>
 
-#include "block_scan.h"
 #include "gallery_core.h"
 
 namespace vnf {
@@ -56,12 +54,12 @@ static __device__ __forceinline__ bool track_overlap(const f32x4_t a, const f32x
   return inter >= min_iou * uni;
 }
 
-// Row j (< w_end, frame fj, score s against the lane's row) offered to the lane's row qrow (frame fq).
+// Row j (in: inside the window; score s against the lane's row) offered to the lane's row qrow (frame fq).
 static __device__ __forceinline__ void track_offer(uint32_t& f_near, uint64_t& f_key, uint32_t& b_near, uint64_t& b_key, float s, int64_t j,
-                                                   int64_t w_end, int64_t qrow, bool qok,
+                                                   bool in, int64_t qrow, bool qok,
                                                    int32_t fq, const int32_t* __restrict__ labels, float t, int max_gap, float min_iou,
                                                    const f32x4_t qbox, const f32x4_t* __restrict__ boxes) {
-  if (!qok || j >= w_end || !(s >= t)) return;
+  if (!qok || !in || !(s >= t)) return;
   const int64_t d = (int64_t)labels[j] - (int64_t)fq;
   const bool f = d > 0 && d <= max_gap && j > qrow, b = d < 0 && -d <= max_gap && j < qrow;
   if (!f && !b) return;
@@ -80,13 +78,12 @@ __global__ void __launch_bounds__(256) tracks_best_kernel(const float* __restric
                                                           const f32x4_t* __restrict__ boxes, float t, float min_iou, int max_gap, int64_t nqg,
                                                           int32_t* __restrict__ next_cand, int32_t* __restrict__ pred_cand,
                                                           float* __restrict__ pred_score) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t qg = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t qg = gallery_wave();
   if (qg >= nqg) return;
-  const int c = lane & 15, g = lane >> 4;
-  const int kgs = EXACT ? KG : (dim >> 4);
-  const int64_t q0 = qg * 16, qrow = q0 + c;
-  const bool qok = qrow < G;
+  GalleryLane<int64_t> L;
+  gallery_lane<KG, EXACT>(L, qg, G, dim);
+  const int64_t q0 = qg * 16, qrow = L.qrow;
+  const bool qok = L.qok;
 
   // the window: the rows of the frames within max_gap of the wave's first and last row, as frame_first has them
   int64_t w_begin = 0, w_end = 0;
@@ -101,20 +98,16 @@ __global__ void __launch_bounds__(256) tracks_best_kernel(const float* __restric
   uint64_t f_key = 0, b_key = 0;
   if (w_begin < w_end) {
     f32x4_t qf[KG];   // the wave's 16 rows, as stored, as B fragments
-    gallery_load_rows<KG, EXACT>(gal, qrow, qok, dim, g, kgs, qf);
+    gallery_load_rows<KG, EXACT>(gal, qrow, qok, dim, L.g, L.kgs, qf);
     const int32_t fq = labels[qok ? qrow : 0];
     f32x4_t qbox = {0.f, 0.f, 0.f, 0.f};
     if (min_iou > 0.f && qok) qbox = boxes[qrow];
     for (int64_t r0 = w_begin; r0 < w_end; r0 += 32) {
       f32x4_t acc0, acc1;
-      gallery_tile<KG, EXACT>(gal, r0, w_begin, w_end, dim, c, g, kgs, qf, acc0, acc1);
-      // D[row = 4 g + r][col = c]: this lane's row against rows r0 + 4 g + r and r0 + 16 + 4 g + r
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t i0 = r0 + 4 * g + r;
-        track_offer(f_near, f_key, b_near, b_key, acc0[r], i0, w_end, qrow, qok, fq, labels, t, max_gap, min_iou, qbox, boxes);
-        track_offer(f_near, f_key, b_near, b_key, acc1[r], i0 + 16, w_end, qrow, qok, fq, labels, t, max_gap, min_iou, qbox, boxes);
-      }
+      gallery_tile<KG, EXACT>(gal, r0, w_begin, w_end, dim, L.c, L.g, L.kgs, qf, acc0, acc1);
+      gallery_for_each(r0, L.g, w_end, acc0, acc1, [&](int, int64_t i, float s, bool in) {
+        track_offer(f_near, f_key, b_near, b_key, s, i, in, qrow, qok, fq, labels, t, max_gap, min_iou, qbox, boxes);
+      });
     }
   }
 
@@ -123,11 +116,10 @@ __global__ void __launch_bounds__(256) tracks_best_kernel(const float* __restric
   track_combine(f_near, f_key, 32);
   track_combine(b_near, b_key, 16);
   track_combine(b_near, b_key, 32);
-  if (g == 0 && qok) {
-    next_cand[qrow] = f_near ? (int32_t)(0xFFFFFFFFu - (uint32_t)f_key) : -1;
-    pred_cand[qrow] = b_near ? (int32_t)(0xFFFFFFFFu - (uint32_t)b_key) : -1;
-    const uint32_t m = (uint32_t)(b_key >> 32);   // a candidate's score is no NaN
-    pred_score[qrow] = __uint_as_float(b_near ? ((m & 0x80000000u) ? (m ^ 0x80000000u) : ~m) : 0xFF800000u);
+  if (L.g == 0 && qok) {
+    next_cand[qrow] = f_near ? (int32_t)gallery_key_row(f_key) : -1;
+    pred_cand[qrow] = b_near ? (int32_t)gallery_key_row(b_key) : -1;
+    pred_score[qrow] = b_near ? gallery_key_score(b_key) : __uint_as_float(0xFF800000u);
   }
 }
 
@@ -146,10 +138,6 @@ __global__ void __launch_bounds__(256) tracks_mutual_kernel(const int32_t* __res
   parent[i] = has_prev ? p : (int32_t)i;
 }
 
-static __device__ __forceinline__ int32_t track_parent_load(const int32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // One round of pointer jumping, in place: every row moves up to its grandparent.  Whatever mix of old and new entries
 // a lane reads, an entry only ever moves to an ancestor and at least as far as a round on a snapshot would take it, so
 // ceil(log2(n)) rounds bring every row of a chain of n rows to its head -- a chain of a track has n_frames rows at most.
@@ -157,8 +145,8 @@ static __device__ __forceinline__ int32_t track_parent_load(const int32_t* p) {
 __global__ void __launch_bounds__(256) tracks_jump_kernel(int32_t* parent, int64_t G) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= G) return;
-  const int32_t p = track_parent_load(parent + i);
-  const int32_t gp = track_parent_load(parent + p);
+  const int32_t p = gallery_load_relaxed(parent + i);
+  const int32_t gp = gallery_load_relaxed(parent + p);
   if (gp != p) __hip_atomic_store(parent + i, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -168,19 +156,6 @@ __global__ void __launch_bounds__(256) tracks_flatten_kernel(const int32_t* __re
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= padded) return;
   flag[i] = i < G && parent[i] == (int32_t)i;
-}
-
-// flag -> its exclusive scan: at a head, the track's number.  One workgroup.
-__global__ void __launch_bounds__(kScanLanes) tracks_number_kernel(uint32_t* flag, uint32_t G, int32_t* __restrict__ n_tracks) {
-  const uint32_t n = block_scan(flag, G);
-  if (threadIdx.x == 0) *n_tracks = (int32_t)n;
-}
-
-__global__ void __launch_bounds__(256) tracks_write_kernel(const int32_t* __restrict__ parent, const uint32_t* __restrict__ number, int64_t G,
-                                                           int32_t* __restrict__ track_out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= G) return;
-  track_out[i] = (int32_t)number[parent[i]];
 }
 
 // counts[track of a head] = the head's row.  counts was filled with -1.
@@ -223,8 +198,6 @@ __global__ void __launch_bounds__(64) tracks_sums_kernel(const float* __restrict
   if (lane == 0) counts[k] = cnt;
 }
 
-static int64_t tracks_align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 // The workspace: five (G) 32-bit arrays, each padded to a multiple of 4 entries.
 struct TracksWorkspace {
   int64_t padded, bytes;
@@ -233,14 +206,13 @@ struct TracksWorkspace {
   uint32_t* flag;
   TracksWorkspace(int64_t G, void* base) {
     padded = (G + 3) / 4 * 4;
-    const int64_t ints = tracks_align16(padded * 4);
-    char* p = (char*)base;
-    next_cand = (int32_t*)p;
-    pred_cand = (int32_t*)(p + ints);
-    pred_score = (float*)(p + 2 * ints);
-    parent = (int32_t*)(p + 3 * ints);
-    flag = (uint32_t*)(p + 4 * ints);
-    bytes = 5 * ints;
+    GalleryCarver w{(char*)base};
+    next_cand = w.take<int32_t>(padded * 4);
+    pred_cand = w.take<int32_t>(padded * 4);
+    pred_score = w.take<float>(padded * 4);
+    parent = w.take<int32_t>(padded * 4);
+    flag = w.take<uint32_t>(padded * 4);
+    bytes = w.bytes;
   }
 };
 
@@ -279,12 +251,10 @@ extern "C" int vnf_gallery_tracks(vnf_handle h, const int32_t* frame_first_dev, 
     const f32x4_t* boxes = reinterpret_cast<const f32x4_t*>(boxes_dev);
 
     // A: every row's best forward and backward candidate
-    if (t->dim == 16 * GAL_MAX_KG)
-      hipLaunchKernelGGL((tracks_best_kernel<GAL_MAX_KG, true>), grid, dim3(256), 0, s, t->mat, t->labels, G, t->dim, frame_first_dev, n_frames,
-                         boxes, threshold, min_iou, max_gap, nqg, ws.next_cand, ws.pred_cand, ws.pred_score);
-    else
-      hipLaunchKernelGGL((tracks_best_kernel<GAL_MAX_KG, false>), grid, dim3(256), 0, s, t->mat, t->labels, G, t->dim, frame_first_dev, n_frames,
-                         boxes, threshold, min_iou, max_gap, nqg, ws.next_cand, ws.pred_cand, ws.pred_score);
+    gallery_dispatch(t->dim, [&](auto exact) {
+      hipLaunchKernelGGL((tracks_best_kernel<GAL_MAX_KG, decltype(exact)::value>), grid, dim3(256), 0, s, t->mat, t->labels, G, t->dim,
+                         frame_first_dev, n_frames, boxes, threshold, min_iou, max_gap, nqg, ws.next_cand, ws.pred_cand, ws.pred_score);
+    });
     VNF_HIP(hipGetLastError());
     // B: mutual bests
     hipLaunchKernelGGL(tracks_mutual_kernel, rows_grid, dim3(256), 0, s, ws.next_cand, ws.pred_cand, ws.pred_score, G, prev_out, next_out,
@@ -297,10 +267,7 @@ extern "C" int vnf_gallery_tracks(vnf_handle h, const int32_t* frame_first_dev, 
     }
     hipLaunchKernelGGL(tracks_flatten_kernel, rows_grid, dim3(256), 0, s, ws.parent, G, ws.padded, ws.flag);
     VNF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(tracks_number_kernel, dim3(1), dim3(kScanLanes), 0, s, ws.flag, (uint32_t)G, n_tracks_out);
-    VNF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(tracks_write_kernel, rows_grid, dim3(256), 0, s, ws.parent, ws.flag, G, track_out);
-    VNF_HIP(hipGetLastError());
+    VNF_HIP(gallery_launch_number(ws.parent, ws.flag, G, n_tracks_out, track_out, s));
     return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());

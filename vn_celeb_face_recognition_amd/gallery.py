@@ -191,21 +191,27 @@ class GalleryModel:
         self._add_rows(sums_d, classes, cuda)
 
     # -- search ---------------------------------------------------------------------------------------------------
-    def search(self, emb, k=1):
-        """(F,input_dim) cuda embeddings (any norm) -> (idx (F,k) int32, label (F,k) int32, score (F,k) fp32): the k best
-        rows per query under (cosine descending, row index ascending); slots beyond the gallery hold -1, -1, -inf."""
+    def _probes(self, emb, k=None):
+        """What search() and mated_search() ask of `emb`, in one order -> (device index, emb as contiguous fp32).
+        k: search()'s k, tested here, between the empty-gallery test and the tests of `emb`, because that is where search()
+        has always refused it: a call wrong in two ways keeps raising what it raised.  mated_search() has no k."""
         dev = self._dev()
         if self.size == 0:
             raise ValueError("the gallery is empty: enrol embeddings with .add() first")
-        if not 1 <= int(k) <= MAX_K:
+        if k is not None and not 1 <= int(k) <= MAX_K:
             raise ValueError("k must lie in 1..%d, got %r" % (MAX_K, k))
         if emb.device.type != "cuda":
             raise RuntimeError("embeddings must live on the gallery's cuda device")
         if emb.dim() != 2 or emb.shape[1] != self.input_dim:
             raise ValueError("expected (F,%d) embeddings, got %s" % (self.input_dim, tuple(emb.shape)))
+        return dev, emb.float().contiguous()
+
+    def search(self, emb, k=1):
+        """(F,input_dim) cuda embeddings (any norm) -> (idx (F,k) int32, label (F,k) int32, score (F,k) fp32): the k best
+        rows per query under (cosine descending, row index ascending); slots beyond the gallery hold -1, -1, -inf."""
+        dev, emb = self._probes(emb, k)
         k = int(k)
         h = self._ensure()
-        emb = emb.float().contiguous()
         f = emb.shape[0]
         idx = torch.empty((f, k), dtype=torch.int32, device=emb.device)
         label = torch.empty((f, k), dtype=torch.int32, device=emb.device)
@@ -214,13 +220,10 @@ class GalleryModel:
         with torch.cuda.device(dev):
             for f0 in range(0, f, self.max_batch):
                 nn = min(self.max_batch, f - f0)
-                nbytes = lib.vnf_gallery_search_workspace_bytes(nn, k, self.size, self.chunk_rows)
-                if nbytes < 0:
-                    _lib.check(int(nbytes))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=emb.device)
+                ws = _lib.workspace(lib.vnf_gallery_search_workspace_bytes(nn, k, self.size, self.chunk_rows), emb.device)
                 _lib.check(lib.vnf_gallery_search(h, ctypes.c_void_p(emb[f0:].data_ptr()), nn, k, ctypes.c_void_p(idx[f0:].data_ptr()),
                                                   ctypes.c_void_p(label[f0:].data_ptr()), ctypes.c_void_p(score[f0:].data_ptr()),
-                                                  self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
+                                                  self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream_ptr()))
         return idx, label, score
 
     def _probe_ints(self, values, f, what, device):
@@ -245,18 +248,11 @@ class GalleryModel:
         mate), column 1 the best row of any other label (the non-mate), under search()'s order; an absent one is
         -1, -1, -inf.  exclude: None, or F row indices with -1 for "none" -- a gallery searched with its own rows passes
         arange(G)."""
-        dev = self._dev()
-        if self.size == 0:
-            raise ValueError("the gallery is empty: enrol embeddings with .add() first")
-        if emb.device.type != "cuda":
-            raise RuntimeError("embeddings must live on the gallery's cuda device")
-        if emb.dim() != 2 or emb.shape[1] != self.input_dim:
-            raise ValueError("expected (F,%d) embeddings, got %s" % (self.input_dim, tuple(emb.shape)))
+        dev, emb = self._probes(emb)
         f = emb.shape[0]
         lab = self._probe_ints(labels, f, "labels", emb.device)
         exc = None if exclude is None else self._probe_ints(exclude, f, "exclude", emb.device)
         h = self._ensure()
-        emb = emb.float().contiguous()
         idx = torch.empty((f, 2), dtype=torch.int32, device=emb.device)
         label = torch.empty((f, 2), dtype=torch.int32, device=emb.device)
         score = torch.empty((f, 2), dtype=torch.float32, device=emb.device)
@@ -264,15 +260,12 @@ class GalleryModel:
         with torch.cuda.device(dev):
             for f0 in range(0, f, self.max_batch):
                 nn = min(self.max_batch, f - f0)
-                nbytes = lib.vnf_gallery_mated_search_workspace_bytes(nn, self.size, self.chunk_rows)
-                if nbytes < 0:
-                    _lib.check(int(nbytes))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=emb.device)
+                ws = _lib.workspace(lib.vnf_gallery_mated_search_workspace_bytes(nn, self.size, self.chunk_rows), emb.device)
                 _lib.check(lib.vnf_gallery_mated_search(h, ctypes.c_void_p(emb[f0:].data_ptr()), ctypes.c_void_p(lab[f0:].data_ptr()),
                                                         ctypes.c_void_p(exc[f0:].data_ptr()) if exc is not None else None, nn,
                                                         ctypes.c_void_p(idx[f0:].data_ptr()), ctypes.c_void_p(label[f0:].data_ptr()),
                                                         ctypes.c_void_p(score[f0:].data_ptr()), self.chunk_rows,
-                                                        ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
+                                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream_ptr()))
         return idx, label, score
 
     def cluster(self, threshold, min_samples=2):
@@ -299,14 +292,11 @@ class GalleryModel:
         n_clusters = torch.empty((1,), dtype=torch.int32, device=cuda)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            nbytes = lib.vnf_gallery_cluster_workspace_bytes(g, self.chunk_rows)
-            if nbytes < 0:
-                _lib.check(int(nbytes))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=cuda)
+            ws = _lib.workspace(lib.vnf_gallery_cluster_workspace_bytes(g, self.chunk_rows), cuda)
             _lib.check(lib.vnf_gallery_cluster(h, threshold, int(min_samples), ctypes.c_void_p(cluster.data_ptr()),
                                                ctypes.c_void_p(degree.data_ptr()), ctypes.c_void_p(nn_idx.data_ptr()),
                                                ctypes.c_void_p(nn_score.data_ptr()), ctypes.c_void_p(n_clusters.data_ptr()),
-                                               self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), nbytes, _lib.current_stream_ptr()))
+                                               self.chunk_rows, ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.current_stream_ptr()))
             n = int(n_clusters.item())
         return cluster, degree, nn_idx, nn_score, n
 

@@ -101,12 +101,9 @@ def link_tracks(emb, frame_ord, boxes=None, *, threshold, min_iou=0.0, max_gap=1
             prev, nxt, track = (torch.empty((g,), dtype=torch.int32, device=cuda) for _ in range(3))
             score = torch.empty((g,), dtype=torch.float32, device=cuda)
             n_dev = torch.empty((1,), dtype=torch.int32, device=cuda)
-            nbytes = lib.vnf_gallery_tracks_workspace_bytes(g)
-            if nbytes < 0:
-                _lib.check(int(nbytes))
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=cuda)
+            ws = _lib.workspace(lib.vnf_gallery_tracks_workspace_bytes(g), cuda)
             _lib.check(lib.vnf_gallery_tracks(h, P(first), n_frames, P(bx) if bx is not None else None, threshold, min_iou, max_gap,
-                                              P(prev), P(nxt), P(score), P(track), P(n_dev), P(ws), nbytes, stream))
+                                              P(prev), P(nxt), P(score), P(track), P(n_dev), P(ws), ws.numel(), stream))
             n = int(n_dev.item())
             sums = torch.empty((n, dim), dtype=torch.float32, device=cuda)
             counts = torch.empty((n,), dtype=torch.int32, device=cuda)
