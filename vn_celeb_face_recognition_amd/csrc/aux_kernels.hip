@@ -3,14 +3,11 @@
 #include <cstdlib>
 #include <algorithm>
 #include <type_traits>
+#include "conv_device.h"
 #include "kernels.h"
 #include "storage_unit.h"
 
 namespace vnf {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 template <typename T> __device__ __forceinline__ float to_f(T v) { return (float)v; }
 
@@ -117,6 +114,36 @@ __global__ void __launch_bounds__(256) stem_conv1a_kernel(const TI* __restrict__
   }
 }
 
+// Prologue and epilogue of the two MFMA forms below.  Lane (row col, k slot g) keeps w[k = 4t + g][channel 16 ct + col]
+// of the 7 k-steps and both channel tiles, and the bias of the channels 16 ct + 4g .. + 3 its accumulators hold; cst is
+// the first of the 8 channels it stores after the lane-row swap.  tap(t, k): the kernel's own set-up of k-step t, where
+// its lane fetches tap k.
+template <class Tap>
+__device__ __forceinline__ void stem1a_lane(const float* __restrict__ wt, int col, int g, float (&wa)[2][7],
+                                            float (&bias)[2][4], int& cst, Tap tap) {
+#pragma unroll
+  for (int t = 0; t < 7; ++t) {
+    const int k = 4 * t + g;
+    wa[0][t] = k < 27 ? wt[k * 32 + col] : 0.f;
+    wa[1][t] = k < 27 ? wt[k * 32 + 16 + col] : 0.f;
+    tap(t, k);
+  }
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bias[ct][e] = wt[27 * 32 + 16 * ct + 4 * g + e];
+  cst = (g & 1) * 16 + (g >> 1) * 8;
+}
+// ReLU, rounding to TO, lane-row swap and the 16-byte store(s) of one pixel's 8 channels at d (every lane calls; ok: this
+// lane's pixel exists)
+template <typename TO>
+__device__ __forceinline__ void stem1a_store(TO* d, bool ok, const f32x4_t& a0, const f32x4_t& a1) {
+  f32x4_t r0, r1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { r0[e] = fmaxf(a0[e], 0.f); r1[e] = fmaxf(a1[e], 0.f); }
+  swap_store<TO>(reinterpret_cast<char*>(d), ok, r0, r1);
+}
+
 // The same convolution on the f32 MFMA (v_mfma_f32_16x16x4_f32: the f32 vector rate, exact fmaf chain in k order, so
 // bit-identical to the kernel above), for the 16-bit and planar split-f16 plans.  The VALU form reads its 27 x 32 weights
 // as wave-uniform scalars at every tap -- 864 values do not fit the SGPR file, and the refetch, not the FMAs, set its
@@ -134,19 +161,11 @@ __global__ void __launch_bounds__(256) stem_conv1a_mfma_kernel(const TI* __restr
   const unsigned ngroups = (total + 15) / 16;
   const unsigned nwaves = gridDim.x * 4, w0 = blockIdx.x * 4 + (threadIdx.x >> 6);
   float wa[2][7], bias[2][4];
-  int koff[7];
-#pragma unroll
-  for (int t = 0; t < 7; ++t) {
-    const int k = 4 * t + g;
-    wa[0][t] = k < 27 ? wt[k * 32 + col] : 0.f;
-    wa[1][t] = k < 27 ? wt[k * 32 + 16 + col] : 0.f;
-    koff[t] = k < 27 ? (k / 9) * S * S + ((k % 9) / 3) * S + k % 3 : 0;
-  }
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bias[ct][e] = wt[27 * 32 + 16 * ct + 4 * g + e];
-  const int cst = (g & 1) * 16 + (g >> 1) * 8;   // the 8 channels this lane stores after the swap
+  // koff: element offset of tap k = 4t + g from the pixel's first tap.  It is filled inside stem1a_lane's weight loop: in
+  // a loop of its own the kernel holds every tap address at once (84 -> 104-108 registers, an occupancy step)
+  int cst, koff[7];
+  stem1a_lane(wt, col, g, wa, bias, cst,
+              [&](int t, int k) { koff[t] = k < 27 ? (k / 9) * S * S + ((k % 9) / 3) * S + k % 3 : 0; });
   for (unsigned gi = w0 * G; gi < ngroups; gi += nwaves * G) {
     float xb[G][7];
 #pragma unroll
@@ -160,45 +179,15 @@ __global__ void __launch_bounds__(256) stem_conv1a_mfma_kernel(const TI* __restr
     }
 #pragma unroll
     for (int q = 0; q < G; ++q) {
-      typedef float f4 __attribute__((ext_vector_type(4)));
-      f4 a0 = {bias[0][0], bias[0][1], bias[0][2], bias[0][3]}, a1 = {bias[1][0], bias[1][1], bias[1][2], bias[1][3]};
+      f32x4_t a0 = {bias[0][0], bias[0][1], bias[0][2], bias[0][3]};
+      f32x4_t a1 = {bias[1][0], bias[1][1], bias[1][2], bias[1][3]};
 #pragma unroll
       for (int t = 0; t < 7; ++t) {
         a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[0][t], xb[q][t], a0, 0, 0, 0);
         a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][t], xb[q][t], a1, 0, 0, 0);
       }
       const unsigned i = (gi + q) * 16 + col;
-      const bool ok = gi + q < ngroups && i < total;
-      if constexpr (__is_same(TO, pf16)) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        h4 h0, l0, h1, l1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const sf16 s0(fmaxf(a0[e], 0.f)), s1(fmaxf(a1[e], 0.f));
-          h0[e] = s0.hi; l0[e] = s0.lo;
-          h1[e] = s1.hi; l1[e] = s1.lo;
-        }
-        const uint2 ph0 = __builtin_bit_cast(uint2, h0), ph1 = __builtin_bit_cast(uint2, h1);
-        const uint2 pl0 = __builtin_bit_cast(uint2, l0), pl1 = __builtin_bit_cast(uint2, l1);
-        const auto hx = __builtin_amdgcn_permlane16_swap(ph0.x, ph1.x, false, false);
-        const auto hy = __builtin_amdgcn_permlane16_swap(ph0.y, ph1.y, false, false);
-        const auto lx = __builtin_amdgcn_permlane16_swap(pl0.x, pl1.x, false, false);
-        const auto ly = __builtin_amdgcn_permlane16_swap(pl0.y, pl1.y, false, false);
-        if (ok) {
-          char* d = reinterpret_cast<char*>(y) + ((size_t)i * ldy + cst) * 4;
-          *reinterpret_cast<uint4*>(d) = uint4{hx[0], hy[0], hx[1], hy[1]};
-          *reinterpret_cast<uint4*>(d + 16) = uint4{lx[0], ly[0], lx[1], ly[1]};
-        }
-      } else {
-        typedef TO t4 __attribute__((ext_vector_type(4)));
-        t4 o0, o1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o0[e] = (TO)fmaxf(a0[e], 0.f); o1[e] = (TO)fmaxf(a1[e], 0.f); }
-        const uint2 p0 = __builtin_bit_cast(uint2, o0), p1 = __builtin_bit_cast(uint2, o1);
-        const auto sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
-        if (ok) *reinterpret_cast<uint4*>(y + (size_t)i * ldy + cst) = uint4{sx[0], sy[0], sx[1], sy[1]};
-      }
+      stem1a_store(y + (size_t)i * ldy + cst, gi + q < ngroups && i < total, a0, a1);
     }
   }
 }
@@ -234,7 +223,6 @@ __global__ void __launch_bounds__(256) stem_conv1a_rows_kernel(const TI* __restr
   // a buffer and 16 bytes: lane 15 of a row's last group (pixel 79, not stored) reads up to one element past the rows
   constexpr int BUFB = 3 * CS * ES + 16;
   typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  typedef float f4 __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) char sm[2 * BUFB];
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -266,19 +254,12 @@ __global__ void __launch_bounds__(256) stem_conv1a_rows_kernel(const TI* __restr
   int band = blockIdx.x;
   if (band >= nbands) return;
   float wa[2][7], bias[2][4];
-  int la[7];   // byte offset in a buffer of tap k = 4t + g of this lane's pixel in the wave's row, group 0
-#pragma unroll
-  for (int t = 0; t < 7; ++t) {
-    const int k = 4 * t + g;
-    wa[0][t] = k < 27 ? wt[k * 32 + col] : 0.f;
-    wa[1][t] = k < 27 ? wt[k * 32 + 16 + col] : 0.f;
+  // la: byte offset in a buffer of tap k = 4t + g of this lane's pixel in the wave's row, group 0; filled inside
+  // stem1a_lane's weight loop like koff above, so that both kernels share one prologue
+  int cst, la[7];
+  stem1a_lane(wt, col, g, wa, bias, cst, [&](int t, int k) {
     la[t] = (2 * wave * S + 2 * col + (k < 27 ? (k / 9) * CS + ((k % 9) / 3) * S + k % 3 : 0)) * ES;
-  }
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bias[ct][e] = wt[27 * 32 + 16 * ct + 4 * g + e];
-  const int cst = (g & 1) * 16 + (g >> 1) * 8;   // the 8 channels this lane stores after the swap
+  });
   fetch(band);
   stash(band, 0);
   // nothing of the prologue is pending inside the band loop: the compiler would otherwise drain the vector-memory
@@ -294,11 +275,11 @@ __global__ void __launch_bounds__(256) stem_conv1a_rows_kernel(const TI* __restr
 #pragma unroll
       for (int t = 0; t < 7; ++t)
         xb[j][t] = to_f(*reinterpret_cast<const TI*>(sm + la[t] + (BUF * BUFB + (J0 + j) * 32 * ES)));
-    f4 a0[NJ], a1[NJ];
+    f32x4_t a0[NJ], a1[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      a0[j] = f4{bias[0][0], bias[0][1], bias[0][2], bias[0][3]};
-      a1[j] = f4{bias[1][0], bias[1][1], bias[1][2], bias[1][3]};
+      a0[j] = f32x4_t{bias[0][0], bias[0][1], bias[0][2], bias[0][3]};
+      a1[j] = f32x4_t{bias[1][0], bias[1][1], bias[1][2], bias[1][3]};
     }
 #pragma unroll
     for (int t = 0; t < 7; ++t)
@@ -308,40 +289,9 @@ __global__ void __launch_bounds__(256) stem_conv1a_rows_kernel(const TI* __restr
         a1[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[1][t], xb[j][t], a1[j], 0, 0, 0);
       }
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const unsigned i = row0 + (J0 + j) * 16 + col;
-      const bool ok = (J0 + j + 1) * 16 <= SO || col < SO - (J0 + j) * 16;
-      if constexpr (__is_same(TO, pf16)) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        h4 h0, l0, h1, l1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const sf16 s0(fmaxf(a0[j][e], 0.f)), s1(fmaxf(a1[j][e], 0.f));
-          h0[e] = s0.hi; l0[e] = s0.lo;
-          h1[e] = s1.hi; l1[e] = s1.lo;
-        }
-        const uint2 ph0 = __builtin_bit_cast(uint2, h0), ph1 = __builtin_bit_cast(uint2, h1);
-        const uint2 pl0 = __builtin_bit_cast(uint2, l0), pl1 = __builtin_bit_cast(uint2, l1);
-        const auto hx = __builtin_amdgcn_permlane16_swap(ph0.x, ph1.x, false, false);
-        const auto hy = __builtin_amdgcn_permlane16_swap(ph0.y, ph1.y, false, false);
-        const auto lx = __builtin_amdgcn_permlane16_swap(pl0.x, pl1.x, false, false);
-        const auto ly = __builtin_amdgcn_permlane16_swap(pl0.y, pl1.y, false, false);
-        if (ok) {
-          char* d = reinterpret_cast<char*>(y) + ((size_t)i * ldy + cst) * 4;
-          *reinterpret_cast<uint4*>(d) = uint4{hx[0], hy[0], hx[1], hy[1]};
-          *reinterpret_cast<uint4*>(d + 16) = uint4{lx[0], ly[0], lx[1], ly[1]};
-        }
-      } else {
-        typedef TO t4 __attribute__((ext_vector_type(4)));
-        t4 o0, o1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { o0[e] = (TO)fmaxf(a0[j][e], 0.f); o1[e] = (TO)fmaxf(a1[j][e], 0.f); }
-        const uint2 p0 = __builtin_bit_cast(uint2, o0), p1 = __builtin_bit_cast(uint2, o1);
-        const auto sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
-        if (ok) *reinterpret_cast<uint4*>(y + (size_t)i * ldy + cst) = uint4{sx[0], sy[0], sx[1], sy[1]};
-      }
-    }
+    for (int j = 0; j < NJ; ++j)
+      stem1a_store(y + (size_t)(row0 + (J0 + j) * 16 + col) * ldy + cst, (J0 + j + 1) * 16 <= SO || col < SO - (J0 + j) * 16,
+                   a0[j], a1[j]);
   };
   // one band out of buffer BUF; false when it was this workgroup's last
   auto one_band = [&](auto buf_c) {

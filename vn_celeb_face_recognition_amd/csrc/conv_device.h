@@ -1,7 +1,10 @@
-// Device-side building blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip: LDS-DMA ring
-// kernel; conv_patch.hip: LDS-resident input patch kernel).
+// Device-side building blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip: LDS-DMA ring kernel;
+// conv_patch.hip: LDS-resident input patch kernel; conv_ws.hip: wave-specialised kernel and its persistent form): the MFMA
+// wrappers per storage layout, the consumer K loop (conv_k_loop), the loaders' pixel-row set-up, the LDS-staged epilogue
+// and the register epilogue's swap-and-store (also under the stem_conv1a kernels of aux_kernels.hip).
 #pragma once
 #include <atomic>
+#include <type_traits>
 
 #include "kernels.h"
 #include "split_f16.h"
@@ -461,6 +464,217 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
 template <int N>
 __device__ __forceinline__ void wait_dma_and_barrier() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+
+// ---- loader side: per-thread pixel-row bookkeeping of the im2col gather.  This thread's row p of the A tile is pixel
+// m0 + row0 + RS * p (ring kernel: row0 = tid >> 3, RS rows per DMA pass of the workgroup; loader waves of conv_ws.hip:
+// row0 = 8 * loader wave + lane >> 3, RS = 8 * loader waves).  Rows past M read the zero page (ahi far outside the image).
+// EARLY: the geometry is read once, in front of the rows.  Read inside the `m < M` branch, as the ring kernel has it,
+// every row fetches its kernel arguments again and waits for them; in the loader waves of conv_ws.hip that wait sits on
+// the way to the first DMA of the workgroup (persistent form: of every tile) and cost 1.2 - 1.5 % of a launch, while the
+// ring kernel's sf16 128x32 tiles lose an occupancy step when it is hoisted (profiles/conv_core_ab.txt).
+struct RowGeom { int M, H, W, Wo, HoWo, ldx, sh, sw, ph, pw; };
+template <int AP, int RS, bool EARLY = false>
+__device__ __forceinline__ void row_setup(const KArgs& a, int m0, int row0, int (&abase)[AP], int (&ahi)[AP],
+                                          int (&awi)[AP]) {
+  auto geom = [&]() { return RowGeom{a.M, a.H, a.W, a.Wo, a.Ho * a.Wo, a.ldx, a.sh, a.sw, a.ph, a.pw}; };
+  const int HoWo = a.Ho * a.Wo;
+  RowGeom early = {};
+  if constexpr (EARLY) early = geom();
+#pragma unroll
+  for (int p = 0; p < AP; ++p) {
+    const int m = m0 + row0 + RS * p;
+    if (m < (EARLY ? early.M : a.M)) {
+      RowGeom g = early;
+      if constexpr (!EARLY) { g = geom(); g.HoWo = HoWo; }
+      const int n = m / g.HoWo, r = m - n * g.HoWo;
+      const int ho = r / g.Wo, wo = r - ho * g.Wo;
+      ahi[p] = ho * g.sh - g.ph;
+      awi[p] = wo * g.sw - g.pw;
+      abase[p] = ((n * g.H + ahi[p]) * g.W + awi[p]) * g.ldx;
+    } else {
+      ahi[p] = -(1 << 24);
+      awi[p] = 0;
+      abase[p] = 0;
+    }
+  }
+}
+
+// ---- consumer side: the K loop of every conv kernel --------------------------------------------------------------
+// Fragments of half ks of a K tile from a swizzled [row][128 B] LDS image (physical 16-byte slot p of row r holds logical
+// k-chunk p ^ (r & 7)): TR MFMA tiles of 16 rows from row0 on, lane (frow, fgrp) reading chunk ks * 4 + fgrp of its row.
+template <int TR>
+__device__ __forceinline__ void read_rows(const char* img, int row0, int frow, int fgrp, int ks, uint4 (&f)[TR]) {
+#pragma unroll
+  for (int i = 0; i < TR; ++i) {
+    const int row = row0 + i * 16 + frow;
+    f[i] = *reinterpret_cast<const uint4*>(img + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
+  }
+}
+
+// The loop over the nkt K tiles of one output tile: acc = the sums over K.
+//   join(kt) makes K tile kt readable -- barrier, counted wait, issue of tile kt + S - 1, stamps: whatever the kernel's
+//     ring needs;
+//   rd(kt, ks, x, w) reads the pixel (x) and weight (w) fragments of its half ks;
+//   ahead(kt), if given, runs behind the last fragment read of tile kt: what the kernel does for tile kt + 1 under the
+//     MFMAs (the patch kernel's table look-up, the persistent kernel's stage advance).
+// The MFMA takes the WEIGHT fragment as the A operand and the PIXEL fragment as B, so an accumulator quad holds 4
+// consecutive output channels of one pixel.
+//   2-byte and f32 layouts, PIPE: software-pipelined over half K tiles, the fragment reads of one half in flight under
+//     the MFMAs of the previous half (also across the join), so a wave never idles on LDS latency even at one or two
+//     waves per SIMD.  The second half of the last tile is K padding when K - kt * BKE <= BKE / 2 and is skipped.
+//   planar split-f16: half 0 / 1 of a K tile is the hi / lo plane of the same 32 k values.  Per tile hi.hi' (needs the hi
+//     fragments only) and the two cross terms; with PIPE the cross terms of tile kt - 1 run under the hi reads of tile kt,
+//     so the hi fragments are double-buffered (static indices: the loop is unrolled by two).
+//   !PIPE keeps ONE fragment set (wave tiles whose accumulators leave no room for two): read, multiply, read, multiply.
+struct no_fetch_ahead { __device__ void operator()(int) const {} };
+template <typename T, int TM, int TN, bool PIPE, class Join, class Rd, class Ahead = no_fetch_ahead>
+__device__ __forceinline__ void conv_k_loop(int K, int nkt, f32x4_t (&acc)[TM][TN], Join&& join, Rd&& rd,
+                                            Ahead&& ahead = Ahead{}) {
+  constexpr int BKE = 128 / (int)sizeof(T);
+  constexpr int NF = PIPE ? 2 : 1;
+  // The sums are kept in a struct per MFMA tile and handed over at the end.  A bare f32x4_t[TM][TN] that is indexed here
+  // directly is turned into ONE wide vector by the compiler (AMDGPU promote-alloca runs before the array is split), and
+  // the small tiles then shuffle that vector in and out of the MFMA's registers at every K tile.  Nothing but the
+  // generated code shows whether this still holds: after a compiler change, redo the per-instantiation table of
+  // profiles/conv_core_ab.txt -- the 64x32 / 32x64 ring tiles must stay at 52 - 64 registers and occupancy 8.
+  struct Sum { f32x4_t v; } c[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) c[i][j].v = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  if constexpr (is_planar<T>::value) {
+    uint4 xh[NF][TM], wh[NF][TN], xl[TM], wl[TN];
+    auto cross = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma_cross(c[i][j].v, w[j], wl[j], x[i], xl[i]);
+    };
+    auto hh = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma_hh(c[i][j].v, w[j], x[i]);
+    };
+    if constexpr (PIPE) {
+      auto step = [&](auto P, int kt) {
+        constexpr int b = decltype(P)::value;
+        join(kt);
+        rd(kt, 0, xh[b], wh[b]);
+        if (kt > 0) cross(xh[b ^ 1], wh[b ^ 1]);
+        rd(kt, 1, xl, wl);
+        ahead(kt);
+        hh(xh[b], wh[b]);
+      };
+      int kt = 0;
+      for (; kt + 1 < nkt; kt += 2) {
+        step(std::integral_constant<int, 0>{}, kt);
+        step(std::integral_constant<int, 1>{}, kt + 1);
+      }
+      if (kt < nkt) {
+        step(std::integral_constant<int, 0>{}, kt);
+        cross(xh[0], wh[0]);
+      } else {
+        cross(xh[NF - 1], wh[NF - 1]);
+      }
+    } else {
+      for (int kt = 0; kt < nkt; ++kt) {
+        join(kt);
+        rd(kt, 0, xh[0], wh[0]);
+        rd(kt, 1, xl, wl);
+        ahead(kt);
+        hh(xh[0], wh[0]);
+        cross(xh[0], wh[0]);
+      }
+    }
+  } else {
+    uint4 xf[NF][TM], wf[NF][TN];
+    auto mma = [&](int ks) {
+      const int fs = PIPE ? ks : 0;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mma_chunk<T>(c[i][j].v, wf[fs][j], xf[fs][i]);
+    };
+    bool pend = false;  // second half of the previous K tile read but not yet multiplied
+    for (int kt = 0; kt < nkt; ++kt) {
+      join(kt);
+      if constexpr (PIPE) {
+        rd(kt, 0, xf[0], wf[0]);
+        if (pend) mma(1);
+        pend = BKE / 2 < K - kt * BKE;
+        if (pend) rd(kt, 1, xf[1], wf[1]);
+        ahead(kt);
+        mma(0);
+      } else {
+        rd(kt, 0, xf[0], wf[0]);
+        mma(0);
+        if (BKE / 2 < K - kt * BKE) {
+          rd(kt, 1, xf[0], wf[0]);
+          mma(1);
+        }
+        ahead(kt);
+      }
+    }
+    if (pend) mma(1);
+  }
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) acc[i][j] = c[i][j].v;
+}
+
+// ---- register epilogue: swap and store -----------------------------------------------------------------------------
+// A lane holds, of one pixel, channel quad fgrp of two neighbouring 16-channel MFMA tiles (v0: tile j, v1: tile j + 1).
+// Rounded to T, the odd lane rows of tile j's quads are exchanged with the even lane rows of tile j + 1's
+// (v_permlane16_swap): every lane then owns 8 consecutive channels, those of tile j + (fgrp & 1) from (fgrp >> 1) * 8
+// on, one 16-byte store.  Every lane of the wave must call these (the swap is a cross-lane operation).
+template <typename T>
+__device__ __forceinline__ uint4 swap_quads(const f32x4_t& v0, const f32x4_t& v1) {
+  static_assert(sizeof(T) == 2, "2-byte elements");
+  typedef T tx4 __attribute__((ext_vector_type(4)));
+  tx4 o0, o1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { o0[e] = (T)v0[e]; o1[e] = (T)v1[e]; }
+  const uint2 p0 = __builtin_bit_cast(uint2, o0), p1 = __builtin_bit_cast(uint2, o1);
+  const auto sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
+  const auto sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
+  return uint4{sx[0], sy[0], sx[1], sy[1]};
+}
+// planar split-f16: an 8-channel unit is [8 hi][8 lo], so the hi quads and the lo quads are exchanged separately
+__device__ __forceinline__ void swap_quads_planar(const f32x4_t& v0, const f32x4_t& v1, uint4& hi, uint4& lo) {
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  h4 h0, l0, h1, l1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const sf16 s0(v0[e]), s1(v1[e]);
+    h0[e] = s0.hi; l0[e] = s0.lo;
+    h1[e] = s1.hi; l1[e] = s1.lo;
+  }
+  const uint2 ph0 = __builtin_bit_cast(uint2, h0), ph1 = __builtin_bit_cast(uint2, h1);
+  const uint2 pl0 = __builtin_bit_cast(uint2, l0), pl1 = __builtin_bit_cast(uint2, l1);
+  const auto hx = __builtin_amdgcn_permlane16_swap(ph0.x, ph1.x, false, false);
+  const auto hy = __builtin_amdgcn_permlane16_swap(ph0.y, ph1.y, false, false);
+  const auto lx = __builtin_amdgcn_permlane16_swap(pl0.x, pl1.x, false, false);
+  const auto ly = __builtin_amdgcn_permlane16_swap(pl0.y, pl1.y, false, false);
+  hi = uint4{hx[0], hy[0], hx[1], hy[1]};
+  lo = uint4{lx[0], ly[0], lx[1], ly[1]};
+}
+// both forms behind one call: the swap in every lane, then this lane's 8-channel unit to d where ok
+template <typename T>
+__device__ __forceinline__ void swap_store(char* d, bool ok, const f32x4_t& v0, const f32x4_t& v1) {
+  if constexpr (is_planar<T>::value) {
+    uint4 hi, lo;
+    swap_quads_planar(v0, v1, hi, lo);
+    if (ok) {
+      *reinterpret_cast<uint4*>(d) = hi;
+      *reinterpret_cast<uint4*>(d + 16) = lo;
+    }
+  } else {
+    const uint4 c = swap_quads<T>(v0, v1);
+    if (ok) *reinterpret_cast<uint4*>(d) = c;
+  }
 }
 
 // ---- conv_patch.hip (LDS-resident input patch kernel; tile configurations follow the ring kernel's ids)

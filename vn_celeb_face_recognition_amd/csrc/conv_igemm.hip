@@ -19,12 +19,13 @@
 // so bytes-in-flight per CU -- what bounds these small-K, small-N problems -- is set by LDS
 // capacity (160 KiB) instead of by register pressure.
 //
-// The MFMA is issued with the WEIGHT fragment as the A operand and the ACTIVATION fragment as
-// the B operand, so an accumulator register quad holds 4 consecutive output channels of one
-// pixel.  The epilogue stages fp32 accumulators through LDS and writes whole NHWC rows with
-// 16-byte stores: bias (folded BatchNorm; optionally one of 9 border classes), residual add,
-// ReLU / PReLU, conversion, and routing of column ranges to different destination tensors
-// (concat-free inception branches) all happen there.
+// The K loop itself -- fragment reads, MFMA order, software pipeline -- is conv_k_loop of
+// conv_device.h, shared with the patch and wave-specialised kernels: the WEIGHT fragment is the A
+// operand and the ACTIVATION fragment the B operand, so an accumulator register quad holds 4
+// consecutive output channels of one pixel.  The epilogue (conv_epilogue, same header) stages fp32
+// accumulators through LDS and writes whole NHWC rows with 16-byte stores: bias (folded BatchNorm;
+// optionally one of 9 border classes), residual add, ReLU / PReLU, conversion, and routing of
+// column ranges to different destination tensors (concat-free inception branches) all happen there.
 //
 // dtype paths: bf16 / f16 -> v_mfma_f32_16x16x32_{bf16,f16}; f32 -> v_mfma_f32_16x16x4_f32
 // (exact f32 FMA chain; the <=1e-4 parity path).
@@ -37,84 +38,11 @@
 
 namespace vnf {
 
-// per-thread pixel-row bookkeeping: thread (tid>>3) owns rows lrow + RS*p of the A tile
-template <int AP, int RS>
-__device__ __forceinline__ void row_setup(const KArgs& a, int m0, int lrow, int (&abase)[AP], int (&ahi)[AP],
-                                          int (&awi)[AP]) {
-  const int HoWo = a.Ho * a.Wo;
-#pragma unroll
-  for (int p = 0; p < AP; ++p) {
-    const int m = m0 + lrow + RS * p;
-    if (m < a.M) {
-      const int n = m / HoWo, r = m - n * HoWo;
-      const int ho = r / a.Wo, wo = r - ho * a.Wo;
-      ahi[p] = ho * a.sh - a.ph;
-      awi[p] = wo * a.sw - a.pw;
-      abase[p] = ((n * a.H + ahi[p]) * a.W + awi[p]) * a.ldx;
-    } else {
-      ahi[p] = -(1 << 24);
-      awi[p] = 0;
-      abase[p] = 0;
-    }
-  }
-}
-
-// fragment reads + MFMAs of one K tile held in LDS (A rows at sA, weight rows at sB)
-template <typename T, int TM, int TN>
-__device__ __forceinline__ void tile_mma(const char* sA, const char* sB, int arow0, int brow0, int frow, int fgrp,
-                                         int kleft, f32x4_t (&acc)[TM][TN]) {
-  constexpr int BKE = 128 / (int)sizeof(T);
-  if constexpr (is_planar<T>::value) {
-    uint4 xh[TM], xl[TM], wh[TN], wl[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = arow0 + i * 16 + frow;
-      xh[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + ((fgrp ^ (row & 7)) << 4));
-      xl[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((4 + fgrp) ^ (row & 7)) << 4));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = brow0 + j * 16 + frow;
-      wh[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + ((fgrp ^ (row & 7)) << 4));
-      wl[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((4 + fgrp) ^ (row & 7)) << 4));
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        mma_hh(acc[i][j], wh[j], xh[i]);
-        mma_cross(acc[i][j], wh[j], wl[j], xh[i], xl[i]);
-      }
-    return;
-  }
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    if (ks * (BKE / 2) < kleft) {
-      uint4 xf[TM], wf[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = arow0 + i * 16 + frow;
-        xf[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = brow0 + j * 16 + frow;
-        wf[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_chunk<T>(acc[i][j], wf[j], xf[i]);
-    }
-  }
-}
-
-
 template <typename T, int BM, int BN, int WM, int WN, int S>
 __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ES = (int)sizeof(T);
-  constexpr int CH = 16 / ES, BKE = 128 / ES;
+  constexpr int BKE = 128 / ES;
   constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
   constexpr int NW = WM * WN, NT = NW * 64, RS = NT / 8;  // waves, threads, tile rows covered per DMA pass
   constexpr int AP = BM / RS, BP = BN / RS, L = AP + BP;  // DMA pieces per wave per K tile
@@ -137,10 +65,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs
   const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);  // LDS byte address of the ring
 
   f32x4_t acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // This lane's k-chunk of the next K tile to issue, as (tap row, tap column, channel): advanced by one K tile per
   // issue() -- issue() is called with consecutive kt -- instead of looked up in the layer's gather table, so the
@@ -178,30 +102,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs
     if (t < nkt) issue(t);
 
   const int frow = lane & 15, fgrp = lane >> 4;
-  // Software-pipelined over half K tiles: the fragment reads of one half are in flight under the
-  // MFMAs of the previous half (also across the barrier), so a wave never idles on LDS latency
-  // even with one or two waves per SIMD.
-  uint4 xf[2][TM], wf[2][TN];
-  auto read_frags = [&](int kt, int ks) {
-    const char* sA = smem + (kt % S) * STAGE;
-    const char* sB = sA + BM * 128;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = wm * WTM + i * 16 + frow;
-      xf[ks][i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = wn * WTN + j * 16 + frow;
-      wf[ks][j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-    }
-  };
-  auto mma = [&](int ks) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) mma_chunk<T>(acc[i][j], wf[ks][j], xf[ks][i]);
-  };
   auto sync_tile = [&](int kt) {
     // tile kt has landed once at most the S-2 younger tiles of this wave are still in flight
     if (kt + S - 2 < nkt)
@@ -211,70 +111,11 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_dma_kernel(const KArgs
     // every wave's pieces of tile kt have landed; stage (kt-1)%S is free for tile kt+S-1
     if (kt + S - 1 < nkt) issue(kt + S - 1);
   };
-  if constexpr (is_planar<T>::value) {
-    // planar split-f16: "half" 0 of a K tile is the hi plane, half 1 the lo plane of the same 32 k values.  Per tile
-    // hi.hi' (needs the hi fragments only) and the two cross terms; the cross terms of tile kt-1 run under the hi reads of
-    // tile kt, so the hi fragments are double-buffered (static indices: the loop is unrolled by two).
-    uint4 xh[2][TM], wh[2][TN];
-    auto rd = [&](int kt, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
-      const char* sA = smem + (kt % S) * STAGE;
-      const char* sB = sA + BM * 128;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = wm * WTM + i * 16 + frow;
-        x[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = wn * WTN + j * 16 + frow;
-        w[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-    };
-    auto step = [&](auto P, int kt) {
-      constexpr int c = decltype(P)::value;
-      sync_tile(kt);
-      rd(kt, 0, xh[c], wh[c]);
-      if (kt > 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[c ^ 1][j], wf[1][j], xh[c ^ 1][i], xf[1][i]);
-      }
-      rd(kt, 1, xf[1], wf[1]);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_hh(acc[i][j], wh[c][j], xh[c][i]);
-    };
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-      step(std::integral_constant<int, 0>{}, kt);
-      step(std::integral_constant<int, 1>{}, kt + 1);
-    }
-    if (kt < nkt) {
-      step(std::integral_constant<int, 0>{}, kt);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[0][j], wf[1][j], xh[0][i], xf[1][i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[1][j], wf[1][j], xh[1][i], xf[1][i]);
-    }
-  } else {
-    bool pend = false;  // second half of the previous K tile read but not yet multiplied
-    for (int kt = 0; kt < nkt; ++kt) {
-      sync_tile(kt);
-      read_frags(kt, 0);
-      if (pend) mma(1);
-      pend = BKE / 2 < a.K - kt * BKE;
-      if (pend) read_frags(kt, 1);
-      mma(0);
-    }
-    if (pend) mma(1);
-  }
+  conv_k_loop<T, TM, TN, true>(a.K, nkt, acc, sync_tile, [&](int kt, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
+    const char* sA = smem + (kt % S) * STAGE;
+    read_rows(sA, wm * WTM, frow, fgrp, ks, x);
+    read_rows(sA + BM * 128, wn * WTN, frow, fgrp, ks, w);
+  });
   __syncthreads();
   conv_epilogue<T, BM, BN, WM, WN, S * STAGE>(a, acc, smem, m0, n0);
 }

@@ -16,8 +16,10 @@
 //
 // The activation fragment of pixel p, tap (kh,kw), channel chunk cc sits at
 //   patch + ((vb(p)-v0 + kh)*Wp + ox(p) + kw)*PP*16 + cc*16  =  pb[p] + ptab[k-chunk]
-// -- one add per fragment read, the table is built from the layer's ktab.  K tiles, MFMA operand
-// roles and the epilogue are those of conv_igemm.hip, so results are bit-identical to it.
+// -- one add per fragment read, the table is built from the layer's ktab.  The K loop is conv_k_loop
+// of conv_device.h -- this kernel's own part: the pixel fragments come from the patch, and the table
+// entries of the next K tile are fetched a tile ahead -- and the epilogue is the ring kernel's, so
+// results are bit-identical to it.
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -33,7 +35,7 @@ template <typename T, int BM, int BN, int WM, int WN, int S, bool DBG = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_patch_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ES = (int)sizeof(T);
-  constexpr int CH = 16 / ES, BKE = 128 / ES;
+  constexpr int CH = 16 / ES;
   constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
   constexpr int NW = WM * WN, NT = NW * 64, RS = NT / 8;
   constexpr int BPM = (BN + RS - 1) / RS;  // weight DMA pieces per K tile (upper bound per wave)
@@ -144,10 +146,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_patch_kernel(const KArgs a) 
   stamp();
 
   f32x4_t acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 15, fgrp = lane >> 4;
   int pb[TM];  // byte offset of this lane's pixel (tap 0, chunk 0) in the patch, per MFMA pixel tile
@@ -159,27 +157,11 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_patch_kernel(const KArgs a) 
     pb[i] = ((vb - v0) * a.Wp + ox) * a.pp * 16;
   }
 
-  // software-pipelined over half K tiles (see conv_igemm.hip); the patch offsets of the next K
-  // tile are fetched one tile ahead so no fragment read waits on a table read
-  uint4 xf[2][TM], wf[2][TN];
-  auto read_frags = [&](int kt, int ks, int t) {
-    const char* sB = smem + (kt % S) * STAGE;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) xf[ks][i] = *reinterpret_cast<const uint4*>(patch + (t >= 0 ? pb[i] + t : -16));
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = wn * WTN + j * 16 + frow;
-      wf[ks][j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-    }
-  };
-  auto mma = [&](int ks) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) mma_chunk<T>(acc[i][j], wf[ks][j], xf[ks][i]);
-  };
+  // the patch offsets of a K tile's two halves (t0, t1) are fetched one tile ahead, so no fragment read waits on a
+  // table read
   int t0 = 0, t1 = 0;
   auto sync_tile = [&](int kt) {
+    stamp();
     // the patch pieces are older than every weight piece, so the first wait covers them too
     if (kt + S - 2 < nkt)
       wait_ring();
@@ -187,71 +169,18 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_patch_kernel(const KArgs a) 
       wait_dma_and_barrier<0>();
     if (kt + S - 1 < nkt) issue(kt + S - 1);
     if (kt == 0) { t0 = sP[fgrp]; t1 = sP[4 + fgrp]; }
+    stamp();
   };
-  if constexpr (is_planar<T>::value) {
-    // planar split-f16 (see conv_igemm.hip): half 0 / 1 of a K tile = hi / lo plane; hi fragments double-buffered
-    uint4 xh[2][TM], wh[2][TN];
-    auto rd = [&](int kt, int ks, int t, uint4 (&x)[TM], uint4 (&w)[TN]) {
-      const char* sB = smem + (kt % S) * STAGE;
+  auto rd = [&](int kt, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
+    const int t = ks ? t1 : t0;
 #pragma unroll
-      for (int i = 0; i < TM; ++i) x[i] = *reinterpret_cast<const uint4*>(patch + (t >= 0 ? pb[i] + t : -16));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = wn * WTN + j * 16 + frow;
-        w[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-    };
-    auto step = [&](auto P, int kt) {
-      constexpr int c = decltype(P)::value;
-      sync_tile(kt);
-      rd(kt, 0, t0, xh[c], wh[c]);
-      if (kt > 0) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[c ^ 1][j], wf[1][j], xh[c ^ 1][i], xf[1][i]);
-      }
-      rd(kt, 1, t1, xf[1], wf[1]);
-      t0 = sP[(kt + 1) * 8 + fgrp];  // one row of slack behind the table
-      t1 = sP[(kt + 1) * 8 + 4 + fgrp];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_hh(acc[i][j], wh[c][j], xh[c][i]);
-    };
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-      step(std::integral_constant<int, 0>{}, kt);
-      step(std::integral_constant<int, 1>{}, kt + 1);
-    }
-    if (kt < nkt) {
-      step(std::integral_constant<int, 0>{}, kt);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[0][j], wf[1][j], xh[0][i], xf[1][i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], wh[1][j], wf[1][j], xh[1][i], xf[1][i]);
-    }
-  } else {
-    bool pend = false;
-    for (int kt = 0; kt < nkt; ++kt) {
-      stamp();
-      sync_tile(kt);
-      stamp();
-      read_frags(kt, 0, t0);
-      if (pend) mma(1);
-      pend = BKE / 2 < a.K - kt * BKE;
-      if (pend) read_frags(kt, 1, t1);
-      t0 = sP[(kt + 1) * 8 + fgrp];  // one row of slack behind the table
-      t1 = sP[(kt + 1) * 8 + 4 + fgrp];
-      mma(0);
-    }
-    if (pend) mma(1);
-  }
+    for (int i = 0; i < TM; ++i) x[i] = *reinterpret_cast<const uint4*>(patch + (t >= 0 ? pb[i] + t : -16));
+    read_rows(smem + (kt % S) * STAGE, wn * WTN, frow, fgrp, ks, w);
+  };
+  conv_k_loop<T, TM, TN, true>(a.K, nkt, acc, sync_tile, rd, [&](int kt) {
+    t0 = sP[(kt + 1) * 8 + fgrp];  // one row of slack behind the table
+    t1 = sP[(kt + 1) * 8 + 4 + fgrp];
+  });
   stamp();
   __syncthreads();
   stamp();

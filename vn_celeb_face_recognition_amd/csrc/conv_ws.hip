@@ -5,8 +5,8 @@
 // 28 B/clk/CU, so a 48-KiB K tile holds the waves ~1700 cycles at issue -- and only then
 // multiplies, so the MFMA pipes idle during the issue phase and the DMA path idles during the
 // MFMA phase.  Here the roles are split (MI355X_MICROARCH.md "ring-gemm"):
-//   * WM x WN consumer waves (one per SIMD) only read fragments and issue MFMAs (software-
-//     pipelined over half K tiles, so LDS latency hides under the previous half's MFMAs);
+//   * WM x WN consumer waves (one per SIMD) only read fragments and issue MFMAs (conv_k_loop of
+//     conv_device.h: LDS latency hides under the previous half K tile's MFMAs);
 //   * LW loader waves only issue LDS-DMA pieces (im2col gather + swizzle in the source address,
 //     exactly the ring kernel's image) and wait for them with counted vmcnt.
 // One raw s_barrier per K tile joins both roles: after it tile kt has landed (the loaders waited
@@ -21,11 +21,40 @@
 
 namespace vnf {
 
+// One K tile of a loader wave: its LA pixel pieces (im2col gather; e = the gather-table entry of this lane's k-chunk in K
+// tile kt) and LB weight pieces, to the stage whose LDS byte address -- this wave's first piece -- is sbase.
+template <typename T, int BM, int LW, int LA, int LB>
+__device__ __forceinline__ void issue_pieces(const KArgs& a, const int4 e, unsigned sbase, int kt, const int (&abase)[LA],
+                                             const int (&ahi)[LA], const int (&awi)[LA], const char* wsrc) {
+#pragma unroll
+  for (int p = 0; p < LA; ++p) {
+    const int hi = ahi[p] + e.y, wi = awi[p] + e.z;
+    const bool ok = e.w && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
+    const char* src = ok ? a.x + (size_t)(abase[p] + e.x) * sizeof(T) : a.zero;
+    glds16(src, sbase + p * (LW * 1024));
+  }
+#pragma unroll
+  for (int p = 0; p < LB; ++p)
+    glds16(wsrc + (size_t)(p * LW * 8) * a.wrs + (size_t)kt * a.wts, sbase + BM * 128 + p * (LW * 1024));
+}
+
+// instrumented build: wait_dma_and_barrier<N> as two statements with a stamp in front of, between and behind them
+// (N < 0: no wait for vector memory -- under stamps a consumer wave's only vector-memory operations are the stamps)
+template <int N, class Stamp>
+__device__ __forceinline__ void stamped_join(Stamp stamp) {
+  stamp(0);
+  if constexpr (N >= 0)
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+  else
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  stamp(1);
+  asm volatile("s_barrier" ::: "memory");
+  stamp(2);
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW, bool DBG = false>
 __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_ws_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ES = (int)sizeof(T);
-  constexpr int CH = 16 / ES, BKE = 128 / ES;
   constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
   constexpr int NC = WM * WN, NT = (NC + LW) * 64;
   constexpr int PA = BM / 8, PB = BN / 8;          // 1-KiB pieces (8 rows x 128 B) per K tile
@@ -44,6 +73,12 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_ws_kernel(const
   const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int nkt = a.nkt;
+  // instrumented build (tools/stamp_ws.py): four cycle stamps per wave and K tile of workgroup 600, the first 64 K tiles
+  auto stamp = [&](int kt, int slot) {
+    if constexpr (DBG) {
+      if (a.dbg && blockIdx.x == 600 && lane == 0 && kt < 64) a.dbg[(wave * 64 + kt) * 4 + slot] = __builtin_readcyclecounter();
+    }
+  };
 
   int4* sK = reinterpret_cast<int4*>(smem + S * STAGE);
   for (int i = tid; i < nkt * 8; i += NT) sK[i] = a.ktab[i];
@@ -54,63 +89,31 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_ws_kernel(const
     const int lw = wave - NC;
     const int prow = lane >> 3, lcol = lane & 7;
     const int lchunk = lcol ^ prow;  // piece rows start at multiples of 8: (row & 7) == prow
-    const int HoWo = a.Ho * a.Wo;
     int abase[LA], ahi[LA], awi[LA];
-#pragma unroll
-    for (int p = 0; p < LA; ++p) {
-      const int m = m0 + (lw + p * LW) * 8 + prow;
-      if (m < a.M) {
-        const int n = m / HoWo, r = m - n * HoWo;
-        const int ho = r / a.Wo, wo = r - ho * a.Wo;
-        ahi[p] = ho * a.sh - a.ph;
-        awi[p] = wo * a.sw - a.pw;
-        abase[p] = ((n * a.H + ahi[p]) * a.W + awi[p]) * a.ldx;
-      } else {
-        ahi[p] = -(1 << 24);
-        awi[p] = 0;
-        abase[p] = 0;
-      }
-    }
+    row_setup<LA, LW * 8, true>(a, m0, lw * 8 + prow, abase, ahi, awi);
     const char* wsrc = a.w + (size_t)(n0 + lw * 8 + prow) * a.wrs + lchunk * 16;
     const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
     auto issue = [&](int kt) {
       const unsigned sbase = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((kt % S) * STAGE) + (unsigned)(lw * 1024));
-      const int4 e = sK[kt * 8 + lchunk];
-#pragma unroll
-      for (int p = 0; p < LA; ++p) {
-        const int hi = ahi[p] + e.y, wi = awi[p] + e.z;
-        const bool ok = e.w && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-        const char* src = ok ? a.x + (size_t)(abase[p] + e.x) * ES : a.zero;
-        glds16(src, sbase + p * (LW * 1024));
-      }
-#pragma unroll
-      for (int p = 0; p < LB; ++p)
-        glds16(wsrc + (size_t)(p * LW * 8) * a.wrs + (size_t)kt * a.wts, sbase + BM * 128 + p * (LW * 1024));
+      issue_pieces<T, BM, LW, LA, LB>(a, sK[kt * 8 + lchunk], sbase, kt, abase, ahi, awi, wsrc);
+    };
+    auto wait_tile = [&](auto keep, int kt) {  // all but this wave's `keep` youngest pieces have landed; meet the others
+      constexpr int N = decltype(keep)::value;
+      if constexpr (DBG)
+        stamped_join<N>([&](int slot) { stamp(kt, slot); });
+      else
+        wait_dma_and_barrier<N>();
     };
 #pragma unroll
     for (int t = 0; t < S - 1; ++t)
       if (t < nkt) issue(t);
     for (int kt = 0; kt < nkt; ++kt) {
-      if constexpr (DBG) {
-        const bool st = a.dbg && blockIdx.x == 600 && lane == 0;
-        long long* d = a.dbg + (wave * 64 + kt) * 4;
-        if (st) d[0] = __builtin_readcyclecounter();
-        if (kt + S - 2 < nkt)
-          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((S - 2) * (LA + LB)) : "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if (st) d[1] = __builtin_readcyclecounter();
-        asm volatile("s_barrier" ::: "memory");
-        if (st) d[2] = __builtin_readcyclecounter();
-        if (kt + S - 1 < nkt) issue(kt + S - 1);
-        if (st) d[3] = __builtin_readcyclecounter();
-        continue;
-      }
       if (kt + S - 2 < nkt)
-        wait_dma_and_barrier<(S - 2) * (LA + LB)>();
+        wait_tile(std::integral_constant<int, (S - 2) * (LA + LB)>{}, kt);
       else
-        wait_dma_and_barrier<0>();
+        wait_tile(std::integral_constant<int, 0>{}, kt);
       if (kt + S - 1 < nkt) issue(kt + S - 1);
+      stamp(kt, 3);
     }
     __syncthreads();
     if (conv_epilogue_is_fast<T, BM, BN>(a, S * STAGE)) {  // the consumers' epilogue barriers
@@ -128,134 +131,25 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_ws_kernel(const
   const int wm = wave / WN, wn = wave % WN;
   const int frow = lane & 15, fgrp = lane >> 4;
   f32x4_t acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   // Big wave tiles (8x4 MFMA tiles = 128 accumulator registers) keep ONE fragment set: two would spill.  Their 32
   // MFMAs per half K tile (512 cycles) dwarf the exposed read latency anyway; smaller tiles double-buffer.
   constexpr bool PIPE = (TM + TN) < 12;
-  constexpr int NF = PIPE ? 2 : 1;
-  uint4 xf[NF][TM], wf[NF][TN];
-  auto read_frags = [&](int kt, int ks) {
-    const int fs = PIPE ? ks : 0;
-    const char* sA = smem + (kt % S) * STAGE;
-    const char* sB = sA + BM * 128;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = wm * WTM + i * 16 + frow;
-      xf[fs][i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = wn * WTN + j * 16 + frow;
-      wf[fs][j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-    }
-  };
-  auto mma = [&](int ks) {
-    const int fs = PIPE ? ks : 0;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) mma_chunk<T>(acc[i][j], wf[fs][j], xf[fs][i]);
-  };
-  if constexpr (is_planar<T>::value) {
-    // planar split-f16 (see conv_igemm.hip): half 0 / 1 of a K tile = hi / lo plane of the same 32 k values
-    uint4 xh[NF][TM], wh[NF][TN], xl[TM], wl[TN];
-    auto rd = [&](int kt, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
-      const char* sA = smem + (kt % S) * STAGE;
-      const char* sB = sA + BM * 128;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = wm * WTM + i * 16 + frow;
-        x[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = wn * WTN + j * 16 + frow;
-        w[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-    };
-    auto cross = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], w[j], wl[j], x[i], xl[i]);
-    };
-    auto hh = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_hh(acc[i][j], w[j], x[i]);
-    };
-    if constexpr (PIPE) {
-      auto step = [&](auto P, int kt) {
-        constexpr int c = decltype(P)::value;
-        wait_dma_and_barrier<0>();
-        rd(kt, 0, xh[c], wh[c]);
-        if (kt > 0) cross(xh[c ^ 1], wh[c ^ 1]);
-        rd(kt, 1, xl, wl);
-        hh(xh[c], wh[c]);
-      };
-      int kt = 0;
-      for (; kt + 1 < nkt; kt += 2) {
-        step(std::integral_constant<int, 0>{}, kt);
-        step(std::integral_constant<int, 1>{}, kt + 1);
-      }
-      if (kt < nkt) {
-        step(std::integral_constant<int, 0>{}, kt);
-        cross(xh[0], wh[0]);
-      } else {
-        cross(xh[NF - 1], wh[NF - 1]);
-      }
-    } else {
-      for (int kt = 0; kt < nkt; ++kt) {
-        wait_dma_and_barrier<0>();
-        rd(kt, 0, xh[0], wh[0]);
-        rd(kt, 1, xl, wl);
-        hh(xh[0], wh[0]);
-        cross(xh[0], wh[0]);
-      }
-    }
-    __syncthreads();
-    conv_epilogue<T, BM, BN, WM, WN, EPI_LDS>(a, acc, smem, m0, n0, S * STAGE);
-    return;
-  }
-  bool pend = false;
-  for (int kt = 0; kt < nkt; ++kt) {
-    if constexpr (DBG) {
-      const bool st = a.dbg && blockIdx.x == 600 && lane == 0;
-      long long* d = a.dbg + (wave * 64 + kt) * 4;
-      if (st) d[0] = __builtin_readcyclecounter();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (st) d[1] = __builtin_readcyclecounter();
-      asm volatile("s_barrier" ::: "memory");
-      if (st) d[2] = __builtin_readcyclecounter();
-      read_frags(kt, 0);
-      if (pend) mma(1);
-      pend = BKE / 2 < a.K - kt * BKE;
-      if (pend) read_frags(kt, 1);
-      mma(0);
-      if (st) d[3] = __builtin_readcyclecounter();
-      continue;
-    }
-    wait_dma_and_barrier<0>();  // no DMA of its own: drains this wave's fragment reads, then joins
-    if constexpr (PIPE) {
-      read_frags(kt, 0);
-      if (pend) mma(1);
-      pend = BKE / 2 < a.K - kt * BKE;
-      if (pend) read_frags(kt, 1);
-      mma(0);
-    } else {
-      read_frags(kt, 0);
-      mma(0);
-      if (BKE / 2 < a.K - kt * BKE) {
-        read_frags(kt, 1);
-        mma(1);
-      }
-    }
-  }
-  if (pend) mma(1);
+  conv_k_loop<T, TM, TN, PIPE>(
+      a.K, nkt, acc,
+      [&](int kt) {
+        if constexpr (DBG) {
+          if (kt > 0) stamp(kt - 1, 3);  // the MFMAs of tile kt - 1 are issued (PIPE: but for its second half)
+          stamped_join<-1>([&](int slot) { stamp(kt, slot); });
+        } else {
+          wait_dma_and_barrier<0>();  // no DMA of its own: drains this wave's fragment reads, then joins
+        }
+      },
+      [&](int kt, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
+        const char* sA = smem + (kt % S) * STAGE;
+        read_rows(sA, wm * WTM, frow, fgrp, ks, x);
+        read_rows(sA + BM * 128, wn * WTN, frow, fgrp, ks, w);
+      });
+  stamp(nkt - 1, 3);
   __syncthreads();
   conv_epilogue<T, BM, BN, WM, WN, EPI_LDS>(a, acc, smem, m0, n0, S * STAGE);
 }
@@ -263,21 +157,20 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_ws_kernel(const
 // ---- persistent form -------------------------------------------------------------------------------------------
 // One workgroup per CU walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ...  The loader waves run the ring straight
 // across tile boundaries (K tiles of the next output tile are in flight while the consumers finish this one), and the
-// consumers store their accumulators from registers -- bias, ReLU, rounding to T, a v_permlane16_swap between the two
-// lane rows that hold neighbouring channel quads so every lane owns 8 channels = one 16-byte store -- without touching
-// LDS or a barrier.  In-kernel stamps of the one-tile-per-workgroup form (tools/stamp_patch.py): a workgroup spent 16 %
-// of its life filling the pipeline and 18-29 % in the epilogue (the store burst of 256 workgroups in lockstep runs at
-// HBM write speed); here both overlap the next tile's K loop.  Only for the layers of the fast epilogue (bias + ReLU,
-// output in T, 2-byte T or planar split-f16).  RES: a residual operand (Block8's up projection, small tiles only): its
-// 16-byte chunks are fetched at the START of the tile -- behind the K loop they would wait, vmcnt being in issue order,
-// for the previous tile's stores -- and un-swapped into the accumulator layout in the epilogue.  Same K order, operand
-// roles, fp32 sum, bias add, residual add, max and rounding: bit-identical results.
+// consumers store their accumulators from registers -- bias, ReLU, then swap_store: rounding to T and the lane-row swap
+// that gives every lane 8 channels = one 16-byte store -- without touching LDS or a barrier.  In-kernel stamps of the
+// one-tile-per-workgroup form (tools/stamp_patch.py): a workgroup spent 16 % of its life filling the pipeline and 18-29 %
+// in the epilogue (the store burst of 256 workgroups in lockstep runs at HBM write speed); here both overlap the next
+// tile's K loop.  Only for the layers of the fast epilogue (bias + ReLU, output in T, 2-byte T or planar split-f16).
+// RES: a residual operand (Block8's up projection, small tiles only): its 16-byte chunks are fetched at the START of the
+// tile -- behind the K loop they would wait, vmcnt being in issue order, for the previous tile's stores -- and un-swapped
+// into the accumulator layout in the epilogue.  Same K order, operand roles, fp32 sum, bias add, residual add, max and
+// rounding: bit-identical results.
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW, bool RES = false>
 __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(const KArgs a) {
   static_assert(sizeof(T) == 2 || is_planar<T>::value, "register epilogue: 2-byte elements or planar split-f16 units");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ES = (int)sizeof(T);
-  constexpr int BKE = 128 / ES;
   constexpr int WTM = BM / WM, WTN = BN / WN, TM = WTM / 16, TN = WTN / 16;
   constexpr int NC = WM * WN, NT = (NC + LW) * 64;
   constexpr int PA = BM / 8, PB = BN / 8;
@@ -301,46 +194,20 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
     const int lw = wave - NC;
     const int prow = lane >> 3, lcol = lane & 7;
     const int lchunk = lcol ^ prow;
-    const int HoWo = a.Ho * a.Wo;
     int abase[LA], ahi[LA], awi[LA];
     const char* wsrc = nullptr;
     auto setup = [&](int it) {
       const int bid = xcd_remap((int)blockIdx.x + it * G, a.nblk);
       const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
-      const int m0 = tile_m * BM, n0 = tile_n * BN;
-#pragma unroll
-      for (int p = 0; p < LA; ++p) {
-        const int m = m0 + (lw + p * LW) * 8 + prow;
-        if (m < a.M) {
-          const int n = m / HoWo, r = m - n * HoWo;
-          const int ho = r / a.Wo, wo = r - ho * a.Wo;
-          ahi[p] = ho * a.sh - a.ph;
-          awi[p] = wo * a.sw - a.pw;
-          abase[p] = ((n * a.H + ahi[p]) * a.W + awi[p]) * a.ldx;
-        } else {
-          ahi[p] = -(1 << 24);
-          awi[p] = 0;
-          abase[p] = 0;
-        }
-      }
-      wsrc = a.w + (size_t)(n0 + lw * 8 + prow) * a.wrs + lchunk * 16;
+      row_setup<LA, LW * 8, true>(a, tile_m * BM, lw * 8 + prow, abase, ahi, awi);
+      wsrc = a.w + (size_t)(tile_n * BN + lw * 8 + prow) * a.wrs + lchunk * 16;
     };
     const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)smem);
     int it_i = 0, kt_i = 0, st_i = 0;  // issue cursor: tile ordinal, K tile inside it, ring stage
     setup(0);
     auto issue = [&]() {
       const unsigned sbase = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(st_i * STAGE) + (unsigned)(lw * 1024));
-      const int4 e = sK[kt_i * 8 + lchunk];
-#pragma unroll
-      for (int p = 0; p < LA; ++p) {
-        const int hi = ahi[p] + e.y, wi = awi[p] + e.z;
-        const bool ok = e.w && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
-        const char* src = ok ? a.x + (size_t)(abase[p] + e.x) * ES : a.zero;
-        glds16(src, sbase + p * (LW * 1024));
-      }
-#pragma unroll
-      for (int p = 0; p < LB; ++p)
-        glds16(wsrc + (size_t)(p * LW * 8) * a.wrs + (size_t)kt_i * a.wts, sbase + BM * 128 + p * (LW * 1024));
+      issue_pieces<T, BM, LW, LA, LB>(a, sK[kt_i * 8 + lchunk], sbase, kt_i, abase, ahi, awi, wsrc);
       st_i = st_i + 1 == S ? 0 : st_i + 1;
       if (++kt_i == nkt) {
         kt_i = 0;
@@ -365,20 +232,13 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
   const int frow = lane & 15, fgrp = lane >> 4;
   // no staging epilogue here: the 4 x 8 wave tile double-buffers too (2-byte dtypes; the planar hi/lo sets would spill)
   constexpr bool PIPE = (TM + TN) < 12 || ((TM + TN) == 12 && !is_planar<T>::value);
-  constexpr int NF = PIPE ? 2 : 1;
-  typedef typename std::conditional<is_planar<T>::value, _Float16, T>::type elem_t;
-  typedef elem_t tx4 __attribute__((ext_vector_type(4)));
   const bool relu = a.act == ACT_RELU, prelu = a.act == ACT_PRELU;
-  int st = 0;
+  int st = 0;  // ring stage of the K tile being read: the ring runs on across output tiles
   for (int it = 0; it < ntile; ++it) {
     const int bid = xcd_remap((int)blockIdx.x + it * G, a.nblk);
     const int tile_m = bid / a.tiles_n, tile_n = bid - tile_m * a.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     f32x4_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     uint4 rres[RES ? TM : 1][RES ? TN / 2 : 1];
     if constexpr (RES) {
 #pragma unroll
@@ -390,116 +250,18 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
           rres[i][jp] = *reinterpret_cast<const uint4*>(a.res + ((size_t)m * a.ldres + (c < a.Cout ? c : 0)) * ES);
         }
     }
-    uint4 xf[NF][TM], wf[NF][TN];
-    auto read_frags = [&](int ks) {
-      const int fs = PIPE ? ks : 0;
-      const char* sA = smem + st * STAGE;
-      const char* sB = sA + BM * 128;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = wm * WTM + i * 16 + frow;
-        xf[fs][i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = wn * WTN + j * 16 + frow;
-        wf[fs][j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-      }
-    };
-    auto mma = [&](int ks) {
-      const int fs = PIPE ? ks : 0;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mma_chunk<T>(acc[i][j], wf[fs][j], xf[fs][i]);
-    };
-    auto join = [&]() {
-      // no vmcnt here: this wave's only vector-memory operations are the previous tile's stores, which may still drain
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    };
-    if constexpr (is_planar<T>::value) {
-      // planar split-f16 (see conv_igemm.hip): half 0 / 1 of a K tile = hi / lo plane of the same 32 k values
-      uint4 xh[NF][TM], wh[NF][TN], xl[TM], wl[TN];
-      auto rd = [&](int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
-        const char* sA = smem + st * STAGE;
-        const char* sB = sA + BM * 128;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int row = wm * WTM + i * 16 + frow;
-          x[i] = *reinterpret_cast<const uint4*>(sA + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int row = wn * WTN + j * 16 + frow;
-          w[j] = *reinterpret_cast<const uint4*>(sB + row * 128 + (((ks * 4 + fgrp) ^ (row & 7)) << 4));
-        }
-      };
-      auto cross = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) mma_cross(acc[i][j], w[j], wl[j], x[i], xl[i]);
-      };
-      auto hh = [&](uint4 (&x)[TM], uint4 (&w)[TN]) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) mma_hh(acc[i][j], w[j], x[i]);
-      };
-      auto next_stage = [&]() { st = st + 1 == S ? 0 : st + 1; };
-      if constexpr (PIPE) {
-        auto step = [&](auto P, bool first) {
-          constexpr int c = decltype(P)::value;
-          join();
-          rd(0, xh[c], wh[c]);
-          if (!first) cross(xh[c ^ 1], wh[c ^ 1]);
-          rd(1, xl, wl);
-          hh(xh[c], wh[c]);
-          next_stage();
-        };
-        int kt = 0;
-        for (; kt + 1 < nkt; kt += 2) {
-          step(std::integral_constant<int, 0>{}, kt == 0);
-          step(std::integral_constant<int, 1>{}, false);
-        }
-        if (kt < nkt) {
-          step(std::integral_constant<int, 0>{}, kt == 0);
-          cross(xh[0], wh[0]);
-        } else {
-          cross(xh[NF - 1], wh[NF - 1]);
-        }
-      } else {
-        for (int kt = 0; kt < nkt; ++kt) {
-          join();
-          rd(0, xh[0], wh[0]);
-          rd(1, xl, wl);
-          hh(xh[0], wh[0]);
-          cross(xh[0], wh[0]);
-          next_stage();
-        }
-      }
-    } else {
-    bool pend = false;
-    for (int kt = 0; kt < nkt; ++kt) {
-      join();
-      if constexpr (PIPE) {
-        read_frags(0);
-        if (pend) mma(1);
-        pend = BKE / 2 < a.K - kt * BKE;
-        if (pend) read_frags(1);
-        mma(0);
-      } else {
-        read_frags(0);
-        mma(0);
-        if (BKE / 2 < a.K - kt * BKE) {
-          read_frags(1);
-          mma(1);
-        }
-      }
-      st = st + 1 == S ? 0 : st + 1;
-    }
-    if (pend) mma(1);
-    }
+    conv_k_loop<T, TM, TN, PIPE>(
+        a.K, nkt, acc,
+        [&](int) {
+          // no vmcnt here: this wave's only vector-memory operations are the previous tile's stores, which may still drain
+          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        },
+        [&](int, int ks, uint4 (&x)[TM], uint4 (&w)[TN]) {
+          const char* sA = smem + st * STAGE;
+          read_rows(sA, wm * WTM, frow, fgrp, ks, x);
+          read_rows(sA + BM * 128, wn * WTN, frow, fgrp, ks, w);
+        },
+        [&](int) { st = st + 1 == S ? 0 : st + 1; });
 
     // register epilogue: tiles j (even) and j+1 of a lane-row pair are exchanged so each lane holds 8 channels
 #pragma unroll
@@ -530,6 +292,7 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
         }
         if constexpr (RES) {
           // the chunk this lane will store holds, swapped, the residual of its two accumulator quads
+          typedef T tx4 __attribute__((ext_vector_type(4)));
           const uint4 r = rres[i][j / 2];
           const auto rx = __builtin_amdgcn_permlane16_swap(r.x, r.z, false, false);
           const auto ry = __builtin_amdgcn_permlane16_swap(r.y, r.w, false, false);
@@ -549,38 +312,8 @@ __global__ __launch_bounds__((WM* WN + LW) * 64) void conv_igemm_wsp_kernel(cons
           }
         }
         const int m = m0 + wm * WTM + i * 16 + frow;
-        if constexpr (is_planar<T>::value) {
-          // an 8-channel unit is [8 hi][8 lo]: the hi quads and the lo quads are exchanged separately
-          typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-          h4 h0, l0, h1, l1;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const sf16 s0(v0[e]), s1(v1[e]);
-            h0[e] = s0.hi; l0[e] = s0.lo;
-            h1[e] = s1.hi; l1[e] = s1.lo;
-          }
-          const uint2 ph0 = __builtin_bit_cast(uint2, h0), ph1 = __builtin_bit_cast(uint2, h1);
-          const uint2 pl0 = __builtin_bit_cast(uint2, l0), pl1 = __builtin_bit_cast(uint2, l1);
-          const auto hx = __builtin_amdgcn_permlane16_swap(ph0.x, ph1.x, false, false);
-          const auto hy = __builtin_amdgcn_permlane16_swap(ph0.y, ph1.y, false, false);
-          const auto lx = __builtin_amdgcn_permlane16_swap(pl0.x, pl1.x, false, false);
-          const auto ly = __builtin_amdgcn_permlane16_swap(pl0.y, pl1.y, false, false);
-          if (m < a.M && c < a.Cout) {
-            char* d = dcol + (size_t)m * dld * ES;
-            *reinterpret_cast<uint4*>(d) = uint4{hx[0], hy[0], hx[1], hy[1]};
-            *reinterpret_cast<uint4*>(d + 16) = uint4{lx[0], ly[0], lx[1], ly[1]};
-          }
-        } else {
-          tx4 o0, o1;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { o0[e] = (elem_t)v0[e]; o1[e] = (elem_t)v1[e]; }
-          const uint2 p0 = __builtin_bit_cast(uint2, o0), p1 = __builtin_bit_cast(uint2, o1);
-          // odd lane rows of p0 <-> even lane rows of p1
-          const auto sx = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
-          const auto sy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
-          if (m < a.M && c < a.Cout)
-            *reinterpret_cast<uint4*>(dcol + (size_t)m * dld * ES) = uint4{sx[0], sy[0], sx[1], sy[1]};
-        }
+        swap_store<T>(dcol + (size_t)m * dld * ES, m < a.M && c < a.Cout, f32x4_t{v0[0], v0[1], v0[2], v0[3]},
+                      f32x4_t{v1[0], v1[1], v1[2], v1[3]});
       }
     }
   }
@@ -626,14 +359,18 @@ bool ws_cfg_ok(const ConvArgs& a, int wcfg) {
   return lds <= 160 * 1024;
 }
 
+// tile grid of a launch into kk; returns its dynamic LDS, the ring and the gather table
+static int ws_geometry(KArgs& kk, int bm, int bn, int s) {
+  kk.tiles_n = (kk.Cout + bn - 1) / bn;
+  kk.nblk = ((kk.M + bm - 1) / bm) * kk.tiles_n;
+  return s * (bm + bn) * 128 + kk.nkt * 8 * 16;
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int S, int LW>
 static hipError_t launch_one_tile(const KArgs& k, hipStream_t s) {
   allow_dynamic_lds<conv_igemm_ws_kernel<T, BM, BN, WM, WN, S, LW>>(160 * 1024);
   KArgs kk = k;
-  const int lds = S * (BM + BN) * 128 + k.nkt * 8 * 16;
-  const int tiles_m = (k.M + BM - 1) / BM;
-  kk.tiles_n = (k.Cout + BN - 1) / BN;
-  kk.nblk = tiles_m * kk.tiles_n;
+  const int lds = ws_geometry(kk, BM, BN, S);
   hipLaunchKernelGGL((conv_igemm_ws_kernel<T, BM, BN, WM, WN, S, LW>), dim3(kk.nblk), dim3((WM * WN + LW) * 64), lds, s,
                      kk);
   return hipGetLastError();
@@ -659,9 +396,7 @@ template <typename T, int BM, int BN, int WM, int WN, int S, int LW, bool RES>
 static hipError_t launch_persistent(const KArgs& k, hipStream_t s) {
   allow_dynamic_lds<conv_igemm_wsp_kernel<T, BM, BN, WM, WN, S, LW, RES>>(160 * 1024);
   KArgs kk = k;
-  const int lds = S * (BM + BN) * 128 + k.nkt * 8 * 16;
-  kk.tiles_n = (k.Cout + BN - 1) / BN;
-  kk.nblk = ((k.M + BM - 1) / BM) * kk.tiles_n;
+  const int lds = ws_geometry(kk, BM, BN, S);
   // one workgroup per CU per LDS-resident copy; whole rounds of 8 workgroups keep the blockIdx -> XCD map of xcd_remap
   // (tile t runs on XCD t % 8)
   const int per_cu = lds <= 80 * 1024 ? 2 : 1;
@@ -713,10 +448,7 @@ static_assert(kStampId >= 0, "the instrumented tile is one of kWs");
 static hipError_t launch_stamped(const KArgs& k, hipStream_t s) {
   constexpr auto kernel = conv_igemm_ws_kernel<__bf16, kStamp.bm, kStamp.bn, kStamp.wm, kStamp.wn, kStamp.s, kStamp.lw, true>;
   KArgs kk = k;
-  const int lds = kStamp.s * (kStamp.bm + kStamp.bn) * 128 + k.nkt * 8 * 16;
-  const int tiles_m = (k.M + kStamp.bm - 1) / kStamp.bm;
-  kk.tiles_n = (k.Cout + kStamp.bn - 1) / kStamp.bn;
-  kk.nblk = tiles_m * kk.tiles_n;
+  const int lds = ws_geometry(kk, kStamp.bm, kStamp.bn, kStamp.s);
   return stamped_launch(
       "VNF_WS_STAMP", 8 * 64 * 4, s,
       [&](long long* dbuf) {
