@@ -190,6 +190,7 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   e.taps["block8"] = {x8[cur], 0, 1792};
   // ---- tail (294-302): avgpool -> last_linear (no bias) -> last_bn (eps 1e-3) -> L2 normalise
   e.ops.push_back(Op::avgpool(x8[cur], pool));
+  e.taps["avgpool_1a"] = {pool, 0, 1792};
   {
     ConvSpec s;
     s.name = "last_linear"; s.x_buf = pool; s.cin = s.cin_pad = 1792;
