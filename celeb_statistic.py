@@ -32,11 +32,11 @@ import torch.distributed as dist
 
 from demo_image import build_emotion, build_models, build_parser
 from vn_celeb_face_recognition_amd import dist as vdist
-from vn_celeb_face_recognition_amd.cli_utils import (append_log_to_file, draw_boxes_on_image, draw_emotions,
-                                                     open_frame_source, write_rgb)
+from vn_celeb_face_recognition_amd.cli_utils import (add_stream_arguments, draw_boxes_on_image, draw_emotions, finish_tracker,
+                                                     open_frame_source, progress_log, start_tracker, total_processed,
+                                                     video_export, write_rgb)
 from vn_celeb_face_recognition_amd.pipeline import FacePipeline
-from vn_celeb_face_recognition_amd.statistics import (build_thresholds, convert_sec_to_max_time_quantity,
-                                                      export_json_stat_dynamic_itv, export_json_stat_fixed_itv,
+from vn_celeb_face_recognition_amd.statistics import (build_thresholds, export_json_stat_dynamic_itv, export_json_stat_fixed_itv,
                                                       frame_is_sampled, read_tracker_csv, tracker_header, tracker_row)
 from vn_celeb_face_recognition_amd.video import run_stream
 
@@ -47,8 +47,7 @@ def emotion_tags(idx2etag, idx):
 
 
 def sampled_source(args, frame_idxes):
-    """the frame source reduced to the frames -fidx keeps (celeb_statistic.py:180-187) -> (source, frames per second
-    of input it keeps)"""
+    """the frame source reduced to the frames -fidx keeps (celeb_statistic.py:180-187) -> (source, kept frames per second of input)"""
     source = open_frame_source(args.video_path)
     if args.fps_video > 0:
         source.fps = float(args.fps_video)
@@ -63,10 +62,7 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
     """celeb_statistic.py:150-300 on video.run_stream; identical control flow for every world size"""
     k = args.topk_emotions if idx2etag is not None else 0
     if rank == 0:
-        os.makedirs(args.output_frame, exist_ok=True)
-        with open(args.output_tracker, 'w') as f:
-            f.write('')
-        append_log_to_file(args.output_tracker, tracker_header(args.track_bbox, k > 0, args.track_faces))
+        start_tracker(args, tracker_header(args.track_bbox, k > 0, args.track_faces))
     start_time = time.time()
     frames_seen, faces_seen = {}, []           # --track_faces, rank 0: what every row was made of; every face of the stream
 
@@ -85,27 +81,16 @@ def main(args, pipe, rank, world, source, device=None, encoder=None, idx2etag=No
             img = draw_emotions(img, boxes, emotion_tags(idx2etag, emotions[0]), emotions[1])
         write_rgb(os.path.join(args.output_frame, 'frame_{}.png'.format(number)), img)
 
-    def log(processed, inf):
-        if (processed % args.log_step) == 0:
-            print('Processing for frame: {}, time: {}'.format(inf[-1][1], convert_sec_to_max_time_quantity(inf[-1][0])))
-
     rows, processed = run_stream(source, pipe, args.n_frames, rank, world, device=device,
-                                 on_frame=on_frame if args.save_frame_recognized else None, log=log,
+                                 on_frame=on_frame if args.save_frame_recognized else None, log=progress_log(args.log_step),
                                  decode="host" if args.host_decode else "device", encoder=encoder, emotions=k, row=row,
                                  decode_entropy=args.decode_entropy, faces=face if args.track_faces else None)
-    if world > 1:
-        tot = torch.tensor([processed], device=device if device is not None else 'cuda')
-        dist.all_reduce(tot)
-        processed = int(tot.item())
+    processed = total_processed(processed, world, device)
     if rank != 0:
         return None
     if args.track_faces:
         rows = track_rows(args, pipe, device, frames_seen, faces_seen, row)
-    with open(args.output_tracker, 'a') as f:
-        f.write(''.join(rows[n] for n in sorted(rows)))
-    processed_time = time.time() - start_time
-    print('Saved tracker file in {} ...'.format(args.output_tracker))
-    print('FPS for recognition face: {}'.format(int(processed / max(processed_time, 1e-9))))
+    finish_tracker(args.output_tracker, rows, processed, start_time)
     return read_tracker_csv(args.output_tracker)
 
 
@@ -138,10 +123,8 @@ def track_rows(args, pipe, device, frames_seen, faces_seen, row):
 def make_parser():
     """the command line of this script"""
     p = build_parser('Face recognition on a video')
-    p.add_argument('-i', '--video_path', default='video.mp4', type=str)
-    p.add_argument('-o', '--output_frame', default='output_frame', type=str)
-    p.add_argument('-ot', '--output_tracker', default='tracker.csv', type=str)
-    p.add_argument('-sfr', '--save_frame_recognized', action='store_true')
+    add_stream_arguments(p, fps_default=0.0, fps_help='frame rate of a frame directory / .npy input',
+                         ov_help='annotated video of the sampled frames, encoded on the GPU (Motion-JPEG .avi)')
     p.add_argument('-jst', '--json_tracker', default='tracker.json', type=str)
     p.add_argument('-fidx', '--frame_idxes', nargs='+', type=int, required=True)
     p.add_argument('-ign', '--ignored_name', default='Unknown', type=str)
@@ -149,24 +132,9 @@ def make_parser():
     p.add_argument('-tap', '--n_time_appear', default=8, type=int)
     p.add_argument('--statistic_mode', default='dynamic_itv', type=str, help='dynamic_itv or fixed_itv')
     p.add_argument('--time_an_interval', default=5, type=int)
-    p.add_argument('--log_step', default=100, type=int)
     p.add_argument('--local_thresholds', default='', type=str)
     p.add_argument('--track_bbox', action='store_true')
     p.add_argument('--youtube_video', action='store_true')
-    p.add_argument('--n_frames', default=16, type=int)
-    p.add_argument('-fps', '--fps_video', default=0.0, type=float, help='frame rate of a frame directory / .npy input')
-    p.add_argument('--host_decode', action='store_true',
-                   help='decode JPEG frames (Motion-JPEG .avi, .jpg directory) with Pillow on the host instead of on the GPU')
-    p.add_argument('--decode_entropy', default='host', choices=['host', 'device'],
-                   help='where the Huffman decode of JPEG frames decoded on the GPU runs: on host threads, or on the GPU too '
-                        '(the compressed frames are uploaded as they are; the same pixels); ignored with --host_decode')
-    p.add_argument('-ov', '--output_video', default='', type=str,
-                   help='annotated video of the sampled frames, encoded on the GPU (Motion-JPEG .avi)')
-    p.add_argument('--ov_quality', default=92, type=int, help='JPEG quality of the frames of -ov (1..100)')
-    p.add_argument('--ov_subsampling', default='4:2:0', choices=['4:4:4', '4:2:2', '4:2:0'],
-                   help='chroma subsampling of the frames of -ov')
-    p.add_argument('--ov_entropy', default='host', choices=['host', 'device'],
-                   help='where the Huffman pass of the frames of -ov runs: on host threads, or on the GPU (the same files)')
     p.add_argument('--track_faces', action='store_true',
                    help='link the faces of consecutive processed frames into tracks on the GPU and name every face by its '
                         'track: one name per track, decided from all of its frames; adds the column Track to the tracker')
@@ -231,28 +199,8 @@ if __name__ == '__main__':
         pipe = FacePipeline(detection_md, emb_model, classify_model, label2name_df, args.target_face_size, threshold,
                             embed_batch=256, emotion=emt_model, topk_emotions=args.topk_emotions)
         source, kept_per_second = sampled_source(args, frame_idxes)
-        encoder = None
-        if args.output_video:
-            from vn_celeb_face_recognition_amd.jpeg_encode import VideoEncoder
-            encoder = VideoEncoder(args.output_video, float(max(kept_per_second, 1)), device, args.ov_quality,
-                                   args.ov_subsampling, rank, world, idx2tag=idx2etag, entropy=args.ov_entropy)
-        try:
+        with video_export(args, bool(args.output_video), float(max(kept_per_second, 1)), device, rank, world, idx2etag) as encoder:
             tracker_df = main(args, pipe, rank, world, source, device=device, encoder=encoder, idx2etag=idx2etag)
-        except BaseException:
-            if encoder is not None:
-                encoder.abort()                               # no half-written video, no spool file of this rank
-            raise
-        if encoder is not None:
-            try:
-                encoder.close()
-            except ValueError as e:                           # a stream without sampled frames
-                raise SystemExit("-ov: {}".format(e))
-            if world > 1:
-                dist.barrier()                                # every rank's spool file is complete
-                if rank == 0:
-                    encoder.merge()
-            if rank == 0:
-                print('Save exported video in {} ...'.format(args.output_video))
     elif rank == 0:
         print('Re-use tracker file {}'.format(args.output_tracker))
         tracker_df = read_tracker_csv(args.output_tracker)

@@ -270,6 +270,59 @@ def test_video_stream_uneven_rounds_two_ranks_gloo(n_total, n_frames, cap):
     assert res[0][4] == want
 
 
+def _sequence_worker(rank, world, port, q, n_total, n_frames, cap):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK=str(rank))
+    sys.path.insert(0, REPO)
+    import torch.distributed as dist
+    from vn_celeb_face_recognition_amd import dist as vdist
+    from vn_celeb_face_recognition_amd.video import FrameSource, run_stream
+    vdist.init_from_env("gloo")
+    seen, real = [], dist.all_gather_into_tensor
+
+    def recorder(out, blk, *a, **kw):
+        seen.append(tuple(blk.shape))
+        return real(out, blk, *a, **kw)
+
+    dist.all_gather_into_tensor = recorder
+    try:
+        run_stream(FrameSource(_frames_for(n_total), 25.0), _StubPipe(), n_frames, rank, world, device="cpu", cap=cap)
+    finally:
+        dist.all_gather_into_tensor = real
+    q.put((rank, seen))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("n_total,n_frames,cap", [(23, 4, 2), (19, 4, None), (3, 4, None), (40, 4, 3)])
+def test_video_stream_collective_sequence_two_ranks_gloo(n_total, n_frames, cap):
+    """The collectives run_stream issues, pinned: per round one all_gather_into_tensor of a (cap + 1, 517) block, in
+    round order; round r's follow-up of max(counts) - cap rows comes from its consume step, which runs after round r + 1
+    was issued or in the final drain.  R rounds: G0, G1, [F0], G2, [F1], ..., G(R-1), [F(R-2)], [F(R-1)], the same on
+    both ranks and nothing else.  Expected from the stub's face counts (frame i holds i % 3 faces)."""
+    import torch.multiprocessing as mp
+    world, width = 2, 517
+    c = cap if cap else max(256, 16 * n_frames)
+    batches = [sum(i % 3 for i in range(b * n_frames + 1, min(n_total, (b + 1) * n_frames) + 1))
+               for b in range((n_total + n_frames - 1) // n_frames)]
+    rounds = [batches[r * world:(r + 1) * world] for r in range((len(batches) + world - 1) // world)]
+    follow = [[(max(cnt) - c, width)] if max(cnt) > c else [] for cnt in rounds]
+    want = []
+    for r in range(len(rounds)):
+        want += [(c + 1, width)] + (follow[r - 1] if r else [])
+    want += follow[-1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 35000 + (os.getpid() % 2000) + n_total
+    procs = [ctx.Process(target=_sequence_worker, args=(r, world, port, q, n_total, n_frames, cap)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=180) for _ in range(world))
+    for p in procs:
+        p.join(60)
+    assert res == [(0, want), (1, want)]
+
+
 def test_video_stream_iterator_source_single_process():
     """a decoder-like source (plain iterator): the frame total is only known once it is exhausted"""
     from vn_celeb_face_recognition_amd.video import FrameSource, run_stream

@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 from vn_celeb_face_recognition_amd import jpeg_encode, models  # noqa: E402
 from vn_celeb_face_recognition_amd.pipeline import FacePipeline  # noqa: E402
 from vn_celeb_face_recognition_amd.synth import make_frames  # noqa: E402
-from vn_celeb_face_recognition_amd.video import FrameSource, run_stream  # noqa: E402
+from vn_celeb_face_recognition_amd.video import FrameSource, run_stream, tracker_row  # noqa: E402
 
 DEV = "cuda:0"
 K = 6
@@ -67,7 +67,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         rows, processed = run_stream(FrameSource(frames, 25.0), pipe, B, 0, 1, device=DEV, encoder=video,
-                                     emotions=K if with_emotions else 0)
+                                     emotions=K if with_emotions else 0,     # the default row formatter takes no emotions
+                                     row=lambda tm, num, names, boxes, shape, emotions=None: tracker_row(tm, num, names, boxes, shape))
         video.close()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0

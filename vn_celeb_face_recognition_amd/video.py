@@ -17,6 +17,9 @@ on one GPU and on N:
     (a rank without a batch in the last round sends an empty block), and nothing else in between;
   * rank 0 classifies the gathered embeddings (one vnf_classify per round) and collates tracker rows in frame order.
 """
+import contextlib
+from dataclasses import dataclass
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -132,6 +135,268 @@ class FrameSource:
         return iter(self.frames)
 
 
+class ExchangeLayout:
+    """What one rank sends per round and how the gathered result is taken apart again; no collective, no stream.
+    A face is one fp32 row of WIDTH = 517 + 2k values: 512 embedding, 4 box, 1 frame slot inside the batch [, k emotion
+    class indices, k probabilities].  With world > 1 a rank's block is (cap + 1, WIDTH): a header row whose first value
+    is the batch's face count, then its first `cap` faces; the others are its spill, for the follow-up gather.  With world
+    == 1 nothing is gathered: the block is the payload."""
+
+    def __init__(self, world, cap, k_emo):
+        self.world, self.cap, self.k, self.WIDTH = int(world), int(cap), int(k_emo), 517 + 2 * int(k_emo)
+
+    def payload(self, counts, boxes, emb, ticket, device):
+        """a ticket's result (k > 0: and its .emo_idx / .emo_prob) as (n, WIDTH) rows on `device`; None without faces"""
+        n = int(sum(counts))
+        if not n:
+            return None
+        slot = np.repeat(np.arange(len(counts)), counts).astype(np.float32)   # frame slot inside the batch
+        extra = np.concatenate([np.asarray(boxes, np.float32).reshape(n, 4), slot[:, None]], axis=1)
+        cols = [emb.to(device).float(), torch.from_numpy(extra).to(device, non_blocking=True)]
+        if self.k:
+            if tuple(ticket.emo_idx.shape) != (n, self.k) or tuple(ticket.emo_prob.shape) != (n, self.k):
+                raise ValueError("run_stream(emotions=%d): the ticket carries emotions of shape %s" % (self.k, tuple(ticket.emo_idx.shape)))
+            cols += [ticket.emo_idx.to(device).float(), ticket.emo_prob.to(device).float()]
+        return torch.cat(cols, dim=1)
+
+    def cut(self, payload, device):
+        """-> (the block this rank sends, the rows that did not fit or None)"""
+        n = 0 if payload is None else payload.shape[0]
+        if self.world == 1:
+            return (payload if n else torch.empty((0, self.WIDTH), dtype=torch.float32, device=device)), None
+        blk = torch.zeros((self.cap + 1, self.WIDTH), dtype=torch.float32, device=device)
+        blk[0, 0] = float(n)
+        if n:
+            blk[1:1 + min(n, self.cap)] = payload[:self.cap]
+        return blk, (payload[self.cap:] if n > self.cap else None)
+
+    def split(self, counts, arr, more=None):
+        """columns of the gathered face rows (more: and of the gathered follow-up) -> per rank r its counts[r] rows"""
+        if self.world == 1:
+            return [arr[:counts[0]]]
+        parts = [arr[r * self.cap: r * self.cap + min(c, self.cap)] for r, c in enumerate(counts)]
+        if more is not None:
+            m = more.shape[0] // self.world
+            parts = [np.concatenate([p, more[r * m: r * m + max(0, c - self.cap)]]) for r, (p, c) in enumerate(zip(parts, counts))]
+        return parts
+
+    def emotions(self, tail, sel):
+        """the keyword that carries the emotions of the faces `sel` of the rows' tail (columns 512..); nothing without k"""
+        k = self.k
+        return {"emotions": (tail[sel, 5:5 + k].astype(np.int64), tail[sel, 5 + k:5 + 2 * k])} if k else {}
+
+
+@dataclass
+class Batch:
+    """a batch between submit and its round's exchange; a rank without a batch in the last round has `rnd` only"""
+    rnd: int
+    ticket: object = None
+    frames: object = None        # host side: arrays, or jpeg.HostFrame of a device-decoded batch
+    info: object = None          # [[time, frame number], ...]
+    frames_dev: object = None
+
+
+@dataclass
+class Round:
+    """a round between its exchange and its rows; what a flag switches off stays None"""
+    rnd: int
+    frames: object               # this rank's batch, as in Batch; None when it ran none in this round
+    info: object
+    n: int = 0                   # its faces
+    spill: object = None         # its device rows past `cap`
+    video: object = None         # encoder: (device frames, upload slot, event they are free behind)
+    hdr: object = None           # pinned host copies, valid behind `event` -- world > 1: the gathered face counts;
+    extra: object = None         # classifying ranks: columns 512.. of the gathered rows, their classes and probabilities;
+    amax: object = None
+    prob: object = None
+    emb: object = None           # face sink: columns ..512
+    event: object = None
+
+
+def _uploads(source, n_frames, rank, world, dev, uploader, decode, decode_entropy):
+    """this rank's batches, as ((batch_index, host-side frames, info), (frames_dev, ready, slot) or None without uploader),
+    the upload one batch AHEAD: submit() blocks on the detector's single read-back, so the next batch's host -> HBM copy
+    has to be in flight before it, or copy and detection would take turns"""
+    as_bytes = uploader is not None and decode == "device" and getattr(source, "compressed", None) is not None
+    it = source.rank_batches(n_frames, rank, world, **({"compressed": True} if as_bytes else {}))
+
+    def start(item):
+        if item is None or uploader is None:
+            return item, None
+        from . import jpeg
+        b, q, inf = item
+        if isinstance(q, jpeg.CompressedBatch):
+            kw = {} if decode_entropy == "host" else {"entropy": decode_entropy}
+            frames_dev, ev, slot, q = jpeg.decode_batch(q, dev, uploader, **kw)
+            return (b, q, inf), (frames_dev, ev, slot)
+        return item, uploader.upload(q) + (uploader.last_slot,)
+
+    nxt, up = start(next(it, None))
+    while nxt is not None:
+        cur, cur_up = nxt, up
+        nxt, up = start(next(it, None))
+        yield cur, cur_up
+
+
+class _Stream:
+    """One run_stream call: what its steps share.  comm / uploader are None on the CPU."""
+
+    def __init__(self, source, pipe, n_frames, rank, world, dev, layout, comm, uploader, on_frame, encoder, row, faces):
+        self.source, self.pipe, self.n_frames, self.rank, self.world, self.dev = source, pipe, n_frames, rank, world, dev
+        self.layout, self.comm, self.uploader, self.on_frame, self.encoder, self.row = layout, comm, uploader, on_frame, encoder, row
+        self.sink = faces if rank == 0 else None
+        self.classify_here = rank == 0 or on_frame is not None or encoder is not None
+        self.number_of = getattr(source, "number_of", None) or (lambda pos: pos + 1)
+        self.on_comm = (lambda: torch.cuda.stream(comm)) if comm is not None else contextlib.nullcontext
+        self.rows, self.pending = {}, []     # pending: issued exchanges
+        self.processed, self.shape = 0, None
+
+    def _to_host(self, x):
+        if x is None or self.comm is None:
+            return x
+        return torch.empty(x.shape, dtype=x.dtype, pin_memory=True).copy_(x, non_blocking=True)
+
+    def _classify(self, rows_dev):
+        if not self.classify_here or rows_dev.shape[0] == 0:
+            return None, None
+        return self.pipe.classifier.classify(rows_dev[:, :512].contiguous(), want_logp=False)[1:3]      # (amax, prob)
+
+    def submit(self, item, up):
+        """push a batch the prefetcher yielded through the pipeline -> Batch"""
+        b, q, inf = item
+        if self.shape is None:
+            self.shape = q[0].shape                           # frames of one stream share a shape
+        if up is not None:
+            frames_dev, ready, slot = up
+            ticket = self.pipe.submit(frames_dev, classify=False, ready=ready)
+            ticket.upload_slot = slot
+        else:                                                 # CPU stand-ins: no uploader, and submit takes no `ready`
+            frames_dev = self.pipe.detector._to_device_frames(q)[0]
+            ticket = self.pipe.submit(frames_dev, classify=False)
+        self.processed += len(q)
+        return Batch(b // self.world, ticket, q, inf, frames_dev)
+
+    def retire(self, inflight, keep=0):
+        """issue the exchange of all but the `keep` newest batches in flight; consume every round but the last issued"""
+        while len(inflight) > keep:
+            self.pending.append(self.issue(inflight.pop(0)))
+            while len(self.pending) > 1:
+                self.consume(self.pending.pop(0))
+
+    def issue(self, batch):
+        """enqueue the round's exchange (+ classification of the gathered embeddings) on the side stream, behind this batch's
+        own event only; nothing here waits on the host"""
+        lay, dev, comm, t = self.layout, self.dev, self.comm, batch.ticket
+        rec, payload = Round(batch.rnd, batch.frames, batch.info), None
+        if t is not None:
+            counts, boxes, emb, _, _ = t.result()
+            # The batch's frames were last read by its warp, ahead of the ticket's (embedding) event (no faces: by its
+            # detection, whose read-back the host has waited for): behind it the upload slot is free -- or the encoder may
+            # draw on the frames, which then stay with the round; a batch outside the ring (slot -1) may be the source's own
+            # tensor and is copied.  The emotions were produced ahead of that event too; result() has waited for it.
+            slot, after = getattr(t, "upload_slot", -1), getattr(t, "event", None)
+            if self.uploader is not None and self.encoder is None:
+                self.uploader.release(slot, after)
+            payload = lay.payload(counts, boxes, emb, t, dev)
+            rec.n = 0 if payload is None else payload.shape[0]
+            if self.encoder is not None:
+                rec.video = (batch.frames_dev if slot is not None and slot >= 0 else batch.frames_dev.clone(), slot, after)
+        if comm is not None:
+            comm.wait_stream(torch.cuda.current_stream(dev))
+        with self.on_comm():
+            gathered, rec.spill = lay.cut(payload, dev)
+            if self.world > 1:
+                out = torch.empty((self.world * (lay.cap + 1), lay.WIDTH), dtype=torch.float32, device=dev)
+                dist.all_gather_into_tensor(out, gathered)
+                g = out.view(self.world, lay.cap + 1, lay.WIDTH)
+                rec.hdr = self._to_host(g[:, 0, 0].contiguous())
+                gathered = g[:, 1:, :].reshape(self.world * lay.cap, lay.WIDTH)
+            amax, prob = self._classify(gathered)
+            if self.classify_here:
+                rec.extra, rec.amax, rec.prob = (self._to_host(x) for x in (gathered[:, 512:].contiguous(), amax, prob))
+            if self.sink is not None:
+                rec.emb = self._to_host(gathered[:, :512].contiguous())
+            if payload is not None and comm is not None:
+                payload.record_stream(comm)
+            rec.event = comm.record_event() if comm is not None else None
+        return rec
+
+    def _follow_up(self, rec, m):
+        """rare: a batch held more faces than the fixed block.  Every rank sees the same headers, so every rank issues this
+        same gather of m rows per rank -> host (tail, amax, prob, emb) of its rows"""
+        with self.on_comm():
+            out = torch.empty((self.world * m, self.layout.WIDTH), dtype=torch.float32, device=self.dev)
+            blk = torch.zeros((m, self.layout.WIDTH), dtype=torch.float32, device=self.dev)
+            if rec.spill is not None:
+                blk[:rec.spill.shape[0]] = rec.spill
+            dist.all_gather_into_tensor(out, blk)
+            amax, prob = self._classify(out)
+            if self.classify_here:
+                return (out[:, 512:].cpu().numpy(), amax.cpu().numpy(), prob.cpu().numpy(),
+                        out[:, :512].cpu().numpy() if self.sink is not None else None)
+            if self.comm is not None:
+                self.comm.synchronize()
+        return (None,) * 4
+
+    def consume(self, rec):
+        """host side of a round, one round after its exchange was issued: per-rank counts from the header rows, the
+        follow-up gather for a batch that did not fit the fixed block, names and tracker rows"""
+        if rec.event is not None:
+            rec.event.synchronize()
+        lay = self.layout
+        counts = [rec.n] if self.world == 1 else [int(round(float(c))) for c in rec.hdr.tolist()]
+        m = max(counts) - lay.cap if self.world > 1 else 0
+        more = self._follow_up(rec, m) if m > 0 else (None,) * 4
+        if not self.classify_here:
+            return
+        tails = lay.split(counts, rec.extra.numpy(), more[0])
+        amax = lay.split(counts, rec.amax.numpy() if rec.amax is not None else np.zeros((0,), np.int32), more[1])
+        prob = lay.split(counts, rec.prob.numpy() if rec.prob is not None else np.zeros((0,), np.float32), more[2])
+        embs = lay.split(counts, rec.emb.numpy(), more[3]) if self.sink is not None else [None] * len(counts)
+        amax = np.concatenate(amax)
+        names = identify_names(amax, np.concatenate(prob), self.pipe.classifier.num_classes, self.pipe.label2name,
+                               self.pipe.threshold) if amax.shape[0] else []
+        o = 0
+        for r, (tail, emb) in enumerate(zip(tails, embs)):    # rank r ran batch rnd * world + r
+            nm = names[o:o + tail.shape[0]]
+            o += tail.shape[0]
+            if r == self.rank and rec.info is not None:
+                self._collate_own(rec, nm, tail, emb)
+            elif self.rank == 0:
+                self._collate_other(rec.rnd * self.world + r, nm, tail, emb)
+
+    def _frame(self, tm, num, shape, sel, nm, tail, emb, own=None):
+        """a frame's callbacks in their order -- on_frame (own: my frame's pixels), row (rank 0), sink -> (names, boxes, emotions kw)"""
+        f_names, f_boxes, f_emo = [nm[j] for j in sel], [tail[j, 0:4] for j in sel], self.layout.emotions(tail, sel)
+        if own is not None and self.on_frame is not None:
+            self.on_frame(own, num, f_names, f_boxes, **f_emo)
+        if self.rank == 0:
+            self.rows[num] = self.row(tm, num, f_names, f_boxes, shape, **f_emo)
+        if self.sink is not None:
+            for j, box in zip(sel, f_boxes):
+                self.sink(num, tm, box, emb[j])
+        return f_names, f_boxes, f_emo
+
+    def _collate_own(self, rec, nm, tail, emb):
+        """my own frames, one by one: pixels, times and numbers are here; then the batch goes to the encoder"""
+        sl = tail[:, 4].astype(np.int64)
+        b_names, b_boxes, b_emo = (list(col) for col in zip(*(
+            self._frame(tm, num, rec.frames[i].shape, np.nonzero(sl == i)[0], nm, tail, emb, own=rec.frames[i])
+            for i, (tm, num) in enumerate(rec.info))))
+        if self.encoder is not None:
+            (frames_dev, slot, after), rec.video = rec.video, None
+            emo = {"emotions": [e["emotions"] for e in b_emo]} if self.layout.k else {}
+            done = self.encoder.write_batch(frames_dev, [num for _, num in rec.info], b_boxes, b_names, after=after, **emo)
+            self.uploader.release(slot, done)
+
+    def _collate_other(self, batch_index, nm, tail, emb):
+        """rank 0, another rank's frames, by ascending frame slot: number and time follow from the batch index"""
+        sl = tail[:, 4].astype(np.int64)
+        for i in np.unique(sl):
+            num = self.number_of(batch_index * self.n_frames + int(i))
+            self._frame(num / self.source.fps, num, self.shape, np.nonzero(sl == i)[0], nm, tail, emb)
+
+
 def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=None, log=None, lag=2, cap=None,
                decode="device", encoder=None, emotions=0, row=None, decode_entropy="host", faces=None):
     """Push this rank's batches through `pipe.submit`, exchange per round, collate on rank 0.
@@ -174,269 +439,43 @@ def run_stream(source, pipe, n_frames, rank=0, world=1, device=None, on_frame=No
         raise ValueError("run_stream: emotions must be in 0..16, got %r" % (emotions,))
     if k_emo and int(getattr(getattr(pipe, "emotion", None), "num_classes", 0) or 0) >= 1 << 24:
         raise ValueError("run_stream: the exchange carries emotion indices as fp32, exact below 2^24 classes only")
-    row = row if row is not None else tracker_row
-    number_of = getattr(source, "number_of", None) or (lambda pos: pos + 1)
+    for name, value, ok in (("decode", decode, ("device", "host")), ("decode_entropy", decode_entropy, ("host", "device"))):
+        if value not in ok:
+            raise ValueError("run_stream: %s must be %r or %r, got %r" % (name, ok[0], ok[1], value))
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    on_gpu = dev.type == "cuda"
     comm = uploader = None
-    if on_gpu:
+    if dev.type == "cuda":
         from .streams import side_stream
         from .upload import FrameUploader
         comm = side_stream(dev, 7)          # the collective's stream (roles 0..6 belong to the pipeline, streams.py)
-        # with an encoder a batch keeps its device slot one round past its exchange (until consume() has its names)
         uploader = FrameUploader(dev, depth=lag + 3 + (2 if encoder is not None else 0))
     elif encoder is not None:
         raise RuntimeError("run_stream: the video encoder works on frames in device memory (there is no CPU path)")
-    cap = int(cap) if cap else max(256, 16 * int(n_frames))
-    WIDTH = 517 + 2 * k_emo                 # 512 embedding + 4 box + 1 frame slot [+ k emotion indices + k probabilities]
-    classify_here = rank == 0 or on_frame is not None or encoder is not None
-    sink = faces if rank == 0 else None
-    rows, inflight, pending = {}, [], []    # inflight: (round, ticket or None, frames, info); pending: issued exchanges
-    state = {"processed": 0, "shape": None}
-
-    def emo(ex, sel):
-        """the keyword that carries the emotions of the faces `sel` of the gathered rows' tail `ex`; nothing without k"""
-        if not k_emo:
-            return {}
-        return {"emotions": (ex[sel, 5:5 + k_emo].astype(np.int64), ex[sel, 5 + k_emo:5 + 2 * k_emo])}
-
-    def to_host(x):
-        if x is None or not on_gpu:
-            return x
-        h = torch.empty(x.shape, dtype=x.dtype, pin_memory=True)
-        h.copy_(x, non_blocking=True)
-        return h
-
-    def classify(rows_dev):
-        if not classify_here or rows_dev.shape[0] == 0:
-            return None, None
-        _, amax, prob = pipe.classifier.classify(rows_dev[:, :512].contiguous(), want_logp=False)
-        return amax, prob
-
-    def issue(item):
-        """enqueue round `rnd`'s exchange (+ classification of the gathered embeddings) on the side stream, behind
-        this batch's own event only; nothing here waits on the host"""
-        rnd, t, q, inf, frames_dev = item
-        n, payload = 0, None
-        if t is not None:
-            counts, boxes, emb, _, _ = t.result()
-            if uploader is not None and encoder is None:
-                # the batch's frames were last read by its warp, which precedes its embedding event (a batch without
-                # faces: by its detection, whose read-back the host has already waited for)
-                uploader.release(getattr(t, "upload_slot", -1), getattr(t, "event", None))
-            n = int(sum(counts))
-            if n:
-                slot = np.repeat(np.arange(len(counts)), counts).astype(np.float32)   # frame slot inside the batch
-                extra = np.concatenate([np.asarray(boxes, np.float32).reshape(n, 4), slot[:, None]], axis=1)
-                cols = [emb.to(dev).float(), torch.from_numpy(extra).to(dev, non_blocking=True)]
-                if k_emo:
-                    # produced on the embedding stream ahead of the ticket's event, which result() has waited for
-                    if tuple(t.emo_idx.shape) != (n, k_emo) or tuple(t.emo_prob.shape) != (n, k_emo):
-                        raise ValueError("run_stream(emotions=%d): the ticket carries emotions of shape %s" %
-                                         (k_emo, tuple(t.emo_idx.shape)))
-                    cols += [t.emo_idx.to(dev).float(), t.emo_prob.to(dev).float()]
-                payload = torch.cat(cols, dim=1)
-        rec = {"rnd": rnd, "q": q, "inf": inf, "own": t is not None, "n": n, "spill": None, "hdr": None}
-        if encoder is not None and t is not None:
-            # the frames stay with the round: the encoder draws on them once the detector and the warp are done with
-            # them (the ticket's embedding event; a batch without faces: the detection the host has waited for)
-            # A batch outside the upload ring (slot -1) may be the source's own tensor -- FrameUploader.upload returns a
-            # cuda tensor it is handed as it is --, and the overlay paints in place: the encoder then gets a copy.
-            slot = getattr(t, "upload_slot", -1)
-            rec["video"] = (frames_dev if slot is not None and slot >= 0 else frames_dev.clone(), slot, getattr(t, "event", None))
-        if comm is not None:
-            comm.wait_stream(torch.cuda.current_stream(dev))
-        with (torch.cuda.stream(comm) if comm is not None else _null()):
-            if world == 1:
-                gathered = payload if n else torch.empty((0, WIDTH), dtype=torch.float32, device=dev)
-            else:
-                blk = torch.zeros((cap + 1, WIDTH), dtype=torch.float32, device=dev)
-                blk[0, 0] = float(n)
-                if n:
-                    blk[1:1 + min(n, cap)] = payload[:cap]
-                    if n > cap:
-                        rec["spill"] = payload[cap:]
-                out = torch.empty((world * (cap + 1), WIDTH), dtype=torch.float32, device=dev)
-                dist.all_gather_into_tensor(out, blk)
-                g = out.view(world, cap + 1, WIDTH)
-                rec["hdr"] = to_host(g[:, 0, 0].contiguous())
-                gathered = g[:, 1:, :].reshape(world * cap, WIDTH)
-            amax, prob = classify(gathered)
-            if classify_here:
-                rec["extra"], rec["amax"], rec["prob"] = to_host(gathered[:, 512:].contiguous()), to_host(amax), to_host(prob)
-            if sink is not None:
-                rec["emb"] = to_host(gathered[:, :512].contiguous())
-            if payload is not None and comm is not None:
-                payload.record_stream(comm)
-            rec["event"] = comm.record_event() if comm is not None else None
-        return rec
-
-    def consume(rec):
-        """host side of a round, one round after its exchange was issued: per-rank counts from the header rows, the
-        follow-up gather for a batch that did not fit the fixed block, names and tracker rows"""
-        if rec["event"] is not None:
-            rec["event"].synchronize()
-        counts = [rec["n"]] if world == 1 else [int(round(float(c))) for c in rec["hdr"].tolist()]
-        parts = None
-        if classify_here:
-            ex = rec["extra"].numpy()
-            am = rec["amax"].numpy() if rec["amax"] is not None else np.zeros((0,), np.int32)
-            pr = rec["prob"].numpy() if rec["prob"] is not None else np.zeros((0,), np.float32)
-            stride = cap if world > 1 else 0
-            parts = [[ex[r * stride: r * stride + min(c, cap if world > 1 else c)],
-                      am[r * stride: r * stride + min(c, cap if world > 1 else c)],
-                      pr[r * stride: r * stride + min(c, cap if world > 1 else c)]] for r, c in enumerate(counts)]
-            if sink is not None:
-                em = rec["emb"].numpy()
-                embs = [em[r * stride: r * stride + min(c, cap if world > 1 else c)] for r, c in enumerate(counts)]
-        if world > 1 and max(counts) > cap:
-            # rare: some rank's batch held more faces than the fixed block; every rank sees the same headers, so every
-            # rank issues this same exactly-sized follow-up here
-            m = max(counts) - cap
-            with (torch.cuda.stream(comm) if comm is not None else _null()):
-                blk = torch.zeros((m, WIDTH), dtype=torch.float32, device=dev)
-                if rec["spill"] is not None:
-                    blk[:rec["spill"].shape[0]] = rec["spill"]
-                out = torch.empty((world * m, WIDTH), dtype=torch.float32, device=dev)
-                dist.all_gather_into_tensor(out, blk)
-                amax, prob = classify(out)
-                if classify_here:
-                    ex2, am2, pr2 = out[:, 512:].cpu().numpy(), amax.cpu().numpy(), prob.cpu().numpy()
-                    for r, c in enumerate(counts):
-                        k = max(0, c - cap)
-                        parts[r] = [np.concatenate([parts[r][0], ex2[r * m: r * m + k]]),
-                                    np.concatenate([parts[r][1], am2[r * m: r * m + k]]),
-                                    np.concatenate([parts[r][2], pr2[r * m: r * m + k]])]
-                    if sink is not None:
-                        em2 = out[:, :512].cpu().numpy()
-                        embs = [np.concatenate([embs[r], em2[r * m: r * m + max(0, c - cap)]]) for r, c in enumerate(counts)]
-                elif comm is not None:
-                    comm.synchronize()
-        if not classify_here:
-            return
-        rnd, q, inf = rec["rnd"], rec["q"], rec["inf"]
-        amax_all = np.concatenate([p[1] for p in parts]) if parts else np.zeros((0,), np.int32)
-        names = identify_names(amax_all, np.concatenate([p[2] for p in parts]), pipe.classifier.num_classes,
-                               pipe.label2name, pipe.threshold) if amax_all.shape[0] else []
-        o = 0
-        for r, (ex, _, _) in enumerate(parts):                # rank r ran batch rnd * world + r
-            k = ex.shape[0]
-            nm, bx, sl = names[o:o + k], ex[:, 0:4], ex[:, 4].astype(np.int64)
-            o += k
-            if r == rank and rec["own"]:                      # my own frames: pixels, times and numbers are here
-                b_names, b_boxes, b_emo = [], [], []
-                for i, (tm, num) in enumerate(inf):
-                    sel = np.nonzero(sl == i)[0]
-                    f_names, f_boxes, f_emo = [nm[j] for j in sel], [bx[j] for j in sel], emo(ex, sel)
-                    b_names.append(f_names)
-                    b_boxes.append(f_boxes)
-                    if k_emo:
-                        b_emo.append(f_emo["emotions"])
-                    if on_frame is not None:
-                        on_frame(q[i], num, f_names, f_boxes, **f_emo)
-                    if rank == 0:
-                        rows[num] = row(tm, num, f_names, f_boxes, q[i].shape, **f_emo)
-                    if sink is not None:
-                        for j in sel:
-                            sink(num, tm, bx[j], embs[r][j])
-                if encoder is not None:
-                    frames_dev, slot, after = rec.pop("video")
-                    done = encoder.write_batch(frames_dev, [num for _, num in inf], b_boxes, b_names, after=after,
-                                               **({"emotions": b_emo} if k_emo else {}))
-                    uploader.release(slot, done)
-            elif rank == 0:                                   # another rank's frames: number and time follow from the batch index
-                for i in np.unique(sl):
-                    sel = np.nonzero(sl == i)[0]
-                    num = number_of((rnd * world + r) * n_frames + int(i))
-                    rows[num] = row(num / source.fps, num, [nm[j] for j in sel], [bx[j] for j in sel], state["shape"],
-                                    **emo(ex, sel))
-                    if sink is not None:
-                        for j in sel:
-                            sink(num, num / source.fps, bx[j], embs[r][j])
-
-    def retire(item):
-        pending.append(issue(item))
-        while len(pending) > 1:
-            consume(pending.pop(0))
-
-    def uploads():
-        """this rank's batches with the upload one batch AHEAD: submit() blocks on the detector's single read-back, so
-        the next batch's host -> HBM copy has to be in flight before it, or copy and detection would take turns"""
-        if decode not in ("device", "host"):
-            raise ValueError("run_stream: decode must be 'device' or 'host', got %r" % (decode,))
-        if decode_entropy not in ("host", "device"):
-            raise ValueError("run_stream: decode_entropy must be 'host' or 'device', got %r" % (decode_entropy,))
-        if uploader is not None and decode == "device" and getattr(source, "compressed", None) is not None:
-            it = source.rank_batches(n_frames, rank, world, compressed=True)
-        else:
-            it = source.rank_batches(n_frames, rank, world)
-
-        def start(item):
-            """enqueue a batch's way into HBM -> (item with host-side frames, (frames_dev, ready, slot) or None)"""
-            if item is None or uploader is None:
-                return item, None
-            from .jpeg import CompressedBatch, decode_batch
-            b, q, inf = item
-            if isinstance(q, CompressedBatch):
-                if decode_entropy == "host":
-                    frames_dev, ev, slot, q = decode_batch(q, dev, uploader)
-                else:
-                    frames_dev, ev, slot, q = decode_batch(q, dev, uploader, entropy=decode_entropy)
-                return (b, q, inf), (frames_dev, ev, slot)
-            return item, uploader.upload(q) + (uploader.last_slot,)
-
-        nxt, up = start(next(it, None))
-        while nxt is not None:
-            cur, cur_up = nxt, up
-            nxt, up = start(next(it, None))
-            yield cur, cur_up
-
-    rounds = 0
-    for (b, q, inf), up in uploads():
-        if state["shape"] is None:
-            state["shape"] = q[0].shape                       # frames of one stream share a shape
-        if up is not None:
-            frames_dev, ready, slot = up
-            ticket = pipe.submit(frames_dev, classify=False, ready=ready)
-            ticket.upload_slot = slot
-        else:
-            frames_dev, _ = pipe.detector._to_device_frames(q)
-            ticket = pipe.submit(frames_dev, classify=False)
-        inflight.append((b // world, ticket, q, inf, frames_dev))
-        rounds = b // world + 1
-        state["processed"] += len(q)
+    layout = ExchangeLayout(world, int(cap) if cap else max(256, 16 * int(n_frames)), k_emo)
+    st = _Stream(source, pipe, n_frames, rank, world, dev, layout, comm, uploader, on_frame, encoder, row or tracker_row, faces)
+    inflight, rounds = [], 0                # submitted batches, retired `lag` late; rounds this rank has a batch in
+    for item, up in _uploads(source, n_frames, rank, world, dev, uploader, decode, decode_entropy):
+        inflight.append(st.submit(item, up))
+        rounds = inflight[-1].rnd + 1
         if log is not None:
-            log(state["processed"], inf)
-        while len(inflight) > lag:
-            retire(inflight.pop(0))
-    # Every rank joins every round's exchange, in round order, and issues no other collective: the stream's length is
-    # known to every rank by now (random access: len(); a decoder: every rank has pulled every frame), so the number of
-    # rounds follows locally.  A rank owns rounds 0 .. rounds-1 without gaps; only the last round can be missing.
-    total_frames = int(source.total if source.total is not None else state["processed"])
-    total_batches = (total_frames + n_frames - 1) // n_frames
-    total_rounds = (total_batches + world - 1) // world
-    for rnd in range(rounds, total_rounds):
-        inflight.append((rnd, None, None, None, None))
+            log(st.processed, item[2])
+        st.retire(inflight, lag)
+    # Every rank joins every round's exchange, in round order, and issues no other collective: it knows the stream's length
+    # by now (random access: len(); a decoder: it has pulled every frame).  It owns rounds 0 .. rounds-1; only the last may be missing.
+    total_frames = int(source.total if source.total is not None else st.processed)
+    total_rounds = ((total_frames + n_frames - 1) // n_frames + world - 1) // world
+    inflight += [Batch(rnd) for rnd in range(rounds, total_rounds)]
     if hasattr(pipe, "flush"):
         pipe.flush()
-    while inflight:
-        retire(inflight.pop(0))
-    while pending:
-        consume(pending.pop(0))
+    st.retire(inflight)
+    for rec in st.pending:                  # the last round issued, if there was any
+        st.consume(rec)
     if uploader is not None:
         uploader.close()
     if rank == 0:
         # a frame without faces sent nothing through the exchange: its (empty) row follows from the frame count
-        none = np.zeros((0,), np.int64)
-        for num in (number_of(pos) for pos in range(total_frames)):
-            if num not in rows:
-                rows[num] = row(num / source.fps, num, [], [], state["shape"] or (1, 1, 3), **emo(np.zeros((0, WIDTH - 512), np.float32), none))
-    return rows, state["processed"]
-
-
-class _null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+        none = layout.emotions(np.zeros((0, layout.WIDTH - 512), np.float32), np.zeros((0,), np.int64))
+        for num in (st.number_of(pos) for pos in range(total_frames)):
+            if num not in st.rows:
+                st.rows[num] = st.row(num / source.fps, num, [], [], st.shape or (1, 1, 3), **none)
+    return st.rows, st.processed
