@@ -352,6 +352,33 @@ int vnf_mtcnn_debug_pnet(vnf_handle h, const uint8_t* frames, int height, int wi
 int vnf_mtcnn_debug_stage3(vnf_handle h, const float* boxes, const float* onet_out, int n, float* fin_out,
                            int max_out, int32_t* n_out, void* stream);
 
+/* staged parity hook for R-Net (net 2) or O-Net (net 3) on their own (mtcnn.py:84-99 / 138-157 behind
+ * detect_face.py:108-117 / 137-146): the caller's rectangles become the candidate table of stage 2 / stage 3 and the
+ * cascade's own launch sequence runs on it -- prefix offsets, then per chunk of the dense batch the crop kernel, the
+ * fused front (conv1 + pool1), the fused mid (conv2 + pool2) where the handle has it, the plan and the heads scatter.
+ *   frames      device (b,H,W,3) uint8, as for vnf_mtcnn_detect
+ *   rects       host int32 (total,4): y, ey, x, ex as pad() returns them (detect_face.py:277-289: 1-based, inclusive),
+ *               frame 0's rows first; every value inside the frame (VNF_E_INVALID otherwise)
+ *   counts      host int32 (b): rectangles per frame, each at most the rows per frame of the handle's tables
+ *               (vnf_mtcnn_cfg.max_candidates) -- VNF_E_CAPACITY beyond, as for b above max_batch
+ *   table_out   host fp32 (total,nf), frame-major: nf = 5 [prob, reg0..3] for R-Net, 15 [prob, reg0..3, lm0..9] for
+ *               O-Net, the rows stage2_post / stage3_post read
+ *   status_out  the kernels' status word (0: nothing flagged)
+ * Reads no environment variable, allocates nothing that outlives the call, forgets the speculative launch sizes and the
+ * last detection's results.  Synchronises. */
+int vnf_mtcnn_debug_net(vnf_handle h, int net, const uint8_t* frames, int b, int height, int width,
+                        const int32_t* rects, const int32_t* counts, float* table_out, int32_t* status_out, void* stream);
+
+/* One buffer of the LAST chunk the previous vnf_mtcnn_debug_net on this handle and net processed, as its raw 32-bit
+ * words: the n_last x H x W x C NHWC rows, no row padding.  dims receives {n_last, H, W, C, split, c0}: split 1 = a
+ * word is a split-f16 (hi, lo) pair (hi in the low half), 0 = an fp32 value (the crops in every form); c0 = dense
+ * index (frames concatenated) of the chunk's first candidate.  Names: crops (C = 4: RGB + 0), pool1, conv2, pool2,
+ * conv3, pool3 and conv4 (O-Net), dense, heads.  raw_out NULL: dims only.  VNF_E_INVALID for an unknown name, without a
+ * preceding debug call on that net, and for a buffer the handle's form never writes (conv2 under the fused mid
+ * kernel); VNF_E_CAPACITY if the rows exceed capacity_bytes. */
+int vnf_mtcnn_debug_net_tap(vnf_handle h, int net, const char* name, void* raw_out, int64_t capacity_bytes,
+                            int32_t dims[6]);
+
 /* RetinaFace detector (replaces /root/reference/models/retina_face.py:56-232, the mobilenet0.25 configuration of
  * cfg/detection/retina_face.json) ---------------------------------------------------------------------------------- */
 typedef struct {

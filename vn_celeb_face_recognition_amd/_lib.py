@@ -101,6 +101,8 @@ SIGNATURES = {
     "vnf_mtcnn_stage_times": (_I, [_P, _P, _I, _I, _I, ctypes.c_char_p, ctypes.c_int64, _P]),
     "vnf_mtcnn_debug_stage3": (_I, [_P, _P, _P, _I, _P, _I, ctypes.POINTER(ctypes.c_int32), _P]),
     "vnf_mtcnn_debug_pnet": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _P]),
+    "vnf_mtcnn_debug_net": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _P]),
+    "vnf_mtcnn_debug_net_tap": (_I, [_P, _I, ctypes.c_char_p, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
     "vnf_retina_create": (_I, [ctypes.POINTER(TensorDesc), _I, ctypes.POINTER(RetinaCfg), ctypes.POINTER(_P)]),
     "vnf_retina_detect": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, ctypes.POINTER(ctypes.c_int32), _P]),
     "vnf_retina_results_device": (_I, [_P, _P, _P, _P, _P, _I, _P]),

@@ -56,6 +56,7 @@ struct Mtcnn : HandleBase {
   bool spec_on = true;                        // VNF_MTCNN_SPEC: size stages 2 / 3 from the previous call's counts
   bool layers = false;                        // VNF_MTCNN_LAYERS (diagnostic): per-layer table of the plans on stderr
   int last_b = 0;  // frames of the last vnf_mtcnn_detect (vnf_mtcnn_results_device)
+  struct Dbg { int net = 0, c0 = 0, n = 0; } dbg;   // last chunk of the last vnf_mtcnn_debug_net (net 0: none) for its taps
   struct Spec { bool valid = false; int b = 0, H = 0, W = 0, max2 = 0, total2 = 0, max3 = 0, total3 = 0; } spec;   // launch sizes of stages 2 / 3 from the previous call
   ~Mtcnn() override { if (h_pin) (void)hipHostFree(h_pin); }
   size_t cap_px = 0, cap_p1 = 0, cap_c2 = 0, cap_out = 0;
@@ -652,6 +653,113 @@ extern "C" int vnf_mtcnn_debug_pnet(vnf_handle h, const uint8_t* frames, int hei
       if (e != hipSuccess) r = fail(VNF_E_HIP, hipGetErrorString(e));
     }
     return r;
+  } catch (const std::exception& ex) {
+    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
+  }
+}
+
+// the net a debug hook names: 2 = R-Net, 3 = O-Net
+static NetStage* debug_net_of(Mtcnn* m, int net) { return net == 2 ? &m->rnet : net == 3 ? &m->onet : nullptr; }
+
+// Staged-parity hook for R-Net / O-Net on their own: the caller's rectangles become the candidate table of stage 2
+// (net 2) or stage 3 (net 3) and run_net -- the cascade's own launch sequence -- processes it.  vnface.h has the layout.
+extern "C" int vnf_mtcnn_debug_net(vnf_handle h, int net, const uint8_t* frames, int b, int height, int width,
+                                   const int32_t* rects, const int32_t* counts, float* table_out, int32_t* status_out,
+                                   void* stream) {
+  try {
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
+    m->last_b = 0; m->spec.valid = false; m->dbg = {};   // whatever comes of this call, the taps and results of earlier ones are gone
+    const NetStage* ns = debug_net_of(m, net);
+    if (!ns) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net: net " + std::to_string(net) + " is neither 2 (R-Net) nor 3 (O-Net)");
+    if (!frames || b <= 0 || height <= 0 || width <= 0 || !counts || !status_out)
+      return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net: bad argument");
+    if (b > m->cfg.max_batch || height > m->cfg.max_height || width > m->cfg.max_width)
+      return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_net: " + std::to_string(b) + " frames of " + std::to_string(height) + " x " +
+                                  std::to_string(width) + " exceed the handle's capacity (max_batch " + std::to_string(m->cfg.max_batch) + ")");
+    int total = 0, maxc = 0;
+    for (int i = 0; i < b; ++i) {
+      if (counts[i] < 0) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net: negative count");
+      if (counts[i] > m->keep)
+        return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_net: frame " + std::to_string(i) + " has " + std::to_string(counts[i]) +
+                                    " rectangles, the handle's tables hold " + std::to_string(m->keep) + " rows per frame");
+      total += counts[i]; maxc = std::max(maxc, counts[i]);
+    }
+    if (total > 0 && (!rects || !table_out)) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net: bad argument");
+    // the crop kernel reads the frame wherever a rectangle points: pad() keeps 1 <= y, ey <= H and 1 <= x, ex <= W
+    for (int k = 0; k < total; ++k) {
+      const int32_t* r = rects + (size_t)k * 4;
+      if (r[0] < 1 || r[0] > height || r[1] < 1 || r[1] > height || r[2] < 1 || r[2] > width || r[3] < 1 || r[3] > width)
+        return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net: rectangle " + std::to_string(k) + " leaves the frame");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    *status_out = 0;
+    if (total == 0) return VNF_OK;
+    Row* drows = net == 2 ? m->rows : m->rows3;
+    int* dcnt = net == 2 ? m->row_cnt : m->row3_cnt;
+    std::vector<Row> rows((size_t)total);
+    for (int k = 0; k < total; ++k) {
+      Row r{};
+      r.y = rects[k * 4]; r.ey = rects[k * 4 + 1]; r.x = rects[k * 4 + 2]; r.ex = rects[k * 4 + 3];
+      rows[k] = r;
+    }
+    for (int i = 0, o = 0; i < b; o += counts[i], ++i)
+      if (counts[i]) VNF_HIP(hipMemcpyAsync(drows + (size_t)i * m->keep, rows.data() + o, (size_t)counts[i] * sizeof(Row), hipMemcpyHostToDevice, s));
+    VNF_HIP(hipMemcpyAsync(dcnt, counts, (size_t)b * 4, hipMemcpyHostToDevice, s));
+    VNF_HIP(hipMemsetAsync(m->status, 0, 4, s));
+    const RunCtx c{m, frames, b, height, width, LevelTable{}, s, nullptr};
+    const int rc = run_net(c, *ns, drows, dcnt, maxc, total);
+    VNF_HIP(hipStreamSynchronize(s));   // also on failure: `rows` and `counts` are still being read
+    if (rc != VNF_OK) return rc;
+    for (int i = 0, o = 0; i < b; o += counts[i], ++i)
+      if (counts[i]) VNF_HIP(hipMemcpy(table_out + (size_t)o * ns->nf, ns->out + (size_t)i * m->keep * ns->nf, (size_t)counts[i] * ns->nf * 4, hipMemcpyDeviceToHost));
+    VNF_HIP(hipMemcpy(status_out, m->status, 4, hipMemcpyDeviceToHost));
+    m->dbg.net = net; m->dbg.c0 = ((total - 1) / ns->cap) * ns->cap; m->dbg.n = total - m->dbg.c0;
+    return VNF_OK;
+  } catch (const std::exception& ex) {
+    return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
+  }
+}
+
+// does the handle's launch sequence write plan buffer `buf` of the net?  The detector's kernels write crops, pooled1 and
+// (fused mid) pooled2, the plan what its convolutions and pools name
+static bool net_writes(const Mtcnn* m, const NetStage& ns, int buf) {
+  if (buf == ns.bufs.crops || buf == ns.bufs.pooled1 || (m->mid && buf == ns.bufs.pooled2)) return true;
+  for (const Op& op : ns.enc->ops) {
+    if (op.kind == Op::MAXPOOL && op.dst == buf) return true;
+    if (op.kind != Op::CONV) continue;
+    const ConvLayer& L = ns.enc->convs[op.layer];
+    for (int i = 0; i < L.nseg; ++i)
+      if (L.seg[i].buf == buf) return true;
+  }
+  return false;
+}
+
+// One plan buffer of the LAST chunk the previous vnf_mtcnn_debug_net processed, as raw 32-bit words (vnface.h).
+extern "C" int vnf_mtcnn_debug_net_tap(vnf_handle h, int net, const char* name, void* raw_out, int64_t capacity_bytes,
+                                       int32_t dims[6]) {
+  try {
+    Mtcnn* m = handle_cast<Mtcnn>(h);
+    if (!m) return fail(VNF_E_INVALID, "not an MTCNN handle");
+    const NetStage* ns = debug_net_of(m, net);
+    if (!ns || !name || !dims) return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net_tap: bad argument");
+    const auto it = ns->enc->taps.find(name);
+    if (it == ns->enc->taps.end()) return fail(VNF_E_INVALID, std::string("vnf_mtcnn_debug_net_tap: no such tap: ") + name);
+    if (m->dbg.net != net)
+      return fail(VNF_E_INVALID, "vnf_mtcnn_debug_net_tap: no vnf_mtcnn_debug_net call on net " + std::to_string(net) +
+                                 " with candidates precedes the tap");
+    if (!net_writes(m, *ns, it->second.buf))
+      return fail(VNF_E_INVALID, std::string("vnf_mtcnn_debug_net_tap: '") + name + "' is computed inside the fused conv2 + pool2 kernel and "
+                  "never reaches memory on this handle: create the detector under VNF_MTCNN_MID=0 (or VNF_MTCNN_DTYPE=f32) to read it");
+    const Buf& bf = ns->enc->bufs[it->second.buf];
+    dims[0] = m->dbg.n; dims[1] = bf.H; dims[2] = bf.W; dims[3] = bf.C;
+    dims[4] = ns->enc->dtype == F16X2 && it->second.buf != ns->bufs.crops ? 1 : 0;   // the crops stay fp32 in every form
+    dims[5] = m->dbg.c0;
+    if (!raw_out) return VNF_OK;   // a size query
+    const int64_t bytes = (int64_t)m->dbg.n * (int64_t)bf.elems_per_image() * 4;
+    if (bytes > capacity_bytes) return fail(VNF_E_CAPACITY, "vnf_mtcnn_debug_net_tap: the tap holds " + std::to_string(bytes) + " bytes");
+    VNF_HIP(hipMemcpy(raw_out, bf.ptr, (size_t)bytes, hipMemcpyDeviceToHost));
+    return VNF_OK;
   } catch (const std::exception& ex) {
     return fail(VNF_E_INVALID, std::string("exception: ") + ex.what());
   }

@@ -67,6 +67,9 @@ int build_rnet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb) {
   TRY(mtcnn_conv(e, wm, "conv3", "prelu3", p2, 48, 48, 64, 64, 2, c3));
   TRY(mtcnn_dense(e, wm, "dense4", "prelu4", c3, 64, 128, d4, keep));
   TRY(mtcnn_heads(e, wm, {{"dense5_1", 2}, {"dense5_2", 4}}, d4, 128, hd, 8));
+  // names of vnf_mtcnn_debug_net_tap (metadata only)
+  e.taps["crops"] = {x, 0, 4}; e.taps["pool1"] = {p1, 0, 32}; e.taps["conv2"] = {c2, 0, 48}; e.taps["pool2"] = {p2, 0, 48};
+  e.taps["conv3"] = {c3, 0, 64}; e.taps["dense"] = {d4, 0, 128}; e.taps["heads"] = {hd, 0, 8};
   return VNF_OK;
 }
 
@@ -87,6 +90,9 @@ int build_onet(Encoder& e, WeightMap& wm, bool mid, NetBufs& nb) {
   TRY(mtcnn_conv(e, wm, "conv4", "prelu4", p3, 64, 64, 128, 128, 2, c4));
   TRY(mtcnn_dense(e, wm, "dense5", "prelu5", c4, 128, 256, d5, keep));
   TRY(mtcnn_heads(e, wm, {{"dense6_1", 2}, {"dense6_2", 4}, {"dense6_3", 10}}, d5, 256, hd, 16));
+  e.taps["crops"] = {x, 0, 4}; e.taps["pool1"] = {p1, 0, 32}; e.taps["conv2"] = {c2, 0, 64}; e.taps["pool2"] = {p2, 0, 64};
+  e.taps["conv3"] = {c3, 0, 64}; e.taps["pool3"] = {p3, 0, 64}; e.taps["conv4"] = {c4, 0, 128}; e.taps["dense"] = {d5, 0, 256};
+  e.taps["heads"] = {hd, 0, 16};
   return VNF_OK;
 }
 

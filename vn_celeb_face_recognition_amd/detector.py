@@ -507,3 +507,40 @@ class MTCNN(_Detector):
                                                 prob.ctypes.data, reg.ctypes.data, dims, _lib.current_stream_ptr()))
         hs, ws, oh, ow = (int(d) for d in dims)
         return (lvl[:3 * hs * ws].reshape(3, hs, ws), prob[:oh * ow].reshape(oh, ow), reg[:4 * oh * ow].reshape(4, oh, ow))
+
+    def debug_net(self, frames, net, rects, counts):
+        """R-Net (net 2) or O-Net (net 3) alone, through the cascade's own launch sequence (vnf_mtcnn_debug_net), on a
+        caller-made candidate table: frames (b,H,W,3) u8, rects (total,4) int32 y, ey, x, ex as pad() returns them
+        (frame 0's rows first), counts (b,) rectangles per frame.  Returns the (total,nf) fp32 table, rows [prob,
+        values...] (nf 5 / 15); the kernels' status word of the call is left in `debug_status`."""
+        frames, _ = self._to_device_frames(frames)
+        b, h, w, _ = frames.shape
+        rects = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if len(counts) != b or int(counts.sum()) != len(rects):
+            raise ValueError("debug_net: %d frames, %d counts that sum to %d, %d rectangles" % (b, len(counts), int(counts.sum()), len(rects)))
+        hd = self._ensure(min(b, self._cap[0]), min(h, self._cap[1]), min(w, self._cap[2]))   # beyond the capacity: the library refuses
+        table = np.zeros((len(rects), 5 if net == 2 else 15), dtype=np.float32)
+        status = ctypes.c_int32(0)
+        with torch.cuda.device(frames.device):
+            _lib.check(_lib.load().vnf_mtcnn_debug_net(hd, int(net), ctypes.c_void_p(frames.data_ptr()), b, h, w, rects.ctypes.data,
+                                                       counts.ctypes.data, table.ctypes.data, ctypes.byref(status),
+                                                       _lib.current_stream_ptr()))
+        self._frames = frames
+        self.debug_status = int(status.value)
+        return table
+
+    def debug_net_tap(self, net, name):
+        """One buffer of the last chunk of the previous debug_net on this net (vnf_mtcnn_debug_net_tap): (raw int32 array
+        (n,H,W,C), split, c0) -- split: a word is a split-f16 (hi, lo) pair instead of an fp32 value; c0: dense index
+        of the chunk's first candidate.  Names: crops, pool1, conv2, pool2, conv3, pool3, conv4, dense, heads."""
+        hd = self._ensure(1, 12, 12)   # the handle of the previous call (the capacity only ever grows), or a fresh one: the library refuses
+        lib = _lib.load()
+        dims = (ctypes.c_int32 * 6)()
+        _lib.check(lib.vnf_mtcnn_debug_net_tap(hd, int(net), name.encode(), None, 0, dims))
+        n, H, W, C, split, c0 = (int(d) for d in dims)
+        raw = np.empty((n, H, W, C), dtype=np.int32)
+        dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(dev):
+            _lib.check(lib.vnf_mtcnn_debug_net_tap(self._handle, int(net), name.encode(), raw.ctypes.data, raw.nbytes, dims))
+        return raw, bool(split), c0
