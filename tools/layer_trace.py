@@ -6,7 +6,7 @@
 Dispatches of one stream follow the plan order.  A step ends with its l2norm dispatch, so every stream's dispatch list is
 cut into steps at the l2norm kernels; only steps with exactly the plan's number of launches count (tuning launches at
 create time form irregular groups and drop out), and EVERY dispatch must be of the kernel family its plan row names
-(stem_conv1a / stem_mid / block35 / block17_trunk / block8_chain / maxpool / avgpool / l2norm / a conv_* kernel) -- a mismatch aborts:
+(stem_conv1a / stem_mid / block35 / block17_trunk / block8_chain / mixed6a_chain / maxpool / avgpool / l2norm / a conv_* kernel) -- a mismatch aborts:
 a shifted table is worse than none.  Rows report the average device time of that launch over the traced steps, its
 algorithmic GFLOP and the achieved TFLOP/s -- measured while the other lanes' kernels share the GPU (the benchmarked
 mode), so the per-row times sum to more than the step time."""
@@ -39,6 +39,8 @@ def family(label):
         return ("block17_trunk",)
     if " chain (reduce+1x3" in label:         # repeat_3.N / block8: reduce + 1x3 + 3x1 in one launch
         return ("block8_chain",)
+    if label.startswith("mixed_6a.branch1.0-1.2 chain"):   # the three branch-1 convolutions of mixed_6a in one launch
+        return ("mixed6a_chain",)
     if label.startswith("maxpool"):
         return ("maxpool_kernel",)
     if label.startswith("avgpool"):

@@ -142,14 +142,17 @@ struct Group { int first, last, chunk; };
 
 // A run of plan ops that fused kernels replace when the compute dtype allows it (16-bit operands): the 40 convolutions
 // of repeat_2 become one launch of block17_trunk_kernel (trunk17.hip), the 25 of repeat_1 five launches of
-// block35_kernel (block35.hip), reduce + 1x3 + 3x1 of each Block8 one launch of block8_chain_kernel (block8.hip).
+// block35_kernel (block35.hip), reduce + 1x3 + 3x1 of each Block8 one launch of block8_chain_kernel (block8.hip), the
+// three branch-1 convolutions of mixed_6a one launch of mixed6a_chain_kernel (mixed6a.hip).
 struct FusedStack {
   // Block17: persistent Block17 stack (trunk17.hip); Block35: one fused launch per Block35 (block35.hip);
   // StemMid: conv2d_2a + conv2d_2b + maxpool_3a in one launch (stem_mid.hip);
   // Block8: reduce + branch1.1 + branch1.2 of one Block8 in one launch (block8.hip): conv0 = the reduce, out_buf = the
   // 384-channel concat; the block's up-projection stays a plan op behind the stack
-  enum class Kind { StemMid, Block35, Block17, Block8 } kind = Kind::Block17;
-  std::string label;           // Block8: the profile row's label (one stack per block)
+  // Mixed6a: mixed_6a.branch1.0 + branch1.1 + branch1.2 in one launch (mixed6a.hip): conv0 = the 1x1, in_buf = the
+  // repeat_1 output, out_buf = the mixed_6a output, of which the launch writes the last convolution's channel slice
+  enum class Kind { StemMid, Block35, Block17, Block8, Mixed6a } kind = Kind::Block17;
+  std::string label;           // Block8, Mixed6a: the profile row's label
   int first = 0, last = 0;     // op range
   int in_buf = -1, out_buf = -1;
   int nblocks = 0;
@@ -172,7 +175,7 @@ struct Tap { int buf, coff, C; };   // buf -2: columns [coff, coff + C) of emb_r
 // Every switch an encoder takes from the environment (VNF_<FIELD NAME>; INTEGRATION.md has the table), read once, when
 // the Encoder is constructed.  Plans, fused stacks, the autotuner and the launchers take their values from here.
 struct EncoderEnv {
-  int fuse = 95, direct_stem = 1, stem1a_mfma = 2, retina_fuse = 3, ws_persist = 1;
+  int fuse = 223, direct_stem = 1, stem1a_mfma = 2, retina_fuse = 3, ws_persist = 1;
   int stem_chunk = 0, ir100_chunk1 = 0, ir100_chunk2 = 0;   // sub-batch of the leading op groups (<= 0: the plan's default)
   int autotune = 1, force_cfg = -2, tune_lanes = 0, autotune_log = 0;
   bool tune_final = true;   // 0: no finalists pass

@@ -2,6 +2,7 @@
 #include "engine.h"
 #include "block35.h"
 #include "block8.h"
+#include "mixed6a.h"
 #include "stem_mid.h"
 #include "trunk17.h"
 
@@ -129,6 +130,45 @@ int prepare_block8(Encoder& e, FusedStack& f) {
   return VNF_OK;
 }
 
+int prepare_mixed6a(Encoder& e, FusedStack& f) {
+  if (!(e.env.fuse & 128) || e.dtype == F16P) return VNF_OK;   // the planar split-f16 dtype keeps the three plan convolutions
+  for (const FusedStack& g : e.fused)   // the Block35 stack kernel has taken branch1.0 (prepared before this stack)
+    if (g.kind == Kind::Block35 && g.active && g.ext && g.ext_conv == f.conv0) return VNF_OK;
+  const ConvLayer& c0 = e.convs[f.conv0];
+  const ConvLayer& c1 = e.convs[f.conv0 + 1];
+  const ConvLayer& c2 = e.convs[f.conv0 + 2];
+  const std::vector<Buf>& bufs = e.bufs;
+  auto plain = [](const ConvLayer& L, int cout, int K, int kh, int st, int pad, int H, int Ho) {
+    return L.cout == cout && L.K == K && L.Kpad == K && L.ncls == 1 && L.nseg == 1 && L.res_buf < 0 && L.act == ACT_RELU &&
+           !L.out_f32 && L.KH == kh && L.KW == kh && L.sh == st && L.sw == st && L.ph == pad && L.pw == pad && L.H == H &&
+           L.W == H && L.Ho == Ho && L.Wo == Ho && L.x_coff == 0 && L.seg[0].c0 == 0 && L.seg[0].c1 == cout;
+  };
+  bool ok = f.last - f.first == 3 && plain(c0, 192, 256, 1, 1, 0, 17, 17) && plain(c1, 192, 1728, 3, 1, 1, 17, 17) &&
+            plain(c2, 256, 1728, 3, 2, 0, 17, 8);
+  for (int i = 0; ok && i < 3; ++i) ok = e.ops[f.first + i].kind == Op::CONV && e.ops[f.first + i].layer == f.conv0 + i;
+  ok = ok && c0.x_buf == f.in_buf && bufs[f.in_buf].H == 17 && bufs[f.in_buf].W == 17 && bufs[f.in_buf].C == 256 &&
+       c0.seg[0].coff == 0 && bufs[c0.seg[0].buf].C == 192 && c1.x_buf == c0.seg[0].buf && c1.cin == 192 &&
+       c1.seg[0].coff == 0 && bufs[c1.seg[0].buf].C == 192 && c2.x_buf == c1.seg[0].buf && c2.cin == 192 &&
+       c2.seg[0].buf == f.out_buf && bufs[f.out_buf].H == 8 && bufs[f.out_buf].W == 8 && c2.seg[0].coff % 8 == 0 &&
+       bufs[f.out_buf].C % 8 == 0 && c2.seg[0].coff + 256 <= bufs[f.out_buf].C;
+  if (!ok) return fail(VNF_E_INVALID, "fused mixed_6a chain: unexpected layer shapes");
+  Mixed6aPack pk;
+  pk.w[0] = c0.w; pk.kpad[0] = c0.Kpad;
+  pk.w[1] = c1.w; pk.kpad[1] = c1.Kpad;
+  pk.w[2] = c2.w; pk.kpad[2] = c2.Kpad;
+  f.wstream = e.dalloc(mixed6a_stream_bytes());
+  f.bias = (float*)e.dalloc(M6_BIAS * 4);
+  if (!f.wstream || !f.bias) return VNF_E_HIP;
+  VNF_HIP(copy_bias(f.bias, c0));
+  VNF_HIP(copy_bias(f.bias + 192, c1));
+  VNF_HIP(copy_bias(f.bias + 384, c2));
+  VNF_HIP(mixed6a_repack(pk, f.wstream, 0));
+  VNF_HIP(hipDeviceSynchronize());
+  f.macs_alg = c0.macs_alg + c1.macs_alg + c2.macs_alg;
+  f.active = true;
+  return VNF_OK;
+}
+
 int prepare_block17(Encoder& e, FusedStack& f) {
   if (!(e.env.fuse & 1)) return VNF_OK;
   Trunk17Pack pk;
@@ -159,7 +199,8 @@ int prepare_block17(Encoder& e, FusedStack& f) {
 
 // env.fuse: bit 0: Block17 stack, bit 1: Block35, bit 2: stem 2a+2b+pool, bit 3: conv2d_3b inside the stem kernel, bit 4:
 // the five Block35 in one launch (with bit 1), bit 5 (off by default: measured at parity with the separate launch):
-// mixed_6a.branch1.0 inside that launch, bit 6: reduce + 1x3 + 3x1 of every Block8 in one launch (bf16 / f16)
+// mixed_6a.branch1.0 inside that launch, bit 6: reduce + 1x3 + 3x1 of every Block8 in one launch (bf16 / f16), bit 7:
+// mixed_6a.branch1.0 + 1.1 + 1.2 in one launch (bf16 / f16; bit 5, where it applies, takes branch1.0 and leaves the plan)
 int Encoder::prepare_fused() {
   for (FusedStack& f : fused) {
     f.active = false;
@@ -170,6 +211,7 @@ int Encoder::prepare_fused() {
       case Kind::Block35: rc = prepare_block35(*this, f); break;
       case Kind::Block17: rc = prepare_block17(*this, f); break;
       case Kind::Block8: rc = prepare_block8(*this, f); break;
+      case Kind::Mixed6a: rc = prepare_mixed6a(*this, f); break;
     }
     if (rc != VNF_OK) return rc;
   }
@@ -201,6 +243,7 @@ bool Encoder::buf_materialised(int buf) const {
         break;
       case Kind::Block17: produced = buf == f.out_buf; break;
       case Kind::Block8: produced = buf == f.out_buf; break;   // the concat; branch1.0 / 1x3 outputs only ever live in LDS
+      case Kind::Mixed6a: produced = buf == f.out_buf; break;  // the mixed_6a output; the two 17 x 17 tensors only live in LDS
     }
     if (!produced) return false;
   }
@@ -279,13 +322,24 @@ int Encoder::launch_fused(const FusedStack& f, int n0, int nn, hipStream_t s) {
       err = launch_block8(ba, dtype, s);
       break;
     }
+    case Kind::Mixed6a: {
+      Mixed6aArgs ma;
+      ma.x = at(f.in_buf, n0); ma.ldx = bufs[f.in_buf].C;
+      ma.y = at(f.out_buf, n0); ma.ldy = bufs[f.out_buf].C;
+      ma.coff = convs[f.conv0 + 2].seg[0].coff;
+      ma.n = nn;
+      ma.wstream = f.wstream; ma.bias = f.bias;
+      what = "fused mixed_6a chain";
+      err = launch_mixed6a(ma, dtype, s);
+      break;
+    }
   }
   return err == hipSuccess ? VNF_OK : fail(VNF_E_HIP, std::string(what) + ": " + hipGetErrorString(err));
 }
 
 const char* fused_label(const FusedStack& f) {
   if (f.kind == Kind::StemMid) return f.ext ? "conv2d_2a+2b+maxpool_3a+3b" : "conv2d_2a+2b+maxpool_3a";
-  if (f.kind == Kind::Block8) return f.label.c_str();
+  if (f.kind == Kind::Block8 || f.kind == Kind::Mixed6a) return f.label.c_str();
   return f.kind == Kind::Block35 ? "repeat_1 (fused blocks)" : "repeat_2 (persistent trunk)";
 }
 
@@ -293,6 +347,7 @@ const char* fused_detail(const FusedStack& f) {
   if (f.kind == Kind::StemMid) return "rolling rows, one launch, one workgroup per image";
   if (f.kind == Kind::Block17) return "10 x Block17 in one launch, one workgroup per image";
   if (f.kind == Kind::Block8) return "one launch, G = 3 images per workgroup, weights streamed to registers";
+  if (f.kind == Kind::Mixed6a) return "1x1 + 3x3 + 3x3 s2 in one launch, image in LDS, one workgroup per image";
   if (!f.stack) return "5 x Block35, one launch per block, one workgroup per image";
   return f.ext ? "5 x Block35 + mixed_6a.branch1.0 in one launch, x in registers"
                : "5 x Block35 in one launch, x in registers, one workgroup per image";

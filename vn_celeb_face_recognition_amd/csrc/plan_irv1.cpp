@@ -125,9 +125,18 @@ int build_irv1(Encoder& e, WeightMap& wm) {
   // ---- mixed_6a (129-149)
   {
     const int X = x35[cur], O = x17[0];
-    TRY(simple("mixed_6a.branch0", X, 0, 256, 256, 384, 3, 3, 2, 0, 0, O, 0));
+    // bf16 / f16: the three branch-1 convolutions as one image-resident launch (mixed6a.hip), unless the Block35 stack
+    // kernel has taken branch1.0.  They are listed in one run; branch0 and the pool write other channels of O
+    FusedStack f;
+    f.kind = FusedStack::Kind::Mixed6a;
+    f.label = "mixed_6a.branch1.0-1.2 chain";
+    f.first = (int)e.ops.size() - 1; f.conv0 = (int)e.convs.size() - 1;
+    f.in_buf = X; f.out_buf = O; f.nblocks = 1;
     TRY(simple("mixed_6a.branch1.1", m6a, 0, 192, 192, 192, 3, 3, 1, 1, 1, m6b, 0));
     TRY(simple("mixed_6a.branch1.2", m6b, 0, 192, 192, 256, 3, 3, 2, 0, 0, O, 384));
+    f.last = (int)e.ops.size();
+    e.fused.push_back(f);
+    TRY(simple("mixed_6a.branch0", X, 0, 256, 256, 384, 3, 3, 2, 0, 0, O, 0));
     e.ops.push_back(Op::maxpool(X, O, 640));
   }
   e.taps["mixed_6a"] = {x17[0], 0, 896};
